@@ -185,13 +185,14 @@ def weak_leg(ctx, args, world, group, per_gpu):
     return rec
 
 
-def settle(ctx, fn, n_batches, group, min_seconds=0.2):
+def settle(ctx, fn, n_batches, group, min_seconds=0.2, fixed=None):
     """Untimed set-up steps (the twin net of the two-steps-in-flight schedule is built on the first call; the GPU
     comes out of seconds of idle while the net was built: 48 + 5 steps = 10 ms of load left the first 20 timed
     steps at 193-196 us, 180 ms of load at 180-182 us, the steady state being 177 -- tools/probe_start.py: a 50 ms
     host pause alone costs the next 20 steps 25 %).  So the set-up runs for at least 0.2 s, synchronised.  Every
     rank must take the same number of steps (each one is a collective): the first 48 are timed and the count
-    that fills 0.2 s is the maximum over ranks.  Returns the number of steps taken."""
+    that fills 0.2 s is the maximum over ranks.  ``fixed`` (a multiple of 16, at least 48) replaces that count with
+    one that does not depend on the clock.  Returns the number of steps taken."""
     for i in range(32):                 # (the first call builds the twin net: not representative)
         fn.enqueue(i % n_batches)
     ctx.sync()
@@ -201,7 +202,9 @@ def settle(ctx, fn, n_batches, group, min_seconds=0.2):
     ctx.sync()
     per_step = max((time.perf_counter() - t_setup) / 16, 1e-6)
     more = float(min(20000, max(0, int(min_seconds / per_step) - 48)))
-    if group is not None:
+    if fixed is not None:
+        more = float(fixed - 48)
+    elif group is not None:
         more = group.rdzv.gather_max(more)
     n_setup = 48 + 16 * ((int(more) + 15) // 16)
     for i in range(48, n_setup):
@@ -362,6 +365,37 @@ def shard_leg(ctx, steps, rows=512):
             os.environ.pop("TN_DP_FORCE", None)
         else:
             os.environ["TN_DP_FORCE"] = old
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SETUP_STEPS = 1024     # set-up steps of a --dump-outputs run (the 0.2 s set-up of the default workload is ~1040)
+
+
+def dump_outputs(out_dir, outs, net):
+    """--dump-outputs: what the last timed step computed, as <out_dir>/<name>.npy in float32 -- the step's
+    [cost, features, logprob] (fn.fetch(), what a caller of the step receives; features only where the head has
+    its own) and every layer's weights after the step's update.  Past DUMP_LIMIT_BYTES in all, every array is
+    cut to a fixed, seeded sample of its flat elements.  Returns {name: shape written}."""
+    cost, feats, logprob = outs
+    arrays = {"cost": np.asarray([cost]), "logprob": logprob}
+    if feats is not logprob:
+        arrays["features"] = feats
+    for i, lyr in enumerate(net.tr_layers):
+        for k, w in enumerate(lyr.get_wts()):
+            arrays["w%d_%s_%d" % (i, type(lyr).__name__, k)] = w
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total, room = sum(a.nbytes for a in arrays.values()), DUMP_LIMIT_BYTES - 256 * len(arrays)    # (.npy headers)
+    if total > room:
+        scale = room / total
+        for k, a in arrays.items():
+            keep = max(1, int(a.size * scale))
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                arrays[k] = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 DTYPE_LABEL = {"f32": "f32", "f16": "f16 (fp16 tensors and MFMA operands, fp32 accumulate, fp32 master weights)",
@@ -536,8 +570,14 @@ def main():
                     help="one step at a time (TN_PIPELINE=0) instead of two steps in flight")
     ap.add_argument("--time-op", default="", help="C-ABI function to bracket with HIP events, "
                     "e.g. tn_fc_wgrad:1 (nth call inside a step)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (cost, logprob, the weights after its update) as "
+                         "DIR/<name>.npy; the set-up then takes a fixed %d steps, so that two builds start the timed "
+                         "steps from the same weights" % DUMP_SETUP_STEPS)
     ap.add_argument("--dp-selfcheck-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dp_selfcheck_child:
         sys.exit(dp_selfcheck_child())
 
@@ -593,7 +633,7 @@ def main():
         fn.enqueue(tune_steps % n_batches)
         tune_steps += 1
     progress["phase"] = "set-up steps (schedule %s)" % getattr(net, "dp_schedule", "single GPU")
-    setup_steps = tune_steps + settle(ctx, fn, n_batches, group)
+    setup_steps = tune_steps + settle(ctx, fn, n_batches, group, fixed=DUMP_SETUP_STEPS if args.dump_outputs else None)
     progress["phase"] = "warm-up steps"
     for i in range(args.warmup):
         fn.enqueue(i % n_batches)
@@ -609,8 +649,10 @@ def main():
     dt = time.perf_counter() - t0
     if group is not None:
         dt = group.rdzv.gather_max(dt)
-    cost = fn.fetch()[0]
+    outs = fn.fetch()
+    cost = outs[0]
     assert np.isfinite(cost), "training diverged"
+    dumped = dump_outputs(args.dump_outputs, outs, net) if args.dump_outputs and world.rank == 0 else None
     # (what the watchdog prints should a LATER leg hang: the headline is measured)
     progress["line"] = {"metric": "training images/sec (fwd+bwd+update) MNIST-CNN bs4096, 1/2/4/8 MI355X",
                         "value": tr["BATCH_SZ"] * args.steps / dt, "unit": "images/sec", "n_gpus": world.size,
@@ -777,6 +819,8 @@ def main():
     }
     if selfcheck is not None:
         line["dp_selfcheck"] = selfcheck
+    if dumped is not None:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     # N > 1: `value` is STRONG scaling, as BASELINE configs[2] states it (the global batch sharded N ways).  The same
     # launch then times the WEAK form (the stated batch per GPU, N times the global batch) and reports it beside it:
     # for mnist.prms the strong figure is bounded by the kernels' fixed costs at 4096/N rows,

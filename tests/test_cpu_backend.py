@@ -296,6 +296,32 @@ def test_bench_two_ranks_reports_strong_and_weak_scaling():
     assert sc["rel_diff"] <= 1e-5 and sc["default"]["collectives"] > sc["plain"]["collectives"]
 
 
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs DIR on the CPU backend: exactly --steps timed steps, ms_per_step in the line, and what
+    the last timed step computed (cost, logprob, the weights after its update) as float32 .npy files under 64 MB --
+    the same, bit for bit, from a second run with the same arguments."""
+    import json
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("d%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "64", "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(d)],
+                           cwd=ROOT, env=_env(OMP_NUM_THREADS="2"), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip())
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        names = sorted(os.listdir(d))
+        assert sorted(n + ".npy" for n in line["dump_outputs"]["arrays"]) == names
+        assert {"cost.npy", "logprob.npy"} <= set(names) and len(names) > 2
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 << 20
+        arrays = {n: np.load(d / n) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["logprob.npy"].shape == (64, 10) and np.isfinite(arrays["cost.npy"]).all()
+        dumps.append(arrays)
+    for n, a in dumps[0].items():
+        np.testing.assert_array_equal(dumps[1][n], a, err_msg=n)
+
+
 def _bench_ranks(world, extra_env, timeout=300):
     import json
     s = socket.socket()

@@ -229,37 +229,67 @@ def test_fd_gradients_float64(same):
                 assert abs(fd - an) <= 1e-6 + 1e-5 * abs(fd), (i, j, idx, fd, an)
 
 
-def test_torch_cross_check_forward_backward():
+# The torch half of the cross-check runs in a child process: torch's wheel carries its own HIP and HSA runtimes, and
+# loading them into a process that already holds the product's (libtheanet_hip.so, loaded by the GPU tests of the same
+# pytest run) leaves two copies of the runtime whose teardown aborts the process at exit.
+TORCH_SIDE = r"""
+import sys
+import numpy as np
+import torch
+import torch.nn.functional as F
+d = dict(np.load(sys.argv[1]))
+out = {}
+for mode, pad in (("valid", 0), ("same", 1)):
+    xt = torch.tensor(d["x"], requires_grad=True); Wt = torch.tensor(d["W"], requires_grad=True)
+    zt = F.conv2d(xt, torch.flip(Wt, (2, 3)), torch.tensor(d["b"]), padding=pad)
+    zt.backward(torch.tensor(d["dz_" + mode]))
+    out["z_" + mode], out["dx_" + mode], out["dW_" + mode] = zt.detach().numpy(), xt.grad.numpy(), Wt.grad.numpy()
+xt = torch.tensor(d["xp"], requires_grad=True)
+yt = F.max_pool2d(xt, 2, ceil_mode=True)
+yt.backward(torch.tensor(d["dy"]))
+out["yp"], out["dxp"] = yt.detach().numpy(), xt.grad.numpy()
+zt = torch.tensor(d["zs"], requires_grad=True)
+lt = F.nll_loss(F.log_softmax(zt, 1), torch.tensor(d["ys"])); lt.backward()
+out["nll"], out["dzs"] = np.float64(lt.item()), zt.grad.numpy()
+np.savez(sys.argv[2], **out)
+"""
+
+
+def test_torch_cross_check_forward_backward(tmp_path):
     """Independent second implementation (torch CPU autograd) on tie-free data."""
-    torch = pytest.importorskip("torch")
-    import torch.nn.functional as F
+    import importlib.util
+    import subprocess
+    import sys
+    if importlib.util.find_spec("torch") is None:
+        pytest.skip("could not import 'torch'")
     rng = np.random.RandomState(5)
     x = rng.rand(3, 2, 8, 8); W = rng.randn(4, 2, 3, 3); b = rng.randn(4)
-    for mode, pad in (("valid", 0), ("same", 1)):
-        z = O.conv2d_fwd(x, W, b, 1, mode)
-        xt = torch.tensor(x, requires_grad=True); Wt = torch.tensor(W, requires_grad=True)
-        zt = F.conv2d(xt, torch.flip(Wt, (2, 3)), torch.tensor(b), padding=pad)
-        np.testing.assert_allclose(z, zt.detach().numpy(), atol=1e-12)
-        dz = rng.randn(*z.shape)
-        zt.backward(torch.tensor(dz))
-        dx, dW, db = O.conv2d_bwd(x, W, dz, 1, mode)
-        np.testing.assert_allclose(dx, xt.grad.numpy(), atol=1e-12)
-        np.testing.assert_allclose(dW, Wt.grad.numpy(), atol=1e-11)
-        np.testing.assert_allclose(db, dz.sum((0, 2, 3)), atol=1e-12)
+    inp, z, dz = {"x": x, "W": W, "b": b}, {}, {}
+    for mode in ("valid", "same"):
+        z[mode] = O.conv2d_fwd(x, W, b, 1, mode)
+        dz[mode] = inp["dz_" + mode] = rng.randn(*z[mode].shape)
     # ceil-mode max pool + its gradient
-    x = rng.rand(2, 3, 7, 7)
-    xt = torch.tensor(x, requires_grad=True)
-    yt = F.max_pool2d(xt, 2, ceil_mode=True)
-    np.testing.assert_array_equal(O.pool_fwd(x, 2), yt.detach().numpy())
-    dy = rng.randn(*yt.shape); yt.backward(torch.tensor(dy))
-    np.testing.assert_allclose(O.pool_bwd(x, dy, 2), xt.grad.numpy())
+    xp = rng.rand(2, 3, 7, 7)
+    dy = rng.randn(*O.pool_fwd(xp, 2).shape)
     # log-softmax + nll gradient
-    z = rng.randn(6, 5); y = rng.randint(0, 5, 6)
-    zt = torch.tensor(z, requires_grad=True)
-    lt = F.nll_loss(F.log_softmax(zt, 1), torch.tensor(y)); lt.backward()
-    lp = O.log_softmax(z)
-    np.testing.assert_allclose(O.nll(lp, y), lt.item(), rtol=1e-12)
-    np.testing.assert_allclose(O.nll_dlogits(lp, y), zt.grad.numpy(), atol=1e-12)
+    zs = rng.randn(6, 5); ys = rng.randint(0, 5, 6)
+    inp.update(xp=xp, dy=dy, zs=zs, ys=ys)
+    np.savez(tmp_path / "in.npz", **inp)
+    r = subprocess.run([sys.executable, "-c", TORCH_SIDE, str(tmp_path / "in.npz"), str(tmp_path / "out.npz")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    t = np.load(tmp_path / "out.npz")
+    for mode in ("valid", "same"):
+        np.testing.assert_allclose(z[mode], t["z_" + mode], atol=1e-12)
+        dx, dW, db = O.conv2d_bwd(x, W, dz[mode], 1, mode)
+        np.testing.assert_allclose(dx, t["dx_" + mode], atol=1e-12)
+        np.testing.assert_allclose(dW, t["dW_" + mode], atol=1e-11)
+        np.testing.assert_allclose(db, dz[mode].sum((0, 2, 3)), atol=1e-12)
+    np.testing.assert_array_equal(O.pool_fwd(xp, 2), t["yp"])
+    np.testing.assert_allclose(O.pool_bwd(xp, dy, 2), t["dxp"])
+    lp = O.log_softmax(zs)
+    np.testing.assert_allclose(O.nll(lp, ys), t["nll"], rtol=1e-12)
+    np.testing.assert_allclose(O.nll_dlogits(lp, ys), t["dzs"], atol=1e-12)
 
 
 def _xchk_net(dtype):
