@@ -196,6 +196,16 @@ int tn_c8_conv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int 
                      const void* prev_a, int prev_act, float prev_prm, int pooled, const uint8_t* mask, const void* wt);
 int tn_c8_conv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int H, int Wd,
                      int K, int pooled, const uint8_t* mask);
+/* Which kernel instantiation a call of this shape launches -- the launchers' own selection, made without a context
+ * (the current device's CU count; 256 where no GPU answers).  op 0: tn_c8_conv_fwd, 1: tn_c8_conv_dgrad (act / prm:
+ * the layer below's), 2: tn_c8_conv_wgrad (act / prm unused); pool: the fused 2x2 max-pool / pooled-gradient form.
+ * Writes up to nout ints to out and returns how many the plan has; TN_E_ARG when the call would refuse the shape
+ * (and always on the CPU backend).
+ *   op 0, 1: FT, MODE, NS, LK, TK (c8_conv_kernel<FT, MODE, NS, LK, TK>), NI images per pixel tile, RT pixel tiles per
+ *            image, KT filter tiles, MT pixel tiles
+ *   op 2:    form (1: c8_wgrad_tr_kernel<NCT, NGX, POOL, ROLL>, 0: c8_wgrad_kernel<NFT, NCT, POOL, NGX, TM, ROLL>), NFT,
+ *            NCT, NGX, TM, ROLL, nstage, NI, S slabs, tiles per slab, tiles, KG filter groups, CG channel groups */
+int tn_c8_conv_plan(int op, int N, int C, int H, int W, int K, int pool, int act, float prm, int* out, int nout);
 /* fully-connected products on an fp16-resident input (replaces hidden.py:30 and its gradients, layer.py:83, for the
  * first dense layer above a c8 conv stack; theanet_amd/csrc/fc_c8.hip): x16 (B, ceil(C/8)*HW*8) halfs is the flattened
  * c8 tensor of C maps of HW pixels (HW = 1: a plain half matrix), W (C*HW, n_out) fp32 keeps the reference's

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 GS = 1024.0
 LEAKY, SLOPE = 1, .1          # TN_ACT_LEAKY (include/theanet_hip.h enum tn_act)
+ACTS = {"leaky": (LEAKY, SLOPE), "tanh": (2, 0.), "sigmoid": (3, 0.)}      # TN_ACT_TANH, TN_ACT_SIGMOID: the generic epilogue
 
 
 @pytest.fixture
@@ -38,18 +39,19 @@ def _rel(got, want):
     return float(np.abs(got - want).max() / np.abs(want).max())
 
 
-def _assert_masks_equal_up_to_provable_near_ties(gotm, bits, a, x, W16, b, C):
+def _assert_masks_equal_up_to_provable_near_ties(gotm, bits, a, x, W16, b, C, fn_err=0.):
     """Index work is bit-exact: every mask byte equals the specification's -- except where the device's fp32 sums and the
     specification's float64 sums may PROVABLY order two window elements differently: a window bit may differ only if
     that element lies within the fp32 accumulation bound of the window maximum, a sign bit only if the maximum lies
     within it of zero.  Bound per pre-activation: (9 C + 2) u * (sum |x| |w| + |b|), u = 2^-24 (n fp32 additions of exact
-    fp16 x fp16 products); the leaky ReLU is monotone with slope <= 1, so the bound carries over to the activations."""
+    fp16 x fp16 products); the leaky ReLU, tanh and the logistic are monotone with slope <= 1, so the bound carries over
+    to the activations, plus fn_err for the device's fp32 tanhf / expf (a few ulps of values of magnitude <= 1)."""
     bad = gotm != bits
     if not bad.any():
         return
     assert bad.mean() < 1e-3, "mask mismatches are not rare: %g" % bad.mean()
     absum = U.conv_same(np.abs(x), np.abs(W16)) + np.abs(b)[None, :, None, None]
-    tol = (9 * C + 2) * 2.0 ** -24 * absum
+    tol = (9 * C + 2) * 2.0 ** -24 * absum + fn_err
     N, K, H, _ = a.shape
     aw = a.reshape(N, K, H // 2, 2, H // 2, 2)
     tw = tol.reshape(N, K, H // 2, 2, H // 2, 2)
@@ -71,56 +73,115 @@ C8_CASES = [  # N, C, H, K
     (520, 3, 32, 32), (131, 5, 64, 40), (2100, 8, 16, 32),      # first layers with enough pixels for 512-pixel weight-gradient tiles
     (40, 32, 16, 64), (21, 32, 8, 64), (6, 24, 32, 96),           # 32-channel layers (conv2 of cifar_like): the sixteen-wave weight gradient with two step subsets
 ]
+C8_CASES += [  # what tests/test_c8_dispatch.py found unreached: each case adds (instantiation, edge) pairs no other case has
+    (7, 40, 8, 32), (3, 44, 16, 48),              # 32-filter weight gradients over 64 channels (NFT 1, NCT 2), C % 8 != 0
+    (4099, 4, 8, 16), (2101, 8, 16, 32),          # first-layer tiles of several images with a partial last one
+    (5, 12, 32, 64), (5, 1, 8, 40), (1, 12, 16, 8),
+    (3, 20, 8, 40), (2, 44, 8, 24),               # 8x8 maps of <= 3 images: the leaky epilogue with two slots (NS 2)
+]
+C8_GENERIC_ACTS = ["tanh", "sigmoid"]
+C8_ACT_NAMES = ["leaky"] + C8_GENERIC_ACTS
+C8_FWD_CASES = [(2, 20, 128, 40), (2, 44, 128, 24)]
 
 
-@pytest.mark.parametrize("case", C8_CASES)
-def test_c8_conv_ops(case, f16_mode):
-    from theanet_amd import _lib
-    assert _lib.TN_ACT_LEAKY == LEAKY
+def _act(name, z):
+    if name == "leaky":
+        return U.leaky(z, SLOPE)
+    return np.tanh(z) if name == "tanh" else 1 / (1 + np.exp(-z))
+
+
+def _act_grad_from_out(name, y):
+    if name == "leaky":
+        return U.leaky_grad_from_out(y, SLOPE)
+    return 1 - y * y if name == "tanh" else y * (1 - y)
+
+
+def _conv_fwd_dgrad(case, name):
+    """Forward, forward + 2x2 max-pool + mask, input gradient and input gradient of a pooled block of one shape, the
+    epilogue's activation `name` (the layer's own in the forward, the layer below's in the input gradients).  Returns
+    what the weight gradient of the same layer reads."""
     N, C, H, K = case
+    act, prm = ACTS[name]
     rng = np.random.RandomState(0)
-    lib = ctx().lib
-    assert lib.tn_c8_conv_supported(N, C, H, H, K, 3, 1, 1) and lib.tn_c8_conv_wgrad_supported(N, C, H, H, K)
     x = U.r16(rng.randn(N, C, H, H))
     W = (rng.randn(K, C, 3, 3) / np.sqrt(9 * C)).astype(np.float32)
     b = (rng.randn(K) * .1).astype(np.float32)
     W16 = U.r16(W)
-    a = U.leaky(U.conv_same(x, W16) + b[None, :, None, None], SLOPE)
+    a = _act(name, U.conv_same(x, W16) + b[None, :, None, None])
     xd, Wd, bd = _c8(x), dev(W), dev(b)
     K8, C8, Hp = K // 8, (C + 7) // 8, H // 2
     # forward
     out = empty((N, K8, H, H, 8), np.uint16)
-    call("tn_c8_conv_fwd", xd.ptr, Wd.ptr, bd.ptr, out.ptr, None, N, C, H, H, K, LEAKY, SLOPE, 0, None)
+    call("tn_c8_conv_fwd", xd.ptr, Wd.ptr, bd.ptr, out.ptr, None, N, C, H, H, K, act, prm, 0, None)
     assert _rel(U.from_c8(out.get_value().view(np.float16), K), U.r16(a)) < 1e-3
     # forward + 2x2 max-pool + mask (ties: every window element equal to the maximum)
     pm, bits = U.pool2(a)
     outp, mk = empty((N, K8, Hp, Hp, 8), np.uint16), empty((N, K8, Hp, Hp, 8), np.uint8)
-    call("tn_c8_conv_fwd", xd.ptr, Wd.ptr, bd.ptr, outp.ptr, mk.ptr, N, C, H, H, K, LEAKY, SLOPE, 1, None)
+    call("tn_c8_conv_fwd", xd.ptr, Wd.ptr, bd.ptr, outp.ptr, mk.ptr, N, C, H, H, K, act, prm, 1, None)
     assert _rel(U.from_c8(outp.get_value().view(np.float16), K), U.r16(pm)) < 1e-3
     gotm = mk.get_value().transpose(0, 1, 4, 2, 3).reshape(N, K, Hp, Hp)
-    _assert_masks_equal_up_to_provable_near_ties(gotm, bits, a, x, W16, b, C)
+    _assert_masks_equal_up_to_provable_near_ties(gotm, bits, a, x, W16, b, C, 0. if name == "leaky" else 2.0 ** -21)
     # input gradient: dz (halfs at the gradient scale) -> dx * act'(output of the layer below), stored as halfs
     dz = U.r16(GS * rng.randn(N, K, H, H) * 1e-3)
-    prev = U.r16(rng.randn(N, C, H, H))
-    prev[0, 0, 0, :2] = 0                              # exact zeros: the tie derivative 1 + slope
-    dxw = U.conv_same_dgrad(dz, W16) * U.leaky_grad_from_out(prev, SLOPE)
+    if name == "leaky":
+        prev = U.r16(rng.randn(N, C, H, H))
+        prev[0, 0, 0, :2] = 0                          # exact zeros: the tie derivative 1 + slope
+    else:
+        prev = U.r16(_act(name, 2 * rng.randn(N, C, H, H)))
+    dxw = U.conv_same_dgrad(dz, W16) * _act_grad_from_out(name, prev)
     dzd, pd = _c8(dz), _c8(prev)
     dxo = empty((N, C8, H, H, 8), np.uint16)
-    call("tn_c8_conv_dgrad", dzd.ptr, Wd.ptr, dxo.ptr, N, C, H, H, K, pd.ptr, LEAKY, SLOPE, 0, None, None)
+    call("tn_c8_conv_dgrad", dzd.ptr, Wd.ptr, dxo.ptr, N, C, H, H, K, pd.ptr, act, prm, 0, None, None)
     assert _rel(U.from_c8(dxo.get_value().view(np.float16), C), U.r16(dxw)) < 1e-3
     # ... of a pooled block: dz = (window bit of the device's own mask) ? pooled gradient : 0
     g = U.r16(GS * rng.randn(N, K, Hp, Hp) * 1e-3)
     gd = _c8(g)
     dzp = U.unpool_dz(g, gotm)
-    call("tn_c8_conv_dgrad", gd.ptr, Wd.ptr, dxo.ptr, N, C, H, H, K, pd.ptr, LEAKY, SLOPE, 1, mk.ptr, None)
-    dxw2 = U.conv_same_dgrad(dzp, W16) * U.leaky_grad_from_out(prev, SLOPE)
+    call("tn_c8_conv_dgrad", gd.ptr, Wd.ptr, dxo.ptr, N, C, H, H, K, pd.ptr, act, prm, 1, mk.ptr, None)
+    dxw2 = U.conv_same_dgrad(dzp, W16) * _act_grad_from_out(name, prev)
     assert _rel(U.from_c8(dxo.get_value().view(np.float16), C), U.r16(dxw2)) < 1e-3
+    return x, xd, dz, dzd, gd, dzp, mk
+
+
+@pytest.mark.parametrize("case", C8_CASES)
+def test_c8_conv_ops(case, f16_mode):
+    """The four conv products of a layer with the leaky-ReLU epilogue, each against the stored-fp16 specification, and
+    the weight gradient, plain and gathered from a pooled gradient."""
+    from theanet_amd import _lib
+    assert _lib.TN_ACT_LEAKY == LEAKY
+    N, C, H, K = case
+    lib = ctx().lib
+    assert lib.tn_c8_conv_supported(N, C, H, H, K, 3, 1, 1) and lib.tn_c8_conv_wgrad_supported(N, C, H, H, K)
+    x, xd, dz, dzd, gd, dzp, mk = _conv_fwd_dgrad(case, "leaky")
     # weight / bias gradient (fp32 results, scale removed), plain and gathered
     gW, gb = empty((K, C, 3, 3)), empty((K,))
     for pooled, src, dzz in ((0, dzd, dz), (1, gd, dzp)):
         call("tn_c8_conv_wgrad", xd.ptr, src.ptr, gW.ptr, gb.ptr, N, C, H, H, K, pooled, mk.ptr if pooled else None)
-        assert _rel(gW.get_value(), U.conv_same_wgrad(x, dzz) / GS) < 2e-5
+        assert _rel(gW.get_value(), _wgrad_blas(x, dzz) / GS) < 2e-5
         assert _rel(gb.get_value(), dzz.sum(axis=(0, 2, 3)) / GS) < 2e-5
+
+
+@pytest.mark.parametrize("name", C8_GENERIC_ACTS)
+@pytest.mark.parametrize("case", C8_CASES)
+def test_c8_conv_ops_generic_activation(case, name, f16_mode):
+    """The four conv products of test_c8_conv_ops with an activation outside the leaky-ReLU family: the generic epilogue
+    of every mode (the weight gradient has no activation: test_c8_conv_ops covers it)."""
+    from theanet_amd import _lib
+    assert (_lib.TN_ACT_TANH, _lib.TN_ACT_SIGMOID) == (ACTS["tanh"][0], ACTS["sigmoid"][0])
+    N, C, H, K = case
+    assert ctx().lib.tn_c8_conv_supported(N, C, H, H, K, 3, 1, 1)
+    _conv_fwd_dgrad(case, name)
+
+
+@pytest.mark.parametrize("name", C8_ACT_NAMES)
+@pytest.mark.parametrize("case", C8_FWD_CASES)
+def test_c8_conv_ops_128_pixel_rows(case, name, f16_mode):
+    """Rows of 128 pixels: the forward and input-gradient kernels take them (the leaky epilogue with four slots of
+    staged cells per thread, NS = 4); the weight gradient does not."""
+    N, C, H, K = case
+    lib = ctx().lib
+    assert lib.tn_c8_conv_supported(N, C, H, H, K, 3, 1, 1) and not lib.tn_c8_conv_wgrad_supported(N, C, H, H, K)
+    _conv_fwd_dgrad(case, name)
 
 
 def _wgrad_blas(x, dz):
@@ -137,12 +198,20 @@ def _wgrad_blas(x, dz):
     return dW
 
 
-@pytest.mark.parametrize("case", [(44, 128, 32, 128), (70, 64, 64, 64), (19, 32, 64, 96), (2049, 16, 32, 32), (21, 40, 32, 72)])
+WGRAD_RING_CASES = [(44, 128, 32, 128), (70, 64, 64, 64), (19, 32, 64, 96), (2049, 16, 32, 32), (21, 40, 32, 72),
+                    # (instantiation, edge) pairs of tests/test_c8_dispatch.py no case above reaches: 8-filter layers
+                    # (a partial 32-filter tile), short last slabs, image tails of first-layer tiles, C % 8 != 0
+                    (257, 12, 8, 8), (513, 1, 8, 8), (257, 1, 8, 72), (1, 12, 32, 8), (65, 68, 16, 8), (129, 68, 8, 8),
+                    (129, 12, 8, 72), (257, 1, 32, 8), (17, 68, 32, 8), (65, 68, 8, 72), (2049, 1, 16, 8), (1025, 1, 8, 136)]
+
+
+@pytest.mark.parametrize("case", WGRAD_RING_CASES)
 def test_c8_wgrad_rolling_ring_over_many_tiles(case, f16_mode):
     """The weight gradient's rolling x ring (c8_wgrad_kernel ROLL: rows of >= 32 pixels, one image band per tile) with SEVERAL
     tiles per slab: the ring wraps (four regions), slabs start in the middle of an image (the row above comes from the
     tile in front of the slab) and cross image boundaries (zero row), the last slab is short, channel / filter planes
-    beyond the tensors (re-read, never stored); plain and gathered from a pooled gradient with a random mask.  convpool.py:54-56 (CorrMM_gradWeights); numbers as in test_c8_conv_ops."""
+    beyond the tensors (re-read, never stored); plain and gathered from a pooled gradient with a random mask.  convpool.py:54-56 (CorrMM_gradWeights); numbers as in test_c8_conv_ops.
+    The cases after the first five are weight-gradient variants and edges tests/test_c8_dispatch.py found unreached."""
     N, C, H, K = case
     rng = np.random.RandomState(11)
     assert ctx().lib.tn_c8_conv_wgrad_supported(N, C, H, H, K)
@@ -261,3 +330,23 @@ def test_c8_unsupported_shapes_are_errors_not_fallbacks(f16_mode):
                    ("ConvLayer", {"num_maps": 16, "filter_sz": 3, "stride": 1, "mode": "same"}),
                    ("SoftmaxLayer", {"n_out": 10})], dict(tp))
     ctx().set_matmul_dtype("float32")
+
+
+def c8_launches():
+    """Every tn_c8_conv_{fwd, dgrad, wgrad} call the tests above make, as (op, N, C, H, K, pool, act, prm) with op 0 / 1 / 2
+    = fwd / dgrad / wgrad: tests/test_c8_dispatch.py checks on the CPU that they reach every kernel instantiation and
+    every edge of each."""
+    out = []
+    for N, C, H, K in C8_CASES:
+        for name in C8_ACT_NAMES:
+            act, prm = ACTS[name]
+            out += [(op, N, C, H, K, pool, act, prm) for op in (0, 1) for pool in (0, 1)]
+        out += [(2, N, C, H, K, pool, 0, 0.) for pool in (0, 1)]
+    for N, C, H, K in C8_FWD_CASES:
+        for name in C8_ACT_NAMES:
+            act, prm = ACTS[name]
+            out += [(op, N, C, H, K, pool, act, prm) for op in (0, 1) for pool in (0, 1)]
+    for N, C, H, K in WGRAD_RING_CASES:
+        out += [(2, N, C, H, K, pool, 0, 0.) for pool in (0, 1)]
+    out.append((0, 3, 16, 16, 24, 0) + ACTS["tanh"])          # test_c8_generic_activation_and_pack_roundtrip
+    return out

@@ -314,8 +314,16 @@ def test_full_size_gradients_mnist(B):
                 #    runs of four at 3 x 4096 rows x 500 units).
                 # Two such events in one tensor and one step fit the bound; anything systematic is orders of magnitude above it.
                 tol = 2e-3
-                assert np.abs(g - g_w).max() <= tol * np.abs(g_w).max(), \
-                    ("grad", s, i, j, np.abs(g - g_w).max(), np.abs(g_w).max())
+                err, gmax = np.abs(g - g_w), np.abs(g_w).max()
+                assert err.max() <= tol * gmax, ("grad", s, i, j, err.max(), gmax)
+                # ... and in bulk, for the dense layers: there such an event touches one column of W (1/500 of fc1's
+                # entries) or one bias entry, so the 99th percentile of the error stays at the typical agreement (3e-7 of
+                # the largest entry measured on the GPU); a systematic error does not.  (Not for the conv layers: a
+                # misrouted pooling window moves every tap of its filter, a quarter of conv1's 36 weights -- 1.3e-4 of the
+                # largest entry at the 99th percentile measured at 512 images.)
+                if prms["layers"][i][0] in ("HiddenLayer", "SoftmaxLayer"):
+                    p99 = np.percentile(err, 99) / gmax
+                    assert p99 <= 1e-5, ("grad bulk", s, i, j, p99, np.linalg.norm(err) / np.linalg.norm(g_w))
                 seen += 1
         assert seen == 8
         vel_prev = [[a.astype(np.float64) for a in row] for row in vel]

@@ -90,6 +90,7 @@ SIGNATURES = {
     "tn_c8_conv_fwd": (c_int, [CTX, P, P, P, P, P] + [c_int] * 6 + [c_float, c_int, P]),
     "tn_c8_conv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 5 + [P, c_int, c_float, c_int, P, P]),
     "tn_c8_conv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_int, P]),
+    "tn_c8_conv_plan": (c_int, [c_int] * 8 + [c_float, POINTER(c_int), c_int]),
     "tn_c8_fc_supported": (c_int, [c_int] * 4),
     "tn_c8_fc_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_float, P]),
     "tn_c8_fc_fwd_dropout": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_float, P, c_float, c_uint64, c_uint32, P, c_uint64]),

@@ -605,6 +605,7 @@ static int c8_geometry(C8G& g, int FT, int K, int C, bool tk = false) {
 }
 
 static int c8_pick_ft(int K) { return K > 32 ? 2 : 1; }
+static bool c8_tap_packed(int C, int dgrad) { return !dgrad && C <= 8; }     // the tap-packed forward form (C <= 8)
 
 static size_t c8_lds_bytes(const C8G& g, int FT) { return (size_t)2 * (2 * g.plane * 16 + 9 * 2 * 32 * FT * 16); }
 
@@ -615,10 +616,27 @@ extern "C" int tn_c8_dbg_read(tn_ctx* ctx, unsigned long long* host, int nblocks
     return hipMemcpy(host, c8_dbg_buf, (size_t)nblocks * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
 }
 
-template <int FT, int MODE, bool TK = false>
-static int c8_launch(tn_ctx* ctx, C8G& g) {
-    const size_t lds = c8_lds_bytes(g, FT);
+// The instantiation c8_run launches for a shape: c8_conv_kernel<FT, MODE, NS, LK, TK>.  c8_plan makes the whole choice
+// (and fills the geometry); c8_run and c8_launch only map it onto templates, and tn_c8_conv_plan reports it.
+struct C8Plan { int FT, NS, LK, TK; };
+
+static int c8_plan(tn_ctx* ctx, C8G& g, int MODE, int K, int C, C8Plan& p) {
+    p.FT = c8_pick_ft(K);
+    p.TK = MODE < 2 && c8_tap_packed(C, 0);
+    TN_REQUIRE(c8_geometry(g, p.FT, K, C, p.TK) && c8_lds_bytes(g, p.FT) <= 156 * 1024, "c8 conv: unsupported shape %dx%d", g.H, g.W);
+    TN_REQUIRE((long long)g.N * g.C8 * g.H * g.W < (1ll << 28) && (long long)g.N * g.K8 * g.H * g.W < (1ll << 28),
+               "c8 conv: tensor too large for 32-bit cell offsets");
+    // the epilogue's activation (forward: the layer's own; gradients: that of the layer below) is a compile-time
+    // leaky-ReLU for the reference's defaults; other kinds share one generic instantiation per mode
+    p.LK = g.act == TN_ACT_LEAKY && g.prm >= 0.f && g.prm < 1.f;
     const int ns = cdiv(g.nslots, 256);
+    p.NS = !p.LK ? 4 : ns <= 2 ? 2 : ns == 3 ? 3 : 4;
+    return TN_OK;
+}
+
+template <int FT, int MODE, bool TK = false>
+static int c8_launch(tn_ctx* ctx, C8G& g, const C8Plan& p) {
+    const size_t lds = c8_lds_bytes(g, FT);
     g.nwork = 8 * cdiv(g.MT, 8) * g.KT;
     // two resident blocks per CU, each walking over its work items; three for the 32-filter kernels (their registers and
     // LDS allow it): another wave per SIMD under their epilogues
@@ -644,12 +662,9 @@ static int c8_launch(tn_ctx* ctx, C8G& g) {
         }                                                                                                     \
         c8_conv_kernel<FT, MODE, NS, LK, TK><<<grid, 256, lds, ctx->stream>>>(g);                             \
     }
-    // the epilogue's activation (forward: the layer's own; gradients: that of the layer below) is a compile-time
-    // leaky-ReLU for the reference's defaults; other kinds share one generic instantiation per mode
-    const bool lk = g.act == TN_ACT_LEAKY && g.prm >= 0.f && g.prm < 1.f;
-    if (!lk) C8_GO(4, false)
-    else if (ns <= 2) C8_GO(2, true)
-    else if (ns == 3) C8_GO(3, true)
+    if (!p.LK) C8_GO(4, false)
+    else if (p.NS == 2) C8_GO(2, true)
+    else if (p.NS == 3) C8_GO(3, true)
     else C8_GO(4, true)
 #undef C8_GO
     TN_LAUNCH_CHECK();
@@ -663,7 +678,6 @@ static size_t c8_wt_elems(int K, int C) {
 }
 
 // halfs the arranging kernels write for a (K filters, C channels) product; tk: the tap-packed forward form (C <= 8)
-static bool c8_tap_packed(int C, int dgrad) { return !dgrad && C <= 8; }
 static size_t c8_wt_total(int K, int C, int dgrad) {
     const int KBF = 32 * c8_pick_ft(K);
     return c8_tap_packed(C, dgrad) ? (size_t)cdiv(K, KBF) * 5 * 2 * KBF * 8 : c8_wt_elems(K, C);
@@ -671,11 +685,11 @@ static size_t c8_wt_total(int K, int C, int dgrad) {
 
 template <int MODE>
 static int c8_run(tn_ctx* ctx, C8G& g, const float* W, int K, int C, const void* wt_ready) {
-    const int FT = c8_pick_ft(K);
-    const bool tk = MODE < 2 && c8_tap_packed(C, 0);
-    TN_REQUIRE(c8_geometry(g, FT, K, C, tk) && c8_lds_bytes(g, FT) <= 156 * 1024, "c8 conv: unsupported shape %dx%d", g.H, g.W);
-    TN_REQUIRE((long long)g.N * g.C8 * g.H * g.W < (1ll << 28) && (long long)g.N * g.K8 * g.H * g.W < (1ll << 28),
-               "c8 conv: tensor too large for 32-bit cell offsets");
+    C8Plan p;
+    const int prc = c8_plan(ctx, g, MODE, K, C, p);
+    if (prc) return prc;
+    const int FT = p.FT;
+    const bool tk = p.TK;
     if (wt_ready) {
         g.wt = static_cast<const _Float16*>(wt_ready);            // arranged beforehand (tn_c8_arrange_multi)
     } else {
@@ -689,9 +703,9 @@ static int c8_run(tn_ctx* ctx, C8G& g, const float* W, int K, int C, const void*
         g.wt = reinterpret_cast<const _Float16*>(wt);
     }
     if constexpr (MODE < 2) {
-        if (tk) return FT == 2 ? c8_launch<2, MODE, true>(ctx, g) : c8_launch<1, MODE, true>(ctx, g);
+        if (tk) return FT == 2 ? c8_launch<2, MODE, true>(ctx, g, p) : c8_launch<1, MODE, true>(ctx, g, p);
     }
-    return FT == 2 ? c8_launch<2, MODE>(ctx, g) : c8_launch<1, MODE>(ctx, g);
+    return FT == 2 ? c8_launch<2, MODE>(ctx, g, p) : c8_launch<1, MODE>(ctx, g, p);
 }
 
 // every conv layer's arranged weights of a step in ONE launch (a net made eleven 5 us launches of c8_wt_kernel per step)
@@ -1867,10 +1881,51 @@ static bool c8w_tr_shape_ok(const C8WG& g, int NCT) {
     const int xch = g.nQx / (4 * NCT);
     return g.nQx == 4 * NCT * xch && xch >= 2 && xch <= 5;
 }
+// x chunks per wave and stage: a compile-time count (the waits are counted); shapes land in one of four buckets
+static int c8w_ngx(const C8WG& g) { return cdiv(g.nQx, 8); }
+
+// The instantiation c8w_run launches for a shape: the sixteen-wave form (tr = 1: c8_wgrad_tr_kernel<NCT, NGX, POOL,
+// ROLL>, NFT = 2, TM = 1) or the eight-wave one (c8_wgrad_kernel<NFT, NCT, POOL, NGX, TM, ROLL>).  c8w_plan makes the
+// whole choice (and fills the geometry); c8w_run only maps it onto templates, and tn_c8_conv_plan reports it.
+struct C8WPlan { int tr, NFT, NCT, NGX, TM, ROLL; };
+
+static int c8w_plan(tn_ctx* ctx, C8WG& g, int num_cus, bool pool, C8WPlan& p) {
+    // first layers (one octet plane, small stages): 512- or 256-pixel tiles when every block still gets four of them
+    int tm = 1;
+    if (g.C <= 8) {
+        C8WG g4 = g;
+        if (c8w_geometry(g4, num_cus, pool, 4) && g4.nstage == 3 && g4.tpb >= 4 && c8w_ngx(g4) <= 2) tm = 4;
+        if (tm == 1) {          // (the pooled form carries the raw gradient and the mask bytes beside the dz image: 256 pixels)
+            C8WG g2 = g;
+            if (c8w_geometry(g2, num_cus, pool, 2) && g2.nstage == 3 && g2.tpb >= 4 && c8w_ngx(g2) <= 1) tm = 2;
+        }
+    }
+    TN_REQUIRE(c8w_geometry(g, num_cus, pool, tm) && c8w_lds_bytes(g) <= 160 * 1024, "c8 conv wgrad: unsupported shape");
+    TN_REQUIRE((long long)g.N * g.C8 * g.H * g.Wd < (1ll << 28) && (long long)g.N * g.K8 * g.H * g.Wd < (1ll << 28),
+               "c8 conv wgrad: tensor too large for 32-bit cell offsets");
+    int NFT, NCT;
+    c8w_tiles(g.K, g.C, NFT, NCT);
+    p.NFT = NFT; p.NCT = NCT; p.TM = tm; p.ROLL = g.roll;
+    const int ngx = c8w_ngx(g);
+    p.tr = NFT == 2 && NCT >= 1 && tm == 1 && c8w_tr_on() && c8w_tr_shape_ok(g, NCT);
+    if (p.tr) {
+        p.NGX = g.roll ? 2 * NCT : g.nQx / (4 * NCT) * NCT;       // (c8w_tr_shape_ok: 2..5 chunks per plane)
+    } else if (NCT == 0) {
+        TN_REQUIRE(ngx <= 2, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
+        p.NGX = tm == 4 ? 2 : tm == 2 ? 1 : ngx <= 1 ? 1 : 2;
+    } else if (g.roll) {
+        p.NGX = NCT;                                             // 2 chunks x 4 NCT planes over 8 waves
+    } else {
+        TN_REQUIRE(ngx <= 5, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
+        p.NGX = ngx <= 2 ? 2 : ngx;
+    }
+    return TN_OK;
+}
+
 template <int NCT, bool POOL>
-static int c8w_tr_go(tn_ctx* ctx, C8WG& g) {
-    if (g.roll) return c8w_tr_launch<NCT, 2 * NCT, POOL, true>(ctx, g);
-    switch (g.nQx / (4 * NCT)) {
+static int c8w_tr_go(tn_ctx* ctx, C8WG& g, const C8WPlan& p) {
+    if (p.ROLL) return c8w_tr_launch<NCT, 2 * NCT, POOL, true>(ctx, g);
+    switch (p.NGX / NCT) {
         case 2: return c8w_tr_launch<NCT, 2 * NCT, POOL, false>(ctx, g);
         case 3: return c8w_tr_launch<NCT, 3 * NCT, POOL, false>(ctx, g);
         case 4: return c8w_tr_launch<NCT, 4 * NCT, POOL, false>(ctx, g);
@@ -1879,56 +1934,42 @@ static int c8w_tr_go(tn_ctx* ctx, C8WG& g) {
     return tn_fail(ctx, TN_E_ARG, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
 }
 
-// x chunks per wave and stage: a compile-time count (the waits are counted); shapes land in one of four buckets
-static int c8w_ngx(const C8WG& g) { return cdiv(g.nQx, 8); }
 template <int NFT, int NCT, bool POOL>
-static int c8w_launch_ng(tn_ctx* ctx, C8WG& g, int tm) {
-    const int ngx = c8w_ngx(g);
+static int c8w_launch_ng(tn_ctx* ctx, C8WG& g, const C8WPlan& p) {
     if constexpr (NCT == 0) {
-        TN_REQUIRE(ngx <= 2, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
-        if (tm == 4) return c8w_launch<NFT, 0, POOL, 2, 4>(ctx, g);
-        if (tm == 2) return c8w_launch<NFT, 0, POOL, 1, 2>(ctx, g);
-        return ngx <= 1 ? c8w_launch<NFT, 0, POOL, 1>(ctx, g) : c8w_launch<NFT, 0, POOL, 2>(ctx, g);
+        if (p.TM == 4) return c8w_launch<NFT, 0, POOL, 2, 4>(ctx, g);
+        if (p.TM == 2) return c8w_launch<NFT, 0, POOL, 1, 2>(ctx, g);
+        return p.NGX == 1 ? c8w_launch<NFT, 0, POOL, 1>(ctx, g) : c8w_launch<NFT, 0, POOL, 2>(ctx, g);
     } else {
-        if (g.roll) return c8w_launch<NFT, NCT, POOL, NCT, 1, true>(ctx, g);      // 2 chunks x 4 NCT planes over 8 waves
-        if (ngx <= 2) return c8w_launch<NFT, NCT, POOL, 2>(ctx, g);
-        if (ngx <= 3) return c8w_launch<NFT, NCT, POOL, 3>(ctx, g);
-        if (ngx <= 4) return c8w_launch<NFT, NCT, POOL, 4>(ctx, g);
-        TN_REQUIRE(ngx <= 5, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
-        return c8w_launch<NFT, NCT, POOL, 5>(ctx, g);
+        if (p.ROLL) return c8w_launch<NFT, NCT, POOL, NCT, 1, true>(ctx, g);
+        switch (p.NGX) {
+            case 2: return c8w_launch<NFT, NCT, POOL, 2>(ctx, g);
+            case 3: return c8w_launch<NFT, NCT, POOL, 3>(ctx, g);
+            case 4: return c8w_launch<NFT, NCT, POOL, 4>(ctx, g);
+            case 5: return c8w_launch<NFT, NCT, POOL, 5>(ctx, g);
+        }
+        return tn_fail(ctx, TN_E_ARG, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
     }
 }
 
 static int c8w_run(tn_ctx* ctx, C8WG& g, float* dW, float* db, bool pool) {
-    // first layers (one octet plane, small stages): 512- or 256-pixel tiles when every block still gets four of them
-    int tm = 1;
-    if (g.C <= 8) {
-        C8WG g4 = g;
-        if (c8w_geometry(g4, ctx->num_cus, pool, 4) && g4.nstage == 3 && g4.tpb >= 4 && c8w_ngx(g4) <= 2) tm = 4;
-        if (tm == 1) {          // (the pooled form carries the raw gradient and the mask bytes beside the dz image: 256 pixels)
-            C8WG g2 = g;
-            if (c8w_geometry(g2, ctx->num_cus, pool, 2) && g2.nstage == 3 && g2.tpb >= 4 && c8w_ngx(g2) <= 1) tm = 2;
-        }
-    }
-    TN_REQUIRE(c8w_geometry(g, ctx->num_cus, pool, tm) && c8w_lds_bytes(g) <= 160 * 1024, "c8 conv wgrad: unsupported shape");
-    TN_REQUIRE((long long)g.N * g.C8 * g.H * g.Wd < (1ll << 28) && (long long)g.N * g.K8 * g.H * g.Wd < (1ll << 28),
-               "c8 conv wgrad: tensor too large for 32-bit cell offsets");
-    int NFT, NCT;
-    c8w_tiles(g.K, g.C, NFT, NCT);
+    C8WPlan p;
+    int rc = c8w_plan(ctx, g, ctx->num_cus, pool, p);
+    if (rc) return rc;
     const size_t n = (size_t)g.K * g.C * 9;
-    int rc = tn_scratch_get(ctx, ((size_t)g.S * n + (size_t)g.S * g.K) * sizeof(float), &g.ws);
+    rc = tn_scratch_get(ctx, ((size_t)g.S * n + (size_t)g.S * g.K) * sizeof(float), &g.ws);
     if (rc) return rc;
     g.dbws = g.ws + (size_t)g.S * n;
     g.oscale = 1.f / ctx->grad_scale;
-#define C8W_GO(A, B) rc = pool ? c8w_launch_ng<A, B, true>(ctx, g, tm) : c8w_launch_ng<A, B, false>(ctx, g, tm)
-    if (NFT == 2 && NCT >= 1 && tm == 1 && c8w_tr_on() && c8w_tr_shape_ok(g, NCT)) {
-        if (NCT == 2) rc = pool ? c8w_tr_go<2, true>(ctx, g) : c8w_tr_go<2, false>(ctx, g);
-        else rc = pool ? c8w_tr_go<1, true>(ctx, g) : c8w_tr_go<1, false>(ctx, g);
-    } else if (NCT == 0 && NFT == 2) C8W_GO(2, 0);
-    else if (NCT == 0) C8W_GO(1, 0);
-    else if (NFT == 2 && NCT == 2) C8W_GO(2, 2);
-    else if (NFT == 2) C8W_GO(2, 1);
-    else if (NCT == 2) C8W_GO(1, 2);
+#define C8W_GO(A, B) rc = pool ? c8w_launch_ng<A, B, true>(ctx, g, p) : c8w_launch_ng<A, B, false>(ctx, g, p)
+    if (p.tr) {
+        if (p.NCT == 2) rc = pool ? c8w_tr_go<2, true>(ctx, g, p) : c8w_tr_go<2, false>(ctx, g, p);
+        else rc = pool ? c8w_tr_go<1, true>(ctx, g, p) : c8w_tr_go<1, false>(ctx, g, p);
+    } else if (p.NCT == 0 && p.NFT == 2) C8W_GO(2, 0);
+    else if (p.NCT == 0) C8W_GO(1, 0);
+    else if (p.NFT == 2 && p.NCT == 2) C8W_GO(2, 2);
+    else if (p.NFT == 2) C8W_GO(2, 1);
+    else if (p.NCT == 2) C8W_GO(1, 2);
     else C8W_GO(1, 1);
 #undef C8W_GO
     if (rc) return rc;
@@ -2075,6 +2116,37 @@ int tn_c8_conv_wgrad_supported(int N, int C, int H, int Wd, int K) {
     if (c8w_lds_bytes(g) > 160 * 1024) return 0;
     if (!c8w_geometry(g, cus, false) || c8w_ngx(g) > 5) return 0;
     return c8w_lds_bytes(g) <= 160 * 1024;
+}
+
+// the kernel a tn_c8_conv_fwd (op 0) / _dgrad (op 1) / _wgrad (op 2) call of this shape launches, from the launchers'
+// own plan functions (layout: include/theanet_hip.h); no context: the current device's CU count as above
+int tn_c8_conv_plan(int op, int N, int C, int H, int Wd, int K, int pool, int act, float prm, int* out, int nout) {
+    int v[13], n = 0;
+    if (K & 7) return TN_E_ARG;
+    if (op == 2) {
+        C8WG g{};
+        g.N = N; g.C = C; g.C8 = (C + 7) / 8; g.H = H; g.Wd = Wd; g.K = K; g.K8 = K / 8;
+        C8WPlan p;
+        const int rc = c8w_plan(nullptr, g, c8_current_cus(), pool != 0, p);
+        if (rc) return rc;
+        const int w[13] = {p.tr, p.NFT, p.NCT, p.NGX, p.TM, p.ROLL, g.nstage, g.NI, g.S, g.tpb, g.NTILES, g.KG, g.CG};
+        for (n = 0; n < 13; ++n) v[n] = w[n];
+    } else if (op == 0 || op == 1) {
+        C8G g{};
+        g.N = N; g.H = H; g.W = Wd; g.act = act; g.prm = prm;
+        // (input gradient: the roles of filters and channels swap, as in tn_c8_conv_dgrad)
+        g.C8 = op ? K / 8 : (C + 7) / 8; g.K8 = op ? (C + 7) / 8 : K / 8;
+        const int mode = 2 * op + (pool != 0);
+        C8Plan p;
+        const int rc = op ? c8_plan(nullptr, g, mode, C, K, p) : c8_plan(nullptr, g, mode, K, C, p);
+        if (rc) return rc;
+        const int w[9] = {p.FT, mode, p.NS, p.LK, p.TK, g.NI, g.RT, g.KT, g.MT};
+        for (n = 0; n < 9; ++n) v[n] = w[n];
+    } else {
+        return TN_E_ARG;
+    }
+    for (int i = 0; i < n && i < nout; ++i) out[i] = v[i];
+    return n;
 }
 
 // (N, C, H, W) fp32 rows row0.. of x -> c8 fp16 (values times scale); channels beyond C are zero

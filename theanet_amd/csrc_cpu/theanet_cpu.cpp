@@ -180,6 +180,7 @@ int tn_set_fc_matmul(tn_ctx* ctx, int mode) {
 // tn_set_matmul_dtype refuses the mode, so the host never gets here
 int tn_c8_conv_supported(int, int, int, int, int, int, int, int) { return 0; }
 int tn_c8_conv_wgrad_supported(int, int, int, int, int) { return 0; }
+int tn_c8_conv_plan(int, int, int, int, int, int, int, int, float, int*, int) { return TN_E_ARG; }
 size_t tn_c8_wt_elems(int, int, int) { return 0; }
 int tn_c8_arrange_multi(tn_ctx* ctx, const tn_c8_wt_seg*, int) { NOT_HERE("tn_c8_arrange_multi"); }
 int tn_c8_conv_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, uint8_t*, int, int, int, int, int, int,
