@@ -10,6 +10,11 @@ is not imported: the hot path is libtheanet_hip.so + RCCL).  Rank 0 prints ONE J
 N > 1 defaults to STRONG scaling as BASELINE.json configs[2] states it ("bs4096 sharded 8 ways"):
 the global batch stays 4096 and every rank trains on 4096/N rows, one flat gradient all-reduce per
 step.  --scaling weak keeps 4096 rows per GPU instead (global 4096*N).
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the --dump-outputs
+arrays and the line.  --full adds every other leg after the timed steps: the sustained, sync-API and
+train-loop figures, the per-kernel roofline, the other BASELINE configurations, bf16x3, the 512-row
+shard, the CPU baseline and (N > 1) the weak-scaling leg; the --no-* options leave legs out of it.
 """
 import argparse
 import ast
@@ -115,7 +120,7 @@ def _pmc_table(config):
 
 DEFAULTS = {"mnist.prms": (4096, 28, 1), "cifar_like.prms": (2048, 32, 3),
             "wide6.prms": (128, 64, 3), "3flat.prms": (4096, 28, 1)}
-# BASELINE.json configs[3] and configs[4] (one GPU's share of it), reported by the default N=1 run beside the headline
+# BASELINE.json configs[3] and configs[4] (one GPU's share of it), reported by a --full N=1 run beside the headline
 OTHER_CONFIGS = (("cifar_like.prms", "f32"), ("cifar_like.prms", "f16"), ("wide6.prms", "f32"), ("wide6.prms", "f16"))
 
 
@@ -561,9 +566,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel roofline leg")
     ap.add_argument("--no-weak-leg", action="store_true",
-                    help="N > 1, strong scaling: skip the weak-scaling leg (value_weak) the same launch appends")
+                    help="N > 1, strong scaling: skip the weak-scaling leg (value_weak) a --full launch appends")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the cifar_like / wide6 legs the default N=1 mnist run appends (other_configs)")
+                    help="skip the cifar_like / wide6 legs a --full N=1 mnist run appends (other_configs)")
     ap.add_argument("--dry-multi", type=int, default=0, metavar="N",
                     help="print the plan of an N-rank run (shards, flat gradient layout, schedule) and exit")
     ap.add_argument("--sequential", action="store_true",
@@ -574,6 +579,10 @@ def main():
                     help="write what the last timed step computed (cost, logprob, the weights after its update) as "
                          "DIR/<name>.npy; the set-up then takes a fixed %d steps, so that two builds start the timed "
                          "steps from the same weights" % DUMP_SETUP_STEPS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (sustained / sync API / train loop, per-kernel "
+                         "roofline, other configurations, bf16x3, 512-row shard, CPU baseline, weak scaling); the "
+                         "--no-* options leave legs out")
     ap.add_argument("--dp-selfcheck-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.steps < 1:
@@ -661,54 +670,55 @@ def main():
                         "data": "synthetic", "config": {"workload": "params/%s, global batch %d = %d images/GPU/step x %d"
                                                         % (args.prms, tr["BATCH_SZ"], per_gpu, world.size),
                                                         "dp_schedule": getattr(net, "dp_schedule", None)}}
-    progress["phase"] = "the legs behind the timed region (sustained / sync API / train loop)"
+    sustained = value_sync_api = value_train_loop = None
+    if args.full:
+        progress["phase"] = "the legs behind the timed region (sustained / sync API / train loop)"
 
-    # The driver's --steps can make the timed region a few milliseconds: a second, longer loop of the
-    # same enqueue-only steps (>= 0.5 s) is reported beside it as `sustained`.
-    sustained = None
-    if dt < 0.05:
-        n_sus = int(min(50000, max(args.steps, 0.6 / max(dt / args.steps, 1e-6))))
+        # A small --steps can make the timed region a few milliseconds: a second, longer loop of the
+        # same enqueue-only steps (>= 0.5 s) is reported beside it as `sustained`.
+        if dt < 0.05:
+            n_sus = int(min(50000, max(args.steps, 0.6 / max(dt / args.steps, 1e-6))))
+            barrier()
+            t1 = time.perf_counter()
+            for i in range(n_sus):
+                fn.enqueue(i % n_batches)
+            barrier()
+            dt_sus = time.perf_counter() - t1
+            if group is not None:
+                dt_sus = group.rdzv.gather_max(dt_sus)
+            sustained = {"steps": n_sus, "seconds": dt_sus, "ms_per_step": 1e3 * dt_sus / n_sus,
+                         "value": tr["BATCH_SZ"] * n_sus / dt_sus}
+        # The drop-in call fn(i) of the reference's loop (train.py:211: cost, features, logprob come back
+        # every step, i.e. a device sync + a D2H of B x n_out floats per step) -- its throughput, untimed above.
+        n_sync = int(min(2000, max(20, 0.3 / max(dt / args.steps, 1e-6))))
         barrier()
         t1 = time.perf_counter()
-        for i in range(n_sus):
-            fn.enqueue(i % n_batches)
+        for i in range(n_sync):
+            fn(i % n_batches)
         barrier()
-        dt_sus = time.perf_counter() - t1
+        dt_sync = time.perf_counter() - t1
         if group is not None:
-            dt_sus = group.rdzv.gather_max(dt_sus)
-        sustained = {"steps": n_sus, "seconds": dt_sus, "ms_per_step": 1e3 * dt_sus / n_sus,
-                     "value": tr["BATCH_SZ"] * n_sus / dt_sus}
-    # The drop-in call fn(i) of the reference's loop (train.py:211: cost, features, logprob come back
-    # every step, i.e. a device sync + a D2H of B x n_out floats per step) -- its throughput, untimed above.
-    n_sync = int(min(2000, max(20, 0.3 / max(dt / args.steps, 1e-6))))
-    barrier()
-    t1 = time.perf_counter()
-    for i in range(n_sync):
-        fn(i % n_batches)
-    barrier()
-    dt_sync = time.perf_counter() - t1
-    if group is not None:
-        dt_sync = group.rdzv.gather_max(dt_sync)
-    value_sync_api = tr["BATCH_SZ"] * n_sync / dt_sync
-    # What THIS build's train.py loop does instead: step_cost(i) -- the step is enqueued and the costs that have arrived
-    # (each step's 4 bytes travel to page-locked memory by themselves) are summed a few calls late; nothing waits.
-    n_loop = int(min(50000, max(args.steps, 0.3 / max(dt / args.steps, 1e-6))))
-    barrier()
-    t1 = time.perf_counter()
-    tot, seen = 0.0, 0
-    for i in range(n_loop):
-        for _, c in fn.step_cost(i % n_batches):
+            dt_sync = group.rdzv.gather_max(dt_sync)
+        value_sync_api = tr["BATCH_SZ"] * n_sync / dt_sync
+        # What THIS build's train.py loop does instead: step_cost(i) -- the step is enqueued and the costs that have arrived
+        # (each step's 4 bytes travel to page-locked memory by themselves) are summed a few calls late; nothing waits.
+        n_loop = int(min(50000, max(args.steps, 0.3 / max(dt / args.steps, 1e-6))))
+        barrier()
+        t1 = time.perf_counter()
+        tot, seen = 0.0, 0
+        for i in range(n_loop):
+            for _, c in fn.step_cost(i % n_batches):
+                tot += float(c)
+                seen += 1
+        for _, c in fn.drain_costs():
             tot += float(c)
             seen += 1
-    for _, c in fn.drain_costs():
-        tot += float(c)
-        seen += 1
-    barrier()
-    dt_loop = time.perf_counter() - t1
-    if group is not None:
-        dt_loop = group.rdzv.gather_max(dt_loop)
-    assert seen == n_loop and np.isfinite(tot), "the cost ring lost a step"
-    value_train_loop = tr["BATCH_SZ"] * n_loop / dt_loop
+        barrier()
+        dt_loop = time.perf_counter() - t1
+        if group is not None:
+            dt_loop = group.rdzv.gather_max(dt_loop)
+        assert seen == n_loop and np.isfinite(tot), "the cost ring lost a step"
+        value_train_loop = tr["BATCH_SZ"] * n_loop / dt_loop
     if dog_main is not None:
         dog_main.cancel()
 
@@ -716,7 +726,7 @@ def main():
     # heavy kernels of the SAME workload; the dominant one (largest share of the step) is
     # reported as `roofline`, the rest as `roofline_others`.
     roof, others = None, []
-    if args.no_roofline or os.environ.get("THEANET_BACKEND", "hip") == "cpu":
+    if not args.full or args.no_roofline or os.environ.get("THEANET_BACKEND", "hip") == "cpu":
         pass                                    # the roofline leg times HIP kernels
     elif args.prms == "mnist.prms":
         conv2, fc1 = net.tr_layers[3], net.tr_layers[5]
@@ -795,28 +805,30 @@ def main():
         "scaling": scaling, "vs_baseline": None,
         "dtype": DTYPE_LABEL[args.dtype],
         "data": "synthetic",
-        "value_sync_api": value_sync_api,
-        "sync_api": {"steps": n_sync, "ms_per_step": 1e3 * dt_sync / n_sync,
-                     "what": "fn(i) returning [cost, features, logprob] every step as the reference's train.py:211 does"},
-        "value_train_loop": value_train_loop,
-        "train_loop": {"steps": n_loop, "ms_per_step": 1e3 * dt_loop / n_loop,
-                       "what": "this build's train.py loop: fn.step_cost(i) -- every step's cost summed on the host a few "
-                               "calls late (page-locked ring), the NaN guard on it; nothing waits for the GPU"},
-        "sustained": sustained,
-        "config": {"workload": "params/%s %dx%dx%d synthetic, global batch %d = %d images/GPU/step x %d, %s"
-                               % (args.prms, img, img, C, tr["BATCH_SZ"], per_gpu, world.size, stage),
-                   "global_batch": tr["BATCH_SZ"], "parallelism": "dp%d" % world.size,
-                   "schedule": "two steps in flight (exact: the update applies the old velocity)"
-                   if type(fn).__name__ == "_PipeTrainFn" and fn._twin is not None else "one step at a time",
-                   "dp_schedule": getattr(net, "dp_schedule", None) if world.size > 1 else None,
-                   "dp_schedule_us_per_step": {k: 1e3 * v for k, v in getattr(net, "dp_tuned_ms", {}).items()}
-                   if world.size > 1 and isinstance(getattr(net, "dp_tuned_ms", None), dict) else None,
-                   "step_gflop_algorithmic": step_flops / 1e9,
-                   "step_tflops_algorithmic": step_flops / (dt / args.steps) / 1e12},
-        "roofline": roof,
-        "roofline_others": others,
-        "final_cost": float(cost),
     }
+    if args.full:
+        line.update({
+            "value_sync_api": value_sync_api,
+            "sync_api": {"steps": n_sync, "ms_per_step": 1e3 * dt_sync / n_sync,
+                         "what": "fn(i) returning [cost, features, logprob] every step as the reference's train.py:211 does"},
+            "value_train_loop": value_train_loop,
+            "train_loop": {"steps": n_loop, "ms_per_step": 1e3 * dt_loop / n_loop,
+                           "what": "this build's train.py loop: fn.step_cost(i) -- every step's cost summed on the host a "
+                                   "few calls late (page-locked ring), the NaN guard on it; nothing waits for the GPU"},
+            "sustained": sustained})
+    line["config"] = {"workload": "params/%s %dx%dx%d synthetic, global batch %d = %d images/GPU/step x %d, %s"
+                                  % (args.prms, img, img, C, tr["BATCH_SZ"], per_gpu, world.size, stage),
+                      "global_batch": tr["BATCH_SZ"], "parallelism": "dp%d" % world.size,
+                      "schedule": "two steps in flight (exact: the update applies the old velocity)"
+                      if type(fn).__name__ == "_PipeTrainFn" and fn._twin is not None else "one step at a time",
+                      "dp_schedule": getattr(net, "dp_schedule", None) if world.size > 1 else None,
+                      "dp_schedule_us_per_step": {k: 1e3 * v for k, v in getattr(net, "dp_tuned_ms", {}).items()}
+                      if world.size > 1 and isinstance(getattr(net, "dp_tuned_ms", None), dict) else None,
+                      "step_gflop_algorithmic": step_flops / 1e9,
+                      "step_tflops_algorithmic": step_flops / (dt / args.steps) / 1e12}
+    if args.full:
+        line.update({"roofline": roof, "roofline_others": others})
+    line["final_cost"] = float(cost)
     if selfcheck is not None:
         line["dp_selfcheck"] = selfcheck
     if dumped is not None:
@@ -825,7 +837,7 @@ def main():
     # launch then times the WEAK form (the stated batch per GPU, N times the global batch) and reports it beside it:
     # for mnist.prms the strong figure is bounded by the kernels' fixed costs at 4096/N rows,
     # the weak one is what the interconnect and the schedule allow.  Every rank takes part (the steps are collectives).
-    if world.size > 1 and scaling == "strong" and not args.no_weak_leg:
+    if args.full and world.size > 1 and scaling == "strong" and not args.no_weak_leg:
         import gc
         import threading
         del fn, net
@@ -856,8 +868,8 @@ def main():
         return
     # BASELINE.json's other single-GPU configurations (north_star: images/sec "on synthetic 28x28x1 and 32x32x3
     # batches ... as fraction of the conv roofline"; the >= 50 % fp32-MFMA target on 3x3 convs; configs[4]'s fp16
-    # path), timed by THIS run after the headline: the default N = 1 mnist run only.
-    if world.size == 1 and args.prms == "mnist.prms" and not args.batch and not args.no_other_configs \
+    # path), timed by THIS run after the headline: the --full N = 1 mnist run only.
+    if args.full and world.size == 1 and args.prms == "mnist.prms" and not args.batch and not args.no_other_configs \
             and not args.no_roofline and os.environ.get("THEANET_BACKEND", "hip") != "cpu":
         import gc
         del fn, net
@@ -888,7 +900,7 @@ def main():
                 "t_4096_ms": round(t_full, 5), "t_512_ms": line["shard_leg"]["ms_per_step"]}
         except Exception as e:
             line["shard_leg"] = {"cfg": "mnist.prms", "rows": 512, "error": "%s: %s" % (type(e).__name__, str(e)[-300:])}
-    if world.size == 1 and not args.no_cpu_baseline:
+    if args.full and world.size == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(prms, img, C, tr["BATCH_SZ"])
     # The compact figures once more, LAST in the line: a reader that keeps only the tail of the output (the round
     # driver keeps 2000 characters) still sees every configuration's step time.

@@ -257,10 +257,10 @@ def test_bench_dry_multi_plans_an_8_rank_run_without_a_communicator(prms, extra,
 
 
 def test_bench_two_ranks_reports_strong_and_weak_scaling():
-    """bench.py --gpus 2 as the driver launches it (one process per rank, RANK / WORLD_SIZE / MASTER_* from the
-    environment), on the CPU backend: ONE JSON line from rank 0 whose `value` is the strong-scaling figure (the stated
-    batch sharded over the ranks, BASELINE configs[2]) and whose `value_weak` is the same launch's weak-scaling leg (the
-    stated batch per rank)."""
+    """bench.py --gpus 2 --full, one process per rank (RANK / WORLD_SIZE / MASTER_* from the environment), on the CPU
+    backend: ONE JSON line from rank 0 whose `value` is the strong-scaling figure (the stated batch sharded over the
+    ranks, BASELINE configs[2]) and whose `value_weak` is the same launch's weak-scaling leg (the stated batch per
+    rank)."""
     import json
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -271,7 +271,8 @@ def test_bench_two_ranks_reports_strong_and_weak_scaling():
         env = _env(RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    OMP_NUM_THREADS="2")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                                       "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--no-roofline"],
+                                       "--warmup", "1", "--batch", "64", "--full", "--no-cpu-baseline",
+                                       "--no-roofline"],
                                       cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -320,6 +321,30 @@ def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
         dumps.append(arrays)
     for n, a in dumps[0].items():
         np.testing.assert_array_equal(dumps[1][n], a, err_msg=n)
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain bench.py run (no --full) on the CPU backend: the headline and nothing after it -- no sustained, sync-API
+    or train-loop leg, no roofline and no CPU baseline, although no --no-* option is given.  --full adds those legs
+    to the same line (--no-cpu-baseline keeps the test short), and the headline fields stay."""
+    import json
+    head = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"}
+    full_only = {"sustained", "sync_api", "value_sync_api", "train_loop", "value_train_loop", "roofline", "cpu_baseline"}
+    lines = []
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "64"] + extra, cwd=ROOT, env=_env(OMP_NUM_THREADS="2"), capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip())
+        assert head <= set(line) and line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(64 * 1e3 / line["ms_per_step"])
+        lines.append(line)
+    plain, full = lines
+    assert not full_only & set(plain), sorted(full_only & set(plain))
+    assert full_only - {"cpu_baseline"} <= set(full) and "cpu_baseline" not in full
+    assert full["sync_api"]["steps"] >= 20 and full["train_loop"]["steps"] >= 3
+    assert plain["metric"] == full["metric"] and plain["dtype"] == full["dtype"]
 
 
 def _bench_ranks(world, extra_env, timeout=300):

@@ -42,8 +42,8 @@ def run(label):
     for kv in envs[label].split():
         k, v = kv.split("=", 1)
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-other-configs", "--no-roofline",
-           "--steps", "400", "--warmup", "50"] + extra.split()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-other-configs",
+           "--no-roofline", "--steps", "400", "--warmup", "50"] + extra.split()
     out = subprocess.run(cmd, env=env, capture_output=True, text=True)
     try:
         j = json.loads(out.stdout.strip().split("\n")[-1])

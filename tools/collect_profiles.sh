@@ -8,8 +8,9 @@
 TAG=${1:-r06}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-other-configs"
+B="python $root/bench.py --full --no-cpu-baseline --no-other-configs"
 run() {   # name, rocprof args..., -- bench args
     local name=$1; shift
     timeout 600 rocprofv3 "$@" > $OUT/$name.log 2>&1 || echo "FAILED $name (see $name.log)"
