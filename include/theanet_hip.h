@@ -144,13 +144,17 @@ int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx,
                     int N, int C, int H, int Wd, int K, int f, int stride, int pad_lo,
                     int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
 
-/* ---- DTYPE 'float16' (BASELINE configs[4]; the reference is float32-only, weights.py:8 `floatX`: an opt-in
- * training param of this build, default off) ----
+/* ---- DTYPE 'float16' / 'bfloat16' (BASELINE configs[4]; the reference is float32-only, weights.py:8 `floatX`: opt-in
+ * training params of this build, default off) ----
  * dtype 0: every tensor fp32 (reference arithmetic).  dtype 1: the conv stack of the net lives in HBM as halfs and is
  * served by the tn_c8_* / tn_fc8_* entry points below; the fp32-tensor conv entry points (tn_conv2d_*, tn_convpool_*)
  * REFUSE to run in this mode (TN_E_ARG: never a silent fp32 run inside a float16 net).  grad_scale (a power of two,
  * e.g. 4096): gradient tensors of the stack hold fp16(grad_scale * g) so that small gradients do not fall into
- * fp16's subnormal range; the fp32 epilogues of the weight gradients remove the factor.                          */
+ * fp16's subnormal range; the fp32 epilogues of the weight gradients remove the factor.
+ * dtype 2: the same with bf16 cells -- every tn_c8_* / tn_fc8_* entry point reads and writes bf16 (same signatures,
+ * layout, kernels and schedule; bf16 MFMA, round-to-nearest-even when a tensor is stored), the fp32-tensor conv entry
+ * points refuse as in dtype 1.  bf16 has fp32's exponent range: grad_scale is still honoured (a power of two scales
+ * exactly), the host passes 1.  In dtypes 0 and 1 the c8 entry points use halfs; the CPU backend refuses dtypes != 0. */
 int tn_set_matmul_dtype(tn_ctx* ctx, int dtype, float grad_scale);
 int tn_get_matmul_dtype(tn_ctx* ctx);
 /* MATMUL 'bf16x3' (opt-in, this build's extension; the reference is float32, weights.py:8): mode 1 runs the products of
@@ -160,6 +164,8 @@ int tn_get_matmul_dtype(tn_ctx* ctx);
 int tn_set_fc_matmul(tn_ctx* ctx, int mode);
 
 /* ---- DTYPE 'float16' on fp16-RESIDENT tensors (theanet_amd/csrc/conv_c8.hip, fc_c8.hip) --------------------
+ * (DTYPE 'bfloat16', tn_set_matmul_dtype mode 2: everything below with bf16 in place of half; the shape predicates and
+ * tn_c8_conv_plan do not depend on the element type.)
  * BASELINE.json configs[4]: "fp16 inputs / fp32 accum MFMA".  The reference is float32-only (weights.py:8); these
  * entry points replace the same Theano call sites as tn_conv2d_* / tn_fc_* (convpool.py:54-72,106-107; hidden.py:30;
  * layer.py:83) for nets built with training param DTYPE = 'float16'.  Activations and the gradients flowing down

@@ -48,8 +48,9 @@ struct tn_ctx {
     // heavy launches since the second stream was last selected: small = two steps in flight share the GPU
     // (tn_fc_bwd then leaves the other stream's kernels a share of the register file), large = this stream has it alone
     int heavy_since_side = 1 << 20;
-    // matmul operand precision of the 3x3 conv products (tn_set_matmul_dtype): 0 fp32, 1 fp16 operands /
-    // fp32 accumulate; grad_scale: power of two applied to dz before it is rounded to fp16
+    // matmul operand precision of the 3x3 conv products (tn_set_matmul_dtype): 0 fp32, 1 fp16 / 2 bf16 operands and
+    // fp32 accumulate (nonzero: the conv stack is 16-bit resident -- several places test it as a boolean); grad_scale:
+    // power of two applied to dz before it is rounded to the 16-bit type
     int mm_f16 = 0;
     int fc_b3 = 0;                         // tn_set_fc_matmul: 1 = FC products as bf16 triplets (gemm_b3.hip)
     float grad_scale = 1.f;

@@ -20,7 +20,9 @@
 //     scaled ONCE where the first fp16 gradient is produced, unscaled in the fp32 epilogues of the weight gradients.
 // The weight gradient (reduction = pixels) wants the other orientation: gfx950's transposing LDS read
 // (ds_read_b64_tr_b16) supplies it between LDS and the registers, so its LDS images are plain copies of the c8 tensors.
-#include "conv_tile_common.h"
+// DTYPE 'bfloat16' runs the same kernels on bf16 cells: the element type is a template parameter (c8_elem.h), its
+// instantiations are compiled by conv_c8_bf16.hip.
+#include "c8_elem.h"
 
 #include <type_traits>
 
@@ -77,11 +79,12 @@ __device__ __forceinline__ float c8_wt_value(const float* __restrict__ W, int K,
                      : W[((size_t)filt * C + ch) * 9 + (8 - tap)];   // true convolution: flipped taps
     return 0.f;
 }
-__global__ __launch_bounds__(256) void c8_wt_kernel(const float* __restrict__ W, _Float16* __restrict__ wt, int K, int C,
+template <typename E>
+__global__ __launch_bounds__(256) void c8_wt_kernel(const float* __restrict__ W, typename E::T* __restrict__ wt, int K, int C,
                                                    int KBF, int nchunk, int total, int dgrad, int tk) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
-    wt[idx] = (_Float16)c8_wt_value(W, K, C, KBF, nchunk, idx, dgrad, tk);
+    wt[idx] = (typename E::T)(c8_wt_value(W, K, C, KBF, nchunk, idx, dgrad, tk));
 }
 
 __device__ __forceinline__ uint4 c8_and4(uint4 v, bool ok) {
@@ -112,7 +115,7 @@ __device__ __forceinline__ uint4 c8_pool_cell(const uint4 g8, const uint2 m8, in
 // channels advance in lockstep (every DPP / SGPR hazard distance is met by the partner channel's instructions): 16.75.
 // o01 / o23: the four activated maxima as halfs; mk: the four mask bytes.
 #define C8_DPPQ "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-#define C8_EPI_PAIR(O, ZA0, ZB0, ZA1, ZB1)                                                          \
+#define C8_EPI_PAIR(CVT, O, ZA0, ZB0, ZA1, ZB1)                                                     \
     "v_max_f32_e32 %3, " ZA0 ", " ZA1 "\n\t"                                                        \
     "v_max_f32_e32 %4, " ZB0 ", " ZB1 "\n\t"                                                        \
     "s_nop 0\n\t"                                                                                   \
@@ -144,20 +147,26 @@ __device__ __forceinline__ uint4 c8_pool_cell(const uint4 g8, const uint2 m8, in
     "v_cndmask_b32_e64 %4, 0, 32, %14\n\t"                                                          \
     "v_or3_b32 %5, %5, %7, %3\n\t"                                                                  \
     "v_or3_b32 %6, %6, %8, %4\n\t"                                                                  \
-    "v_cvt_pk_f16_f32 " O ", %9, %10\n\t"
+    CVT " " O ", %9, %10\n\t"
+template <typename E>
 __device__ __forceinline__ void c8_pool_epi4(unsigned& o01, unsigned& o23, unsigned& mk, const float (&z0)[4], const float (&z1)[4],
                                              float prm, unsigned kA, unsigned kB) {
     unsigned t3, t4, t5, t6, t7, t8, t9, t10;
     unsigned long long s11, s12, s13, s14;
-    asm volatile(C8_EPI_PAIR("%0", "%15", "%16", "%19", "%20")
-                 "v_lshl_or_b32 %2, %6, 8, %5\n\t"
-                 C8_EPI_PAIR("%1", "%17", "%18", "%21", "%22")
-                 "v_lshl_or_b32 %5, %6, 8, %5\n\t"
-                 "v_lshl_or_b32 %2, %5, 16, %2"
-                 : "=&v"(o01), "=&v"(o23), "=&v"(mk), "=&v"(t3), "=&v"(t4), "=&v"(t5), "=&v"(t6), "=&v"(t7), "=&v"(t8),
-                   "=&v"(t9), "=&v"(t10), "=&s"(s11), "=&s"(s12), "=&s"(s13), "=&s"(s14)
-                 : "v"(z0[0]), "v"(z0[1]), "v"(z0[2]), "v"(z0[3]), "v"(z1[0]), "v"(z1[1]), "v"(z1[2]), "v"(z1[3]), "s"(prm),
-                   "v"(kA), "v"(kB));
+#define C8_EPI_ASM(CVT)                                                                                     \
+    asm volatile(C8_EPI_PAIR(CVT, "%0", "%15", "%16", "%19", "%20")                                         \
+                 "v_lshl_or_b32 %2, %6, 8, %5\n\t"                                                         \
+                 C8_EPI_PAIR(CVT, "%1", "%17", "%18", "%21", "%22")                                         \
+                 "v_lshl_or_b32 %5, %6, 8, %5\n\t"                                                         \
+                 "v_lshl_or_b32 %2, %5, 16, %2"                                                             \
+                 : "=&v"(o01), "=&v"(o23), "=&v"(mk), "=&v"(t3), "=&v"(t4), "=&v"(t5), "=&v"(t6), "=&v"(t7), "=&v"(t8), \
+                   "=&v"(t9), "=&v"(t10), "=&s"(s11), "=&s"(s12), "=&s"(s13), "=&s"(s14)                    \
+                 : "v"(z0[0]), "v"(z0[1]), "v"(z0[2]), "v"(z0[3]), "v"(z1[0]), "v"(z1[1]), "v"(z1[2]), "v"(z1[3]), "s"(prm), \
+                   "v"(kA), "v"(kB))
+    // the conversion of the two activated maxima to the element type (nearest-even either way)
+    if constexpr (E::BF) C8_EPI_ASM("v_cvt_pk_bf16_f32");
+    else C8_EPI_ASM("v_cvt_pk_f16_f32");
+#undef C8_EPI_ASM
 }
 
 // MODE 0: forward (bias + act); 1: forward + 2x2 max-pool + mask; 2: input gradient (x act' of the layer below);
@@ -168,9 +177,10 @@ __device__ __forceinline__ void c8_pool_epi4(unsigned& o01, unsigned& o23, unsig
 // ahead whatever tile they belong to, so a tile's epilogue stores and the next tile's first loads overlap the matrix
 // work instead of bracketing it (cycle stamps of the one-tile-per-block form, conv2 of wide6: prologue 5.4 k + main
 // loop 11.5 k + epilogue 5.5 k cycles per block, all blocks of a round in the same phase).
-template <int FT, int MODE, int NS, bool LK, bool TK = false>
+template <typename E, int FT, int MODE, int NS, bool LK, bool TK = false>
 __global__ __launch_bounds__(256, 2) void c8_conv_kernel(C8G g) {
     extern __shared__ __attribute__((aligned(16))) float ct_smem[];
+    typedef typename E::v8 half8;                     // 8 elements of the c8 type (halfs or bf16)
     constexpr bool DGRAD = MODE >= 2;
     constexpr bool POOLED = MODE == 3;
     constexpr int KBF = 32 * FT;
@@ -402,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void c8_conv_kernel(C8G g) {
                             const float z1[4] = {acc[f][1][h * 8 + 4 * q], acc[f][1][h * 8 + 4 * q + 1], acc[f][1][h * 8 + 4 * q + 2],
                                                  acc[f][1][h * 8 + 4 * q + 3]};
                             unsigned a, b, mk;
-                            c8_pool_epi4(a, b, mk, z0, z1, prm, 1u << dj, 4u << dj);
+                            c8_pool_epi4<E>(a, b, mk, z0, z1, prm, 1u << dj, 4u << dj);
                             o4[2 * q] = (int)a; o4[2 * q + 1] = (int)b;
                             if (q == 0) m2.x = mk; else m2.y = mk;
                         }
@@ -429,7 +439,7 @@ __global__ __launch_bounds__(256, 2) void c8_conv_kernel(C8G g) {
                             bits |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)bits, 0xB1, 0xF, 0xF, false);
                         }
                         bits |= (m > 0.f ? 16u : 0u) | (m < 0.f ? 32u : 0u);
-                        o8[e] = (_Float16)m;
+                        o8[e] = (typename E::T)(m);
                         mb[e] = bits;
                     }
                     if (ok && dj == 0 && oct < g.K8) {
@@ -468,12 +478,12 @@ __global__ __launch_bounds__(256, 2) void c8_conv_kernel(C8G g) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             float v = acc[f][pt][h * 8 + e];
-                            if (g.prev_a) v *= actg((float)pa[f][h][e]);
-                            o8[e] = (_Float16)v;
+                            if (g.prev_a) v *= actg((float)(pa[f][h][e]));
+                            o8[e] = (typename E::T)(v);
                         }
                     } else {
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) o8[e] = (_Float16)actf(acc[f][pt][h * 8 + e]);
+                        for (int e = 0; e < 8; ++e) o8[e] = (typename E::T)(actf(acc[f][pt][h * 8 + e]));
                     }
                     if (pok[pt] && oct < g.K8) reinterpret_cast<half8*>(g.out)[pbase + (unsigned)oct * Ho * Wo] = o8;
                 }
@@ -536,8 +546,8 @@ __global__ __launch_bounds__(256, 2) void c8_conv_kernel(C8G g) {
             }
 #pragma unroll
             for (int f = 0; f < FT; ++f) {
-                acc[f][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cur][f], b[cur][0], acc[f][0], 0, 0, 0);
-                acc[f][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cur][f], b[cur][1], acc[f][1], 0, 0, 0);
+                acc[f][0] = E::mfma(a[cur][f], b[cur][0], acc[f][0]);
+                acc[f][1] = E::mfma(a[cur][f], b[cur][1], acc[f][1]);
             }
             __builtin_amdgcn_sched_group_barrier(0x100, FT + 2, 0);       // DS reads of the next tap
             __builtin_amdgcn_sched_group_barrier(0x008, 2 * FT, 0);       // then this tap's MFMAs
@@ -610,7 +620,7 @@ static bool c8_tap_packed(int C, int dgrad) { return !dgrad && C <= 8; }     // 
 static size_t c8_lds_bytes(const C8G& g, int FT) { return (size_t)2 * (2 * g.plane * 16 + 9 * 2 * 32 * FT * 16); }
 
 static unsigned long long* c8_dbg_buf = nullptr;
-extern "C" int tn_c8_dbg_read(tn_ctx* ctx, unsigned long long* host, int nblocks) {
+extern "C" int C8_API(tn_c8_dbg_read)(tn_ctx* ctx, unsigned long long* host, int nblocks) {
     if (!c8_dbg_buf) return -1;
     (void)ctx;
     return hipMemcpy(host, c8_dbg_buf, (size_t)nblocks * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
@@ -634,7 +644,7 @@ static int c8_plan(tn_ctx* ctx, C8G& g, int MODE, int K, int C, C8Plan& p) {
     return TN_OK;
 }
 
-template <int FT, int MODE, bool TK = false>
+template <typename E, int FT, int MODE, bool TK = false>
 static int c8_launch(tn_ctx* ctx, C8G& g, const C8Plan& p) {
     const size_t lds = c8_lds_bytes(g, FT);
     g.nwork = 8 * cdiv(g.MT, 8) * g.KT;
@@ -656,11 +666,11 @@ static int c8_launch(tn_ctx* ctx, C8G& g, const C8Plan& p) {
     {                                                                                                         \
         static bool attr_set = false;                                                                         \
         if (!attr_set) {                                                                                      \
-            TN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c8_conv_kernel<FT, MODE, NS, LK, TK>),  \
+            TN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c8_conv_kernel<E, FT, MODE, NS, LK, TK>),  \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));              \
             attr_set = true;                                                                                  \
         }                                                                                                     \
-        c8_conv_kernel<FT, MODE, NS, LK, TK><<<grid, 256, lds, ctx->stream>>>(g);                             \
+        c8_conv_kernel<E, FT, MODE, NS, LK, TK><<<grid, 256, lds, ctx->stream>>>(g);                             \
     }
     if (!p.LK) C8_GO(4, false)
     else if (p.NS == 2) C8_GO(2, true)
@@ -683,7 +693,7 @@ static size_t c8_wt_total(int K, int C, int dgrad) {
     return c8_tap_packed(C, dgrad) ? (size_t)cdiv(K, KBF) * 5 * 2 * KBF * 8 : c8_wt_elems(K, C);
 }
 
-template <int MODE>
+template <typename E, int MODE>
 static int c8_run(tn_ctx* ctx, C8G& g, const float* W, int K, int C, const void* wt_ready) {
     C8Plan p;
     const int prc = c8_plan(ctx, g, MODE, K, C, p);
@@ -697,26 +707,27 @@ static int c8_run(tn_ctx* ctx, C8G& g, const float* W, int K, int C, const void*
         float* wt;
         int rc = tn_scratch_get(ctx, (size_t)total * sizeof(_Float16), &wt);
         if (rc) return rc;
-        c8_wt_kernel<<<cdiv(total, 256), 256, 0, ctx->stream>>>(W, reinterpret_cast<_Float16*>(wt), K, C, KBF, g.nchunk,
-                                                               total, MODE >= 2 ? 1 : 0, tk ? 1 : 0);
+        c8_wt_kernel<E><<<cdiv(total, 256), 256, 0, ctx->stream>>>(W, reinterpret_cast<typename E::T*>(wt), K, C, KBF,
+                                                                  g.nchunk, total, MODE >= 2 ? 1 : 0, tk ? 1 : 0);
         TN_LAUNCH_CHECK();
         g.wt = reinterpret_cast<const _Float16*>(wt);
     }
     if constexpr (MODE < 2) {
-        if (tk) return FT == 2 ? c8_launch<2, MODE, true>(ctx, g, p) : c8_launch<1, MODE, true>(ctx, g, p);
+        if (tk) return FT == 2 ? c8_launch<E, 2, MODE, true>(ctx, g, p) : c8_launch<E, 1, MODE, true>(ctx, g, p);
     }
-    return FT == 2 ? c8_launch<2, MODE>(ctx, g, p) : c8_launch<1, MODE>(ctx, g, p);
+    return FT == 2 ? c8_launch<E, 2, MODE>(ctx, g, p) : c8_launch<E, 1, MODE>(ctx, g, p);
 }
 
 // every conv layer's arranged weights of a step in ONE launch (a net made eleven 5 us launches of c8_wt_kernel per step)
 struct C8WtBatch {
-    struct { const float* W; _Float16* wt; int K, C, KBF, nchunk, total, dgrad, tk; } s[32];
+    struct { const float* W; _Float16* wt; int K, C, KBF, nchunk, total, dgrad, tk; } s[32];    // wt: E's elements
 };
+template <typename E>
 __global__ __launch_bounds__(256) void c8_wt_multi_kernel(C8WtBatch b) {
     const auto& q = b.s[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= q.total) return;
-    q.wt[idx] = (_Float16)c8_wt_value(q.W, q.K, q.C, q.KBF, q.nchunk, idx, q.dgrad, q.tk);
+    reinterpret_cast<typename E::T*>(q.wt)[idx] = (typename E::T)(c8_wt_value(q.W, q.K, q.C, q.KBF, q.nchunk, idx, q.dgrad, q.tk));
 }
 
 // =================================================================================================
@@ -751,8 +762,9 @@ __device__ __forceinline__ void c8_glds16(const void* gsrc, unsigned lds_dst) {
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
-__device__ __forceinline__ half4v c8_tr16(const char* l) {
-    return __builtin_bit_cast(half4v, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) c8_short4*)l));
+template <typename E>
+__device__ __forceinline__ typename E::v4 c8_tr16(const char* l) {
+    return __builtin_bit_cast(typename E::v4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) c8_short4*)l));
 }
 
 struct C8WG {
@@ -783,9 +795,11 @@ struct C8WG {
 // that came from it is cleared with a v_and.  At 64-pixel rows a halo tile is 4 x 66 cells for 2 x 64 of content: 5 chunks
 // per plane became 2 (32-pixel rows: 4 -> 2, 16-pixel rows: 3 -> 2); the kernel was bound by the LDS-DMA stream
 // (DMA alone 58 k of a block's 87 k cycles on conv2 of wide6).
-template <int NFT, int NCT, bool POOL, int NGX, int TM = 1, bool ROLL = false>
+template <typename E, int NFT, int NCT, bool POOL, int NGX, int TM = 1, bool ROLL = false>
 __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
     extern __shared__ __attribute__((aligned(16))) float ct_smem[];
+    typedef typename E::v8 half8;                     // 8 / 4 elements of the c8 type (halfs or bf16)
+    typedef typename E::v4 half4v;
     static_assert(!ROLL || (NCT != 0 && TM == 1), "ROLL: channel-tiled layers, 128-pixel tiles");
     constexpr int RGB = 2048, ZRO = 4 * RGB;          // ROLL: bytes of a ring region per plane; offset of the zero row
     // eight waves = two per SIMD: while one waits for its LDS operands or sits in the issue of an LDS-DMA (~100 cycles
@@ -977,8 +991,8 @@ __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) accb[r] = 0.f;
     const bool want_db = cg == 0 && ct == 0;
-    const half8 ones = {(_Float16)1.f, (_Float16)1.f, (_Float16)1.f, (_Float16)1.f,
-                        (_Float16)1.f, (_Float16)1.f, (_Float16)1.f, (_Float16)1.f};
+    const half8 ones = {(typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f),
+                        (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f)};
 
     // ---- operand addresses of this lane: group of 16 lanes = 4 pixels x 16 channels; lane (r4, q8) supplies pixel r4,
     // channels 4 q8 .. + 3 of the group's pair of octet planes and receives channel (lane & 15)'s four pixels
@@ -1076,7 +1090,7 @@ __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
             }
             const int p = 16 * (ps + PS * i) + 8 * (grp >> 1) + r4;
             const char* ap = ab + p * 16;
-            const half4v a0 = c8_tr16(ap), a1 = c8_tr16(ap + 64);
+            const half4v a0 = c8_tr16<E>(ap), a1 = c8_tr16<E>(ap + 64);
             const char* xp = bb + (((p >> g.lgP) * g.THi + ((p >> g.lgW) & THm)) * g.RS + (p & Wm)) * 16;
             half4v bv[NACC][2];
             if (ROLL) {
@@ -1092,8 +1106,8 @@ __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
                     const int ro = u == 0 ? (st_top[i] ? top_off : rbase) : u == 1 ? rbase + W16 : (st_bot[i] ? bot_off : rbase + 2 * W16);
 #pragma unroll
                     for (int v = 0; v < 3; ++v) {
-                        bv[(u * 3 + v) % NACC][0] = c8_tr16(xc + ro + v * 16);
-                        bv[(u * 3 + v) % NACC][1] = c8_tr16(xc + ro + v * 16 + 64);
+                        bv[(u * 3 + v) % NACC][0] = c8_tr16<E>(xc + ro + v * 16);
+                        bv[(u * 3 + v) % NACC][1] = c8_tr16<E>(xc + ro + v * 16 + 64);
                     }
                     uint2 e0 = __builtin_bit_cast(uint2, bv[(u * 3) % NACC][0]);
                     e0.x &= mL;
@@ -1105,16 +1119,16 @@ __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
             } else if (TAPK) {
 #pragma unroll
                 for (int jt = 0; jt < 3; ++jt) {
-                    bv[jt][0] = c8_tr16(xp + toff[jt]);
-                    bv[jt][1] = c8_tr16(xp + toff[jt] + 64);
+                    bv[jt][0] = c8_tr16<E>(xp + toff[jt]);
+                    bv[jt][1] = c8_tr16<E>(xp + toff[jt] + 64);
                 }
             } else {
 #pragma unroll
                 for (int u = 0; u < 3; ++u)
 #pragma unroll
                     for (int v = 0; v < 3; ++v) {
-                        bv[(u * 3 + v) % NACC][0] = c8_tr16(xp + u * RS16 + v * 16);
-                        bv[(u * 3 + v) % NACC][1] = c8_tr16(xp + u * RS16 + v * 16 + 64);
+                        bv[(u * 3 + v) % NACC][0] = c8_tr16<E>(xp + u * RS16 + v * 16);
+                        bv[(u * 3 + v) % NACC][1] = c8_tr16<E>(xp + u * RS16 + v * 16 + 64);
                     }
             }
             const half8 a = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
@@ -1122,12 +1136,12 @@ __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
             for (int tp = 0; tp < NACC; ++tp) {
                 const half8 b = {bv[tp][0][0], bv[tp][0][1], bv[tp][0][2], bv[tp][0][3],
                                  bv[tp][1][0], bv[tp][1][1], bv[tp][1][2], bv[tp][1][3]};
-                acc[tp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[tp], 0, 0, 0);
+                acc[tp] = E::mfma(a, b, acc[tp]);
             }
             // the bias product of a step is taken by ONE of the channel-tile waves that share its pixels, alternating by
             // step: with it always on channel tile 0 those waves ran 10 MFMAs per step against 9 and the others waited
             // for them at every tile's barrier
-            if (cg == 0 && (NCTe == 1 || (i & 1) == ct)) accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, ones, accb, 0, 0, 0);
+            if (cg == 0 && (NCTe == 1 || (i & 1) == ct)) accb = E::mfma(a, ones, accb);
             issue_range(std::integral_constant<int, J0>{}, std::integral_constant<int, J1>{});
         };
 #define C8W_ST(I) if (NSTEP > I) step(std::integral_constant<int, (I) % NSTEP>{});
@@ -1290,9 +1304,11 @@ __global__ __launch_bounds__(512) void c8_wgrad_kernel(C8WG g) {
 #ifndef C8W_ABL
 #define C8W_ABL 0
 #endif
-template <int NCT, int NGX, bool POOL, bool ROLL>
+template <typename E, int NCT, int NGX, bool POOL, bool ROLL>
 __global__ __launch_bounds__(1024) void c8_wgrad_tr_kernel(C8WG g) {
     extern __shared__ __attribute__((aligned(16))) float ct_smem[];
+    typedef typename E::v8 half8;                     // 8 / 4 elements of the c8 type (halfs or bf16)
+    typedef typename E::v4 half4v;
     constexpr int RGB = 2048, ZRO = 4 * RGB;
     // NCT = 2: 64 channels, wave = (filter tile, channel tile, tap row), all eight steps of a tile.  NCT = 1: 32 channels
     // (conv2 of cifar_like), wave = (filter tile, tap row, step subset): PS = 2 interleaved subsets of four steps, added up
@@ -1497,8 +1513,8 @@ __global__ __launch_bounds__(1024) void c8_wgrad_tr_kernel(C8WG g) {
     } else {
         // ================================ compute waves: tap row u of a 32 x 32 tile ================================
         const bool want_b = cg == 0;
-        const half8 ones = {(_Float16)1.f, (_Float16)1.f, (_Float16)1.f, (_Float16)1.f,
-                            (_Float16)1.f, (_Float16)1.f, (_Float16)1.f, (_Float16)1.f};
+        const half8 ones = {(typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f),
+                            (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f)};
         const int grp = lane >> 4, r4 = (lane >> 2) & 3, q8 = lane & 3;
         const int a_off = g.offD + (ft * 4 + 2 * (grp & 1) + (q8 >> 1)) * g.DPS + (q8 & 1) * 8;
         const int b_off = (ct * 4 + 2 * (grp & 1) + (q8 >> 1)) * g.XPS + (q8 & 1) * 8;
@@ -1552,7 +1568,7 @@ __global__ __launch_bounds__(1024) void c8_wgrad_tr_kernel(C8WG g) {
                 if (C8W_ABL & 2) {
 #pragma unroll
                     for (int b_ = 0; b_ < 2; ++b_) {
-                        av[b_][0] = av[b_][1] = half4v{(_Float16)lane, (_Float16)1.f, (_Float16)2.f, (_Float16)3.f};
+                        av[b_][0] = av[b_][1] = half4v{(typename E::T)lane, (typename E::T)(1.f), (typename E::T)(2.f), (typename E::T)(3.f)};
 #pragma unroll
                         for (int v = 0; v < 3; ++v) bv[b_][v][0] = bv[b_][v][1] = av[b_][0];
                     }
@@ -1561,8 +1577,8 @@ __global__ __launch_bounds__(1024) void c8_wgrad_tr_kernel(C8WG g) {
                     constexpr int i = decltype(Ic)::value, B_ = i & 1, gi = NCT == 2 ? i : X + PS * i;     // gi: step of the tile
                     const int p = 16 * gi + l16;
                     if (C8W_ABL & 2) return;
-                    av[B_][0] = c8_tr16(a_lane + 256 * gi);
-                    av[B_][1] = c8_tr16(a_lane + 256 * gi + 64);
+                    av[B_][0] = c8_tr16<E>(a_lane + 256 * gi);
+                    av[B_][1] = c8_tr16<E>(a_lane + 256 * gi + 64);
                     const char* xp;
                     if (ROLL) {
                         const int rbase = reg_off + st_ro[i];
@@ -1573,8 +1589,8 @@ __global__ __launch_bounds__(1024) void c8_wgrad_tr_kernel(C8WG g) {
                     }
 #pragma unroll
                     for (int v = 0; v < 3; ++v) {
-                        bv[B_][v][0] = c8_tr16(xp + v * 16);
-                        bv[B_][v][1] = c8_tr16(xp + v * 16 + 64);
+                        bv[B_][v][0] = c8_tr16<E>(xp + v * 16);
+                        bv[B_][v][1] = c8_tr16<E>(xp + v * 16 + 64);
                     }
                 };
                 auto mult = [&](auto Ic) __attribute__((always_inline)) {
@@ -1597,11 +1613,11 @@ __global__ __launch_bounds__(1024) void c8_wgrad_tr_kernel(C8WG g) {
                         const half8 b = {bv[B_][v][0][0], bv[B_][v][0][1], bv[B_][v][0][2], bv[B_][v][0][3],
                                          bv[B_][v][1][0], bv[B_][v][1][1], bv[B_][v][1][2], bv[B_][v][1][3]};
                         if (C8W_ABL & 1) { asm volatile("" :: "v"(a), "v"(b)); continue; }      // (the reads stay: their values are "used")
-                        acc[v] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[v], 0, 0, 0);
+                        acc[v] = E::mfma(a, b, acc[v]);
                     }
                     // the bias product of a step: ONE of the waves that share its dz operand, known at compile time
                     if ((NCT == 2 ? (i % 3 == U && ((i / 3) & 1) == X) : (i % 3 == U)) && want_b && !(C8W_ABL & 1))
-                        accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, ones, accb, 0, 0, 0);
+                        accb = E::mfma(a, ones, accb);
                 };
                 load(std::integral_constant<int, 0>{});
                 // (forcing the next step's reads between this step's products with sched_group_barrier -- product, three
@@ -1818,11 +1834,11 @@ static size_t c8w_lds_bytes(const C8WG& g) {
     return a > red ? a : red;
 }
 
-template <int NFT, int NCT, bool POOL, int NGX, int TM = 1, bool ROLL = false>
+template <typename E, int NFT, int NCT, bool POOL, int NGX, int TM = 1, bool ROLL = false>
 static int c8w_launch(tn_ctx* ctx, C8WG& g) {
     static bool attr_set = false;
     if (!attr_set) {
-        TN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c8_wgrad_kernel<NFT, NCT, POOL, NGX, TM, ROLL>),
+        TN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c8_wgrad_kernel<E, NFT, NCT, POOL, NGX, TM, ROLL>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
@@ -1845,17 +1861,17 @@ static int c8w_launch(tn_ctx* ctx, C8WG& g) {
         }
         g.exp = exp_;
     }
-    c8_wgrad_kernel<NFT, NCT, POOL, NGX, TM, ROLL><<<grid, 512, c8w_lds_bytes(g), ctx->stream>>>(g);
+    c8_wgrad_kernel<E, NFT, NCT, POOL, NGX, TM, ROLL><<<grid, 512, c8w_lds_bytes(g), ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
 // the sixteen-wave form (c8_wgrad_tr_kernel): x chunks per LOADER wave and stage
-template <int NCT, int NGX, bool POOL, bool ROLL>
+template <typename E, int NCT, int NGX, bool POOL, bool ROLL>
 static int c8w_tr_launch(tn_ctx* ctx, C8WG& g) {
     static bool attr_set = false;
     if (!attr_set) {
-        TN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c8_wgrad_tr_kernel<NCT, NGX, POOL, ROLL>),
+        TN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c8_wgrad_tr_kernel<E, NCT, NGX, POOL, ROLL>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
@@ -1870,7 +1886,7 @@ static int c8w_tr_launch(tn_ctx* ctx, C8WG& g) {
         TN_HIP(hipMemsetAsync(c8_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream));
         g.dbg = grid <= 65536 ? c8_dbg_buf : nullptr;
     }
-    c8_wgrad_tr_kernel<NCT, NGX, POOL, ROLL><<<grid, 1024, c8w_lds_bytes(g), ctx->stream>>>(g);
+    c8_wgrad_tr_kernel<E, NCT, NGX, POOL, ROLL><<<grid, 1024, c8w_lds_bytes(g), ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
@@ -1922,36 +1938,37 @@ static int c8w_plan(tn_ctx* ctx, C8WG& g, int num_cus, bool pool, C8WPlan& p) {
     return TN_OK;
 }
 
-template <int NCT, bool POOL>
+template <typename E, int NCT, bool POOL>
 static int c8w_tr_go(tn_ctx* ctx, C8WG& g, const C8WPlan& p) {
-    if (p.ROLL) return c8w_tr_launch<NCT, 2 * NCT, POOL, true>(ctx, g);
+    if (p.ROLL) return c8w_tr_launch<E, NCT, 2 * NCT, POOL, true>(ctx, g);
     switch (p.NGX / NCT) {
-        case 2: return c8w_tr_launch<NCT, 2 * NCT, POOL, false>(ctx, g);
-        case 3: return c8w_tr_launch<NCT, 3 * NCT, POOL, false>(ctx, g);
-        case 4: return c8w_tr_launch<NCT, 4 * NCT, POOL, false>(ctx, g);
-        case 5: return c8w_tr_launch<NCT, 5 * NCT, POOL, false>(ctx, g);
+        case 2: return c8w_tr_launch<E, NCT, 2 * NCT, POOL, false>(ctx, g);
+        case 3: return c8w_tr_launch<E, NCT, 3 * NCT, POOL, false>(ctx, g);
+        case 4: return c8w_tr_launch<E, NCT, 4 * NCT, POOL, false>(ctx, g);
+        case 5: return c8w_tr_launch<E, NCT, 5 * NCT, POOL, false>(ctx, g);
     }
     return tn_fail(ctx, TN_E_ARG, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
 }
 
-template <int NFT, int NCT, bool POOL>
+template <typename E, int NFT, int NCT, bool POOL>
 static int c8w_launch_ng(tn_ctx* ctx, C8WG& g, const C8WPlan& p) {
     if constexpr (NCT == 0) {
-        if (p.TM == 4) return c8w_launch<NFT, 0, POOL, 2, 4>(ctx, g);
-        if (p.TM == 2) return c8w_launch<NFT, 0, POOL, 1, 2>(ctx, g);
-        return p.NGX == 1 ? c8w_launch<NFT, 0, POOL, 1>(ctx, g) : c8w_launch<NFT, 0, POOL, 2>(ctx, g);
+        if (p.TM == 4) return c8w_launch<E, NFT, 0, POOL, 2, 4>(ctx, g);
+        if (p.TM == 2) return c8w_launch<E, NFT, 0, POOL, 1, 2>(ctx, g);
+        return p.NGX == 1 ? c8w_launch<E, NFT, 0, POOL, 1>(ctx, g) : c8w_launch<E, NFT, 0, POOL, 2>(ctx, g);
     } else {
-        if (p.ROLL) return c8w_launch<NFT, NCT, POOL, NCT, 1, true>(ctx, g);
+        if (p.ROLL) return c8w_launch<E, NFT, NCT, POOL, NCT, 1, true>(ctx, g);
         switch (p.NGX) {
-            case 2: return c8w_launch<NFT, NCT, POOL, 2>(ctx, g);
-            case 3: return c8w_launch<NFT, NCT, POOL, 3>(ctx, g);
-            case 4: return c8w_launch<NFT, NCT, POOL, 4>(ctx, g);
-            case 5: return c8w_launch<NFT, NCT, POOL, 5>(ctx, g);
+            case 2: return c8w_launch<E, NFT, NCT, POOL, 2>(ctx, g);
+            case 3: return c8w_launch<E, NFT, NCT, POOL, 3>(ctx, g);
+            case 4: return c8w_launch<E, NFT, NCT, POOL, 4>(ctx, g);
+            case 5: return c8w_launch<E, NFT, NCT, POOL, 5>(ctx, g);
         }
         return tn_fail(ctx, TN_E_ARG, "c8 conv wgrad: %d LDS-DMA chunks per x stage", g.nQx);
     }
 }
 
+template <typename E>
 static int c8w_run(tn_ctx* ctx, C8WG& g, float* dW, float* db, bool pool) {
     C8WPlan p;
     int rc = c8w_plan(ctx, g, ctx->num_cus, pool, p);
@@ -1961,10 +1978,10 @@ static int c8w_run(tn_ctx* ctx, C8WG& g, float* dW, float* db, bool pool) {
     if (rc) return rc;
     g.dbws = g.ws + (size_t)g.S * n;
     g.oscale = 1.f / ctx->grad_scale;
-#define C8W_GO(A, B) rc = pool ? c8w_launch_ng<A, B, true>(ctx, g, p) : c8w_launch_ng<A, B, false>(ctx, g, p)
+#define C8W_GO(A, B) rc = pool ? c8w_launch_ng<E, A, B, true>(ctx, g, p) : c8w_launch_ng<E, A, B, false>(ctx, g, p)
     if (p.tr) {
-        if (p.NCT == 2) rc = pool ? c8w_tr_go<2, true>(ctx, g, p) : c8w_tr_go<2, false>(ctx, g, p);
-        else rc = pool ? c8w_tr_go<1, true>(ctx, g, p) : c8w_tr_go<1, false>(ctx, g, p);
+        if (p.NCT == 2) rc = pool ? c8w_tr_go<E, 2, true>(ctx, g, p) : c8w_tr_go<E, 2, false>(ctx, g, p);
+        else rc = pool ? c8w_tr_go<E, 1, true>(ctx, g, p) : c8w_tr_go<E, 1, false>(ctx, g, p);
     } else if (p.NCT == 0 && p.NFT == 2) C8W_GO(2, 0);
     else if (p.NCT == 0) C8W_GO(1, 0);
     else if (p.NFT == 2 && p.NCT == 2) C8W_GO(2, 2);
@@ -1982,7 +1999,8 @@ static int c8w_run(tn_ctx* ctx, C8WG& g, float* dW, float* db, bool pool) {
 
 // ---- NCHW fp32 <-> c8 fp16 -------------------------------------------------------------------------------
 // one thread = one cell (8 channels of a pixel); rows row0.. of the source (a minibatch window of a dataset)
-__global__ __launch_bounds__(256) void c8_pack_kernel(const float* __restrict__ x, _Float16* __restrict__ out, int C, int C8,
+template <typename E>
+__global__ __launch_bounds__(256) void c8_pack_kernel(const float* __restrict__ x, typename E::T* __restrict__ out, int C, int C8,
                                                      int HW, size_t cells, float scale) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= cells) return;
@@ -1990,16 +2008,17 @@ __global__ __launch_bounds__(256) void c8_pack_kernel(const float* __restrict__ 
     const size_t pl = i / HW;
     const int o = (int)(pl % C8);
     const size_t n = pl / C8;
-    half8 h;
+    typename E::v8 h;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int c = o * 8 + e;
-        h[e] = (_Float16)(c < C ? scale * x[(n * C + c) * HW + p] : 0.f);
+        h[e] = (typename E::T)(c < C ? scale * x[(n * C + c) * HW + p] : 0.f);
     }
-    reinterpret_cast<half8*>(out)[i] = h;
+    reinterpret_cast<typename E::v8*>(out)[i] = h;
 }
 // one thread = 4 consecutive pixels of one channel (16-byte store)
-__global__ __launch_bounds__(256) void c8_unpack_kernel(const _Float16* __restrict__ x, float* __restrict__ out, int C,
+template <typename E>
+__global__ __launch_bounds__(256) void c8_unpack_kernel(const typename E::T* __restrict__ x, float* __restrict__ out, int C,
                                                        int C8, int HW, size_t quads, float scale) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= quads) return;
@@ -2008,15 +2027,28 @@ __global__ __launch_bounds__(256) void c8_unpack_kernel(const _Float16* __restri
     const size_t pl = i / q4;
     const int c = (int)(pl % C);
     const size_t n = pl / C;
-    const _Float16* src = x + ((n * C8 + (c >> 3)) * HW + 4 * q) * 8 + (c & 7);
+    const typename E::T* src = x + ((n * C8 + (c >> 3)) * HW + 4 * q) * 8 + (c & 7);
     *reinterpret_cast<float4*>(out + (n * C + c) * HW + 4 * q) =
-        make_float4(scale * (float)src[0], scale * (float)src[8], scale * (float)src[16], scale * (float)src[24]);
+        make_float4(scale * (float)(src[0]), scale * (float)(src[8]), scale * (float)(src[16]), scale * (float)(src[24]));
 }
 
 extern "C" {
 
+#ifndef C8_BF16_TU
+// the bf16 entry points (conv_c8_bf16.hip)
+int c8b_tn_c8_arrange_multi(tn_ctx* ctx, const tn_c8_wt_seg* segs, int nseg);
+int c8b_tn_c8_conv_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, uint8_t* mask, int N, int C,
+                       int H, int Wd, int K, int act, float prm, int pool, const void* wt);
+int c8b_tn_c8_conv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int H, int Wd, int K,
+                         const void* prev_a, int prev_act, float prev_prm, int pooled, const uint8_t* mask, const void* wt);
+int c8b_tn_c8_conv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int H, int Wd,
+                         int K, int pooled, const uint8_t* mask);
+int c8b_tn_c8_pack(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int HW, float scale);
+int c8b_tn_c8_unpack(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, float scale);
+#endif
+
 // 1 if the c8 kernels take a 3x3 'same' stride-1 layer of this shape (forward, both gradients)
-int tn_c8_conv_supported(int N, int C, int H, int W, int K, int f, int stride, int pad) {
+int C8_API(tn_c8_conv_supported)(int N, int C, int H, int W, int K, int f, int stride, int pad) {
     if (f != 3 || stride != 1 || pad != 1 || (K & 7)) return 0;
     C8G g{};
     g.N = N; g.H = H; g.W = W;
@@ -2030,10 +2062,11 @@ int tn_c8_conv_supported(int N, int C, int H, int W, int K, int f, int stride, i
 // y = act(conv(x, W) + b) [pool != 0: followed by a 2x2 max-pool; mask (may be NULL) records the window elements
 // that attained each maximum and the sign of the pooled value]; x, y c8 fp16, W (K, C, 3, 3) and b fp32
 // halfs of the arranged-weight buffer of a layer's forward (dgrad == 0) or input-gradient (dgrad != 0) product
-size_t tn_c8_wt_elems(int K, int C, int dgrad) { return dgrad ? c8_wt_elems(C, K) : c8_wt_elems(K, C); }
+size_t C8_API(tn_c8_wt_elems)(int K, int C, int dgrad) { return dgrad ? c8_wt_elems(C, K) : c8_wt_elems(K, C); }
 
 // arranged weights of up to 32 products in one launch; segs: host array of tn_c8_wt_seg
-int tn_c8_arrange_multi(tn_ctx* ctx, const tn_c8_wt_seg* segs, int nseg) {
+int C8_API(tn_c8_arrange_multi)(tn_ctx* ctx, const tn_c8_wt_seg* segs, int nseg) {
+    C8_TO_BF16(tn_c8_arrange_multi, ctx, segs, nseg);
     TN_REQUIRE(nseg >= 0 && nseg <= 32 && (segs != nullptr || nseg == 0), "tn_c8_arrange_multi: 0..32 segments");
     if (!nseg) return TN_OK;
     C8WtBatch b;
@@ -2048,26 +2081,29 @@ int tn_c8_arrange_multi(tn_ctx* ctx, const tn_c8_wt_seg* segs, int nseg) {
         b.s[i].tk = c8_tap_packed(C, segs[i].dgrad) ? 1 : 0;
         if (b.s[i].total > mx) mx = b.s[i].total;
     }
-    c8_wt_multi_kernel<<<dim3(cdiv(mx, 256), nseg), 256, 0, ctx->stream>>>(b);
+    c8_wt_multi_kernel<C8E><<<dim3(cdiv(mx, 256), nseg), 256, 0, ctx->stream>>>(b);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
-int tn_c8_conv_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, uint8_t* mask, int N, int C,
-                   int H, int Wd, int K, int act, float prm, int pool, const void* wt) {
+int C8_API(tn_c8_conv_fwd)(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, uint8_t* mask, int N, int C,
+                           int H, int Wd, int K, int act, float prm, int pool, const void* wt) {
+    C8_TO_BF16(tn_c8_conv_fwd, ctx, x, W, b, y, mask, N, C, H, Wd, K, act, prm, pool, wt);
     TN_REQUIRE((K & 7) == 0, "c8 conv: the number of filters must be a multiple of 8 (got %d)", K);
     C8G g{};
     g.x = static_cast<const _Float16*>(x); g.out = static_cast<_Float16*>(y); g.bias = b; g.mask_out = mask;
     g.N = N; g.C8 = (C + 7) / 8; g.K8 = K / 8; g.H = H; g.W = Wd; g.act = act; g.prm = prm;
-    return pool ? c8_run<1>(ctx, g, W, K, C, wt) : c8_run<0>(ctx, g, W, K, C, wt);
+    return pool ? c8_run<C8E, 1>(ctx, g, W, K, C, wt) : c8_run<C8E, 0>(ctx, g, W, K, C, wt);
 }
 
 // dx (N, C, H, W) = conv^T(dz, W) * act'(prev_a) of the layer below (prev_a NULL: no activation below; for a pooled
 // block below prev_a is its POOLED output and dx has its shape -- the gradient a pooled block receives always carries
 // act'(pooled output)).  pooled != 0: dz is not a tensor: the `dz` argument is the pooled gradient (N, K, H/2, W/2) and
 // dz = (bit of the window element in the block's mask) ? pooled gradient : 0, gathered while staging
-int tn_c8_conv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int H, int Wd, int K,
-                     const void* prev_a, int prev_act, float prev_prm, int pooled, const uint8_t* mask, const void* wt) {
+int C8_API(tn_c8_conv_dgrad)(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int H, int Wd, int K,
+                             const void* prev_a, int prev_act, float prev_prm, int pooled, const uint8_t* mask,
+                             const void* wt) {
+    C8_TO_BF16(tn_c8_conv_dgrad, ctx, dz, W, dx, N, C, H, Wd, K, prev_a, prev_act, prev_prm, pooled, mask, wt);
     TN_REQUIRE((K & 7) == 0, "c8 conv: the number of filters must be a multiple of 8 (got %d)", K);
     TN_REQUIRE(!pooled || mask != nullptr, "c8 conv dgrad: a pooled block needs its mask");
     C8G g{};
@@ -2077,20 +2113,21 @@ int tn_c8_conv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int 
     g.mask_in = mask;
     // the roles of filters and channels swap: "filters" = the C input channels (rounded up to whole octets: the
     // arranged weights of channels beyond C are zero, so their cells come out zero)
-    return pooled ? c8_run<3>(ctx, g, W, C, K, wt) : c8_run<2>(ctx, g, W, C, K, wt);
+    return pooled ? c8_run<C8E, 3>(ctx, g, W, C, K, wt) : c8_run<C8E, 2>(ctx, g, W, C, K, wt);
 }
 
 // dW (K, C, 3, 3), db (K) from x and dz (pooled != 0: dz is gathered from the pooled gradient and the block's mask as in
 // tn_c8_conv_dgrad); dz carries the gradient scale, the results do not
-int tn_c8_conv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int H, int Wd,
-                     int K, int pooled, const uint8_t* mask) {
+int C8_API(tn_c8_conv_wgrad)(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int H, int Wd,
+                             int K, int pooled, const uint8_t* mask) {
+    C8_TO_BF16(tn_c8_conv_wgrad, ctx, x, dz, dW, db, N, C, H, Wd, K, pooled, mask);
     TN_REQUIRE((K & 7) == 0, "c8 conv: the number of filters must be a multiple of 8 (got %d)", K);
     TN_REQUIRE(!pooled || mask != nullptr, "c8 conv wgrad: a pooled block needs its mask");
     C8WG g{};
     g.x = static_cast<const uint4*>(x); g.dz = static_cast<const uint4*>(dz);
     g.mask = reinterpret_cast<const uint2*>(mask);
     g.N = N; g.C = C; g.C8 = (C + 7) / 8; g.H = H; g.Wd = Wd; g.K = K; g.K8 = K / 8;
-    return c8w_run(ctx, g, dW, db, pooled != 0);
+    return c8w_run<C8E>(ctx, g, dW, db, pooled != 0);
 }
 
 // (the answer does not depend on the device's CU count: in c8w_geometry it only sets the number of slabs S and
@@ -2107,7 +2144,7 @@ static int c8_current_cus() {
     }
     return n;
 }
-int tn_c8_conv_wgrad_supported(int N, int C, int H, int Wd, int K) {
+int C8_API(tn_c8_conv_wgrad_supported)(int N, int C, int H, int Wd, int K) {
     const int cus = c8_current_cus();       // (asked every time: the answer must follow the device that is current NOW;
                                             //  what the check reads -- LDS bytes, DMA chunks per stage -- does not depend on it)
     C8WG g{};
@@ -2120,7 +2157,7 @@ int tn_c8_conv_wgrad_supported(int N, int C, int H, int Wd, int K) {
 
 // the kernel a tn_c8_conv_fwd (op 0) / _dgrad (op 1) / _wgrad (op 2) call of this shape launches, from the launchers'
 // own plan functions (layout: include/theanet_hip.h); no context: the current device's CU count as above
-int tn_c8_conv_plan(int op, int N, int C, int H, int Wd, int K, int pool, int act, float prm, int* out, int nout) {
+int C8_API(tn_c8_conv_plan)(int op, int N, int C, int H, int Wd, int K, int pool, int act, float prm, int* out, int nout) {
     int v[13], n = 0;
     if (K & 7) return TN_E_ARG;
     if (op == 2) {
@@ -2150,22 +2187,24 @@ int tn_c8_conv_plan(int op, int N, int C, int H, int Wd, int K, int pool, int ac
 }
 
 // (N, C, H, W) fp32 rows row0.. of x -> c8 fp16 (values times scale); channels beyond C are zero
-int tn_c8_pack(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int HW, float scale) {
+int C8_API(tn_c8_pack)(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int HW, float scale) {
+    C8_TO_BF16(tn_c8_pack, ctx, x, row0, out, N, C, HW, scale);
     const int C8 = (C + 7) / 8;
     const size_t cells = (size_t)N * C8 * HW;
     if (!cells) return TN_OK;
-    c8_pack_kernel<<<(unsigned)cdiv(cells, 256), 256, 0, ctx->stream>>>(x + (size_t)row0 * C * HW,
-                                                                        static_cast<_Float16*>(out), C, C8, HW, cells, scale);
+    c8_pack_kernel<C8E><<<(unsigned)cdiv(cells, 256), 256, 0, ctx->stream>>>(
+        x + (size_t)row0 * C * HW, static_cast<typename C8E::T*>(out), C, C8, HW, cells, scale);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
 // c8 fp16 -> (N, C, H, W) fp32 (values times scale)
-int tn_c8_unpack(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, float scale) {
+int C8_API(tn_c8_unpack)(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, float scale) {
+    C8_TO_BF16(tn_c8_unpack, ctx, x, out, N, C, HW, scale);
     TN_REQUIRE((HW & 3) == 0, "tn_c8_unpack: maps of %d pixels", HW);
     const size_t quads = (size_t)N * C * (HW >> 2);
     if (!quads) return TN_OK;
-    c8_unpack_kernel<<<(unsigned)cdiv(quads, 256), 256, 0, ctx->stream>>>(static_cast<const _Float16*>(x), out, C,
-                                                                          (C + 7) / 8, HW, quads, scale);
+    c8_unpack_kernel<C8E><<<(unsigned)cdiv(quads, 256), 256, 0, ctx->stream>>>(static_cast<const typename C8E::T*>(x), out,
+                                                                               C, (C + 7) / 8, HW, quads, scale);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }

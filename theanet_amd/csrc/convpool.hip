@@ -575,7 +575,7 @@ int tn_convpool_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b,
 int tn_convpool_fwd_mask(tn_ctx* ctx, const float* x, const float* W, const float* b, float* y,
                          uint8_t* mask, int N, int C, int H, int Wd, int K, int f, int pad_lo, int Ho,
                          int Wo, int p, int Hp, int Wp, int act, float act_param) {
-    TN_REQUIRE(!ctx->mm_f16, "tn_convpool_fwd_mask: fp32 tensors in DTYPE float16 mode (the mode's entry points are tn_c8_*)");
+    TN_REQUIRE(!ctx->mm_f16, "tn_convpool_fwd_mask: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
     if (!tn_convpool_supported(C, f, 1, p) &&
         tn_convpool_tile_supported(N, C, H, Wd, K, f, 1, pad_lo, Ho, Wo, p, Hp, Wp))
         return tn_conv_tile_pool_fwd(ctx, x, W, b, y, mask, N, C, H, Wd, K, act, act_param);   // wide layers
@@ -602,7 +602,7 @@ int tn_convpool_bwd_mask_dx(tn_ctx* ctx, const float* x, const float* W, const f
                             int Wd, int K, int f, int pad_lo, int Ho, int Wo, int p, int Hp, int Wp, int act,
                             float act_param, const float* prev_a, int prev_act, float prev_act_param) {
     TN_REQUIRE(x && W && g && y && mask, "tn_convpool_bwd_mask_dx: null argument");
-    TN_REQUIRE(!ctx->mm_f16, "tn_convpool_bwd_mask_dx: fp32 tensors in DTYPE float16 mode (the mode's entry points are tn_c8_*)");
+    TN_REQUIRE(!ctx->mm_f16, "tn_convpool_bwd_mask_dx: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
     TN_REQUIRE(tn_convpool_tile_supported(N, C, H, Wd, K, f, 1, pad_lo, Ho, Wo, p, Hp, Wp),
                "tn_convpool_bwd_mask_dx: unsupported block (C=%d K=%d %dx%d f=%d p=%d)", C, K, H, Wd, f, p);
     return tn_conv_tile_pool_bwd(ctx, x, W, g, y, mask, dx, dW, db, N, C, H, Wd, K, act, act_param, prev_a,

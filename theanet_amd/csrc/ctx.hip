@@ -82,7 +82,7 @@ int tn_ctx_destroy(tn_ctx* ctx) {
 }
 
 int tn_set_matmul_dtype(tn_ctx* ctx, int dtype, float grad_scale) {
-    TN_REQUIRE(dtype == 0 || dtype == 1, "tn_set_matmul_dtype: dtype %d (0 fp32, 1 fp16 operands)", dtype);
+    TN_REQUIRE(dtype >= 0 && dtype <= 2, "tn_set_matmul_dtype: dtype %d (0 fp32, 1 fp16 operands, 2 bf16 operands)", dtype);
     int ex = 0;
     const float m = frexpf(grad_scale, &ex);
     TN_REQUIRE(grad_scale > 0.f && m == 0.5f, "tn_set_matmul_dtype: grad_scale %g is not a power of two", grad_scale);

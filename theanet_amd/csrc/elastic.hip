@@ -6,6 +6,7 @@
 // The gather kernel is the HBM-bound part: x read once, out written once.
 #include <cstdlib>
 
+#include "c8_elem.h"
 #include "common.h"
 #include "update_body.h"
 #include "elastic_field.h"
@@ -186,10 +187,11 @@ __global__ __launch_bounds__(256) void elastic_apply4_kernel(
 // image is neither written nor read back by a packing pass.  thread = ONE pixel x the channels of an octet (a quad per
 // thread ran three channels x 16 gathers in sequence on a quarter of the threads: 26 us against 18 + 12 for the two
 // passes it replaces), one 16-byte store.
-typedef _Float16 el_half8 __attribute__((ext_vector_type(8)));
+// (DTYPE bfloat16: the same with bf16 cells, E = C8B)
+template <typename E>
 __global__ __launch_bounds__(256) void elastic_apply_c8_kernel(
     const float* __restrict__ x, int64_t x_row0, const int64_t* __restrict__ d_row0,
-    _Float16* __restrict__ out, long long total, int C, int C8, int hw, int w, int invert, int nearest,
+    typename E::T* __restrict__ out, long long total, int C, int C8, int hw, int w, int invert, int nearest,
     const int32_t* __restrict__ map_idx, const float* __restrict__ map_fy,
     const float* __restrict__ map_fx, float pflip, const uint8_t* __restrict__ flipmask, uint32_t k0,
     uint32_t k1, uint32_t step, const uint32_t* d_step, int64_t row_global0) {
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(256) void elastic_apply_c8_kernel(
     const bool bil = map_idx && !nearest;
     const float fy = bil ? map_fy[p] : 0.f, fx = bil ? map_fx[p] : 0.f;
     const uint32_t st = step + (d_step ? *d_step : 0u);
-    el_half8 cell;
+    typename E::v8 cell;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int c = 8 * o + e;
@@ -236,9 +238,9 @@ __global__ __launch_bounds__(256) void elastic_apply_c8_kernel(
                 if (tn_u01(rw[t & 3]) < pflip) v = 1.f - v;
             }
         }
-        cell[e] = (_Float16)v;
+        cell[e] = (typename E::T)(v);
     }
-    reinterpret_cast<el_half8*>(out)[(n * C8 + o) * hw + p] = cell;
+    reinterpret_cast<typename E::v8*>(out)[(n * C8 + o) * hw + p] = cell;
 }
 
 // ---- ElasticLayer resampling fused into the first conv block's forward --------------------------
@@ -591,7 +593,7 @@ int tn_elastic_apply(tn_ctx* ctx, const float* x, int64_t x_row0, const int64_t*
     return TN_OK;
 }
 
-// tn_elastic_apply with the c8 fp16 tensor of the first conv layer as its output (DTYPE float16; include/theanet_hip.h)
+// tn_elastic_apply with the c8 tensor of the first conv layer as its output (DTYPE float16 / bfloat16; include/theanet_hip.h)
 int tn_c8_elastic_apply(tn_ctx* ctx, const float* x, int64_t x_row0, const int64_t* d_row0, void* out16,
                         int N, int C, int h, int w, int invert, int nearest, const int32_t* map_idx,
                         const float* map_fy, const float* map_fx, float pflip, const uint8_t* flipmask,
@@ -602,9 +604,14 @@ int tn_c8_elastic_apply(tn_ctx* ctx, const float* x, int64_t x_row0, const int64
     TN_REQUIRE((h * w) % 4 == 0 && al, "tn_c8_elastic_apply: maps of %d x %d pixels / unaligned operands", h, w);
     const int C8 = (C + 7) / 8;
     const long long total = (long long)N * C8 * (h * w);
-    elastic_apply_c8_kernel<<<cdiv(total, 256), 256, 0, ctx->stream>>>(
-        x, x_row0, d_row0, static_cast<_Float16*>(out16), total, C, C8, h * w, w, invert, nearest, map_idx, map_fy, map_fx,
-        pflip, flipmask, (uint32_t)seed, (uint32_t)(seed >> 32), step, d_step, row_global0);
+    if (tn_c8_bf16(ctx))
+        elastic_apply_c8_kernel<C8B><<<cdiv(total, 256), 256, 0, ctx->stream>>>(
+            x, x_row0, d_row0, static_cast<__bf16*>(out16), total, C, C8, h * w, w, invert, nearest, map_idx, map_fy, map_fx,
+            pflip, flipmask, (uint32_t)seed, (uint32_t)(seed >> 32), step, d_step, row_global0);
+    else
+        elastic_apply_c8_kernel<C8H><<<cdiv(total, 256), 256, 0, ctx->stream>>>(
+            x, x_row0, d_row0, static_cast<_Float16*>(out16), total, C, C8, h * w, w, invert, nearest, map_idx, map_fy, map_fx,
+            pflip, flipmask, (uint32_t)seed, (uint32_t)(seed >> 32), step, d_step, row_global0);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }

@@ -19,7 +19,8 @@
 //             16-byte stores of fp16(acc * act'(y)) -- y = the pooled output below, in the same order.
 //   wgrad   : both operands want 8 consecutive SAMPLES per lane but are stored sample-major: tiles go to LDS as they
 //             are (dz converted on the way) and gfx950's transposing LDS read (ds_read_b64_tr_b16) delivers them.
-#include "common.h"
+// (DTYPE 'bfloat16': the same kernels on bf16 cells, element type E = C8B; fc_c8_bf16.hip, c8_elem.h)
+#include "c8_elem.h"
 #include "elastic_field.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -28,8 +29,9 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short fc8_short4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ half4v fc8_tr16(const char* l) {
-    return __builtin_bit_cast(half4v, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fc8_short4*)l));
+template <typename E>
+__device__ __forceinline__ typename E::v4 fc8_tr16(const char* l) {
+    return __builtin_bit_cast(typename E::v4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fc8_short4*)l));
 }
 __host__ __device__ __forceinline__ int fc8_swap23(int j) { return (j & ~12) | ((j & 4) << 1) | ((j & 8) >> 1); }
 
@@ -56,7 +58,7 @@ struct FC8 {
 // shape and gradient scale; consumed or dropped by the next tn_c8_fc_dgrad / any other c8 dense call)
 struct Fc8Dz16Keep {
     tn_ctx* ctx = nullptr; hipStream_t stream = nullptr; const float* dz = nullptr; _Float16* dz16 = nullptr;
-    int B = 0, n_out = 0; float gs = 0.f;
+    int B = 0, n_out = 0, mm = 0; float gs = 0.f;    // mm: the context's dtype (element type of dz16) when it was written
     unsigned long long gen = 0;            // ctx->scratch_gen when it was written: nobody has asked for scratch since
 };
 static Fc8Dz16Keep fc8_dz16_keep;
@@ -69,17 +71,19 @@ __device__ __forceinline__ int fc8_wrow(const FC8& g, int cell, int e, int rows)
     return min((o * 8 + e) * g.HW + p, rows - 1);
 }
 
-__device__ __forceinline__ half8 fc8_cvt8(const float (&v)[8]) {
-    half8 h;
+template <typename E>
+__device__ __forceinline__ typename E::v8 fc8_cvt8(const float (&v)[8]) {
+    typename E::v8 h;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (_Float16)v[j];
+    for (int j = 0; j < 8; ++j) h[j] = (typename E::T)(v[j]);
     return h;
 }
 
 typedef unsigned fc8_u4 __attribute__((ext_vector_type(4)));
 typedef float fc8_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ half4v fc8_cvt4(const fc8_f4 v) {
-    return half4v{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+template <typename E>
+__device__ __forceinline__ typename E::v4 fc8_cvt4(const fc8_f4 v) {
+    return typename E::v4{(typename E::T)(v.x), (typename E::T)(v.y), (typename E::T)(v.z), (typename E::T)(v.w)};
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -145,8 +149,10 @@ static int fc8_xcd_on() {             // TN_FC8_XCD=0: plain block decode (A/B)
 #define FC8F_WS 192         // W tile row stride (64 halfs + 64 bytes = 64 (mod 128): the 4 rows of a transposing read on disjoint banks)
 // FIN: the product has ONE K slab and whole 64-column tiles: bias, activation and dropout happen on the way out and the
 // outputs go straight to g.out (no slab, no finishing launch)
-template <bool FIN>
+template <typename E, bool FIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void fc8_fwd_kernel(FC8 g, Fc8Drop dr) {
+    typedef typename E::v8 half8;                     // 8 / 4 elements of the c8 type (halfs or bf16)
+    typedef typename E::v4 half4v;
     __shared__ __attribute__((aligned(16))) char xs[128 * FC8F_XS];
     __shared__ __attribute__((aligned(16))) char wsm[64 * FC8F_WS];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<fc8_u4*>(xdst + 16 * i) = xr[st][i];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<half4v*>(wdst + 16 * i * FC8F_WS) = fc8_cvt4(wr[st][i]);
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<half4v*>(wdst + 16 * i * FC8F_WS) = fc8_cvt4<E>(wr[st][i]);
     };
     const int grp = lane >> 4, r4 = (lane >> 2) & 3, q4 = lane & 3;
     const char* const ard = xs + (wm * 64 + l31) * FC8F_XS + 16 * hi;
@@ -200,12 +206,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto compute = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const half4v b0 = fc8_tr16(brd + 16 * ks * FC8F_WS), b1 = fc8_tr16(brd + (16 * ks + 4) * FC8F_WS);
+            const half4v b0 = fc8_tr16<E>(brd + 16 * ks * FC8F_WS), b1 = fc8_tr16<E>(brd + (16 * ks + 4) * FC8F_WS);
             const half8 b = half8{b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const half8 a = *reinterpret_cast<const half8*>(ard + 32 * i * FC8F_XS + 32 * ks);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[i], 0, 0, 0);
+                acc[i] = E::mfma(a, b, acc[i]);
             }
         }
     };
@@ -294,18 +300,22 @@ __global__ __launch_bounds__(256) void fc8_fwd_finish_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------
 // dz16[m][n] = fp16(gs * dz[m][n]), rows padded with zeros to a multiple of 64 outputs: the operand every block of the
 // input-gradient product re-reads (Kc / 64 times) at half the bytes, converted once
-__global__ __launch_bounds__(256) void fc8_dz16_kernel(const float* __restrict__ dz, _Float16* __restrict__ out, int M, int N,
-                                                      int Np, float gs) {
+template <typename E>
+__global__ __launch_bounds__(256) void fc8_dz16_kernel(const float* __restrict__ dz, typename E::T* __restrict__ out, int M,
+                                                      int N, int Np, float gs) {
+    typedef typename E::v4 half4v;
     const int i = blockIdx.x * 256 + threadIdx.x;            // one 4-column group
     const int q = Np >> 2, m = i / q, n = 4 * (i - m * q);
     if (m >= M) return;
     fc8_f4 v = {0.f, 0.f, 0.f, 0.f};
     if (n < N) v = *reinterpret_cast<const fc8_f4*>(dz + (size_t)m * N + n) * gs;
-    *reinterpret_cast<half4v*>(out + (size_t)m * Np + n) = fc8_cvt4(v);
+    *reinterpret_cast<half4v*>(out + (size_t)m * Np + n) = fc8_cvt4<E>(v);
 }
 
-template <int NST>                  // ring depth
+template <typename E, int NST>      // element type, ring depth
 __global__ __launch_bounds__(512) void fc8_dgrad_kernel(FC8 g) {
+    typedef typename E::v8 half8;                     // 8 / 4 elements of the c8 type (halfs or bf16)
+    typedef typename E::v4 half4v;
     constexpr int NC = 64, RS = NC * 2 + 16;                 // outputs per chunk; row stride: an odd number of 16-byte slots
     __shared__ __attribute__((aligned(16))) char wl[64 * RS];
     __shared__ __attribute__((aligned(16))) char dl[128 * RS];
@@ -340,7 +350,7 @@ __global__ __launch_bounds__(512) void fc8_dgrad_kernel(FC8 g) {
     };
     auto lstore = [&](int st) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) *reinterpret_cast<half4v*>(wdst + 32 * i * RS) = fc8_cvt4(wr[st][i]);
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<half4v*>(wdst + 32 * i * RS) = fc8_cvt4<E>(wr[st][i]);
 #pragma unroll
         for (int i = 0; i < 2; ++i) *reinterpret_cast<fc8_u4*>(ddst + 64 * i * RS) = dr[st][i];
     };
@@ -351,7 +361,7 @@ __global__ __launch_bounds__(512) void fc8_dgrad_kernel(FC8 g) {
         for (int ks = 0; ks < NC / 16; ++ks) {
             const half8 a = *reinterpret_cast<const half8*>(ard + 32 * ks);
             const half8 b = *reinterpret_cast<const half8*>(brd + 32 * ks);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+            acc = E::mfma(a, b, acc);
         }
     };
 #pragma unroll
@@ -382,10 +392,10 @@ __global__ __launch_bounds__(512) void fc8_dgrad_kernel(FC8 g) {
             for (int e = 0; e < 8; ++e) {
                 float v = acc[h * 8 + e];
                 if (g.ya) {
-                    const float y = (float)y8[e];
+                    const float y = (float)(y8[e]);
                     v *= g.act == TN_ACT_LEAKY ? (y > 0.f ? 1.f : (y < 0.f ? g.prm : tie)) : tn_act_grad_from_out(y, g.act, g.prm);
                 }
-                o8[e] = (_Float16)v;
+                o8[e] = (typename E::T)(v);
             }
             *reinterpret_cast<half8*>(g.dx + o) = o8;
         }
@@ -401,7 +411,10 @@ __global__ __launch_bounds__(512) void fc8_dgrad_kernel(FC8 g) {
 // RIDER: grid layers z >= S carry a light independent job of the step -- the elastic field of the NEXT minibatch
 // (tn_rider_elastic_field; inlayers.py:72-125) -- as extra blocks behind the product, like the fp32 nets' paired GEMM
 // launch does: a float16 net has no such launch, and the field cost its stream a 14 us launch of its own per step.
+template <typename E>
 __global__ __launch_bounds__(256) void fc8_wgrad_kernel(FC8 g, ElField rider, int nrider) {
+    typedef typename E::v8 half8;                     // 8 / 4 elements of the c8 type (halfs or bf16)
+    typedef typename E::v4 half4v;
     __shared__ __attribute__((aligned(16))) char lds[2][64 * FC8_RS];        // [x | dz][sample][column]
     if ((int)blockIdx.z >= g.S) {
         const int rb = (((int)blockIdx.z - g.S) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -426,8 +439,8 @@ __global__ __launch_bounds__(256) void fc8_wgrad_kernel(FC8 g, ElField rider, in
         for (int r = 0; r < 16; ++r) accb[i][r] = 0.f;
     }
     const bool want_db = blockIdx.x == 0 && (wave & 1) == 0;
-    const half8 ones = {(_Float16)1.f, (_Float16)1.f, (_Float16)1.f, (_Float16)1.f,
-                        (_Float16)1.f, (_Float16)1.f, (_Float16)1.f, (_Float16)1.f};
+    const half8 ones = {(typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f),
+                        (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f), (typename E::T)(1.f)};
     // staging: thread -> sample row t >> 2 (64 rows), 32-column quarter t & 3
     const int sr = t >> 2, sq = (t & 3) * 32;
     // transposing reads: group of 16 lanes = 4 samples x 16 columns; lane supplies sample r4, columns 4 q .. 4 q + 3
@@ -458,7 +471,7 @@ __global__ __launch_bounds__(256) void fc8_wgrad_kernel(FC8 g, ElField rider, in
             const bool in = ok && n0 + sq + 4 * i < g.N;
             const float s = in ? g.gs : 0.f;
             const float f[8] = {dv[i].x * s, dv[i].y * s, dv[i].z * s, dv[i].w * s, dv[i + 1].x * s, dv[i + 1].y * s, dv[i + 1].z * s, dv[i + 1].w * s};
-            const half8 h8 = fc8_cvt8(f);
+            const half8 h8 = fc8_cvt8<E>(f);
             *reinterpret_cast<half8*>(lds[1] + sr * FC8_RS + (sq + 4 * i) * 2) = h8;
             // the blocks of row tile 0 keep what they rounded: fp16(gs dz), (M, Np), zeros beyond N -- exactly what
             // fc8_dz16_kernel writes for tn_c8_fc_dgrad (which then skips that 5 us launch)
@@ -473,19 +486,19 @@ __global__ __launch_bounds__(256) void fc8_wgrad_kernel(FC8 g, ElField rider, in
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const char* ap = lds[0] + ks * 16 * FC8_RS + rd + (wk + 32 * i) * 2;
-                const half4v a0 = fc8_tr16(ap), a1 = fc8_tr16(ap + 4 * FC8_RS);
+                const half4v a0 = fc8_tr16<E>(ap), a1 = fc8_tr16<E>(ap + 4 * FC8_RS);
                 a[i] = half8{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
                 const char* bp = lds[1] + ks * 16 * FC8_RS + rd + (wn + 32 * i) * 2;
-                const half4v b0 = fc8_tr16(bp), b1 = fc8_tr16(bp + 4 * FC8_RS);
+                const half4v b0 = fc8_tr16<E>(bp), b1 = fc8_tr16<E>(bp + 4 * FC8_RS);
                 b[i] = half8{b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acc[i][j] = E::mfma(a[i], b[j], acc[i][j]);
             if (want_db) {
-                accb[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, b[0], accb[0], 0, 0, 0);
-                accb[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, b[1], accb[1], 0, 0, 0);
+                accb[0] = E::mfma(ones, b[0], accb[0]);
+                accb[1] = E::mfma(ones, b[1], accb[1]);
             }
         }
     }
@@ -550,8 +563,20 @@ static int fc8_check(tn_ctx* ctx, int B, int C, int HW, int n_out, const char* w
 
 extern "C" {
 
+#ifndef C8_BF16_TU
+// the bf16 entry points (fc_c8_bf16.hip)
+int c8b_tn_c8_fc_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW, int n_out,
+                     int act, float act_param, const uint8_t* mask);
+int c8b_tn_c8_fc_fwd_dropout(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW,
+                             int n_out, int act, float act_param, uint8_t* mask_out, float pdrop, uint64_t seed,
+                             uint32_t step, const uint32_t* d_step, uint64_t elem0);
+int c8b_tn_c8_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B, int C, int HW, int n_out,
+                       const void* y, int act, float act_param);
+int c8b_tn_c8_fc_wgrad(tn_ctx* ctx, const void* x, const float* dz, float* dW, float* db, int B, int C, int HW, int n_out);
+#endif
+
 // 1 if the fp16-resident FC products take this layer (input = C maps of HW pixels, c8 order; HW = 1: a plain matrix)
-int tn_c8_fc_supported(int B, int C, int HW, int n_out) {
+int C8_API(tn_c8_fc_supported)(int B, int C, int HW, int n_out) {
     const int Kc = ((C + 7) / 8) * HW * 8;
     return B > 0 && C > 0 && HW > 0 && n_out > 0 && Kc % 64 == 0 && n_out % 32 == 0;
 }
@@ -591,29 +616,32 @@ static int fc8_fwd_run(tn_ctx* ctx, const void* x, const float* W, const float* 
     }
     if (S == 1 && n_out % 64 == 0 && fin_on && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)mask | (uintptr_t)dr.mask_out) & 15) == 0) {
         g.bias = b; g.mask = mask; g.out = a; g.act = act; g.prm = act_param;
-        fc8_fwd_kernel<true><<<dim3(colg, 1, rowg), 256, 0, ctx->stream>>>(g, dr);
+        fc8_fwd_kernel<C8E, true><<<dim3(colg, 1, rowg), 256, 0, ctx->stream>>>(g, dr);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
     rc = tn_scratch_get(ctx, (size_t)S * B * n_out * sizeof(float), &g.ws);
     if (rc) return rc;
-    fc8_fwd_kernel<false><<<dim3(colg, S, rowg), 256, 0, ctx->stream>>>(g, dr);
+    fc8_fwd_kernel<C8E, false><<<dim3(colg, S, rowg), 256, 0, ctx->stream>>>(g, dr);
     TN_LAUNCH_CHECK();
     const size_t MN = (size_t)B * n_out;
     fc8_fwd_finish_kernel<<<cdiv(MN, 256), 256, 0, ctx->stream>>>(g.ws, S, MN, n_out, b, mask, a, act, act_param, dr);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
-int tn_c8_fc_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW, int n_out,
-                 int act, float act_param, const uint8_t* mask) {
+int C8_API(tn_c8_fc_fwd)(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW,
+                         int n_out, int act, float act_param, const uint8_t* mask) {
+    C8_TO_BF16(tn_c8_fc_fwd, ctx, x, W, b, a, B, C, HW, n_out, act, act_param, mask);
     return fc8_fwd_run(ctx, x, W, b, a, B, C, HW, n_out, act, act_param, mask, Fc8Drop{});
 }
 // the same with the dropout mask drawn by the finishing kernel (dropout.py:12: keep = u01 >= pdrop, no rescale) and
 // written to mask_out for the backward pass: the numbers of tn_dropout_mask(mask_out, B * n_out, pdrop, seed, step,
 // d_step, elem0), one launch and one pass over the mask less
-int tn_c8_fc_fwd_dropout(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW,
-                         int n_out, int act, float act_param, uint8_t* mask_out, float pdrop, uint64_t seed, uint32_t step,
-                         const uint32_t* d_step, uint64_t elem0) {
+int C8_API(tn_c8_fc_fwd_dropout)(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C,
+                                 int HW, int n_out, int act, float act_param, uint8_t* mask_out, float pdrop, uint64_t seed,
+                                 uint32_t step, const uint32_t* d_step, uint64_t elem0) {
+    C8_TO_BF16(tn_c8_fc_fwd_dropout, ctx, x, W, b, a, B, C, HW, n_out, act, act_param, mask_out, pdrop, seed, step, d_step,
+               elem0);
     TN_REQUIRE(mask_out != nullptr, "tn_c8_fc_fwd_dropout: NULL mask");
     Fc8Drop dr{mask_out, pdrop, (uint32_t)seed, (uint32_t)(seed >> 32), step, d_step, elem0};
     return fc8_fwd_run(ctx, x, W, b, a, B, C, HW, n_out, act, act_param, nullptr, dr);
@@ -621,8 +649,9 @@ int tn_c8_fc_fwd_dropout(tn_ctx* ctx, const void* x, const float* W, const float
 
 // dx16 (B, C8*HW*8) halfs = fp16(gs * dz . W^T * act'(y16)): dz (B, n_out) fp32 = d cost / d z of this layer, y16 = output
 // of the layer below in x's order (NULL: none), (act, prm) its activation.  dx carries the gradient scale.
-int tn_c8_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B, int C, int HW, int n_out, const void* y,
-                   int act, float act_param) {
+int C8_API(tn_c8_fc_dgrad)(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B, int C, int HW, int n_out,
+                           const void* y, int act, float act_param) {
+    C8_TO_BF16(tn_c8_fc_dgrad, ctx, dz, W, dx, B, C, HW, n_out, y, act, act_param);
     int rc = fc8_check(ctx, B, C, HW, n_out, "tn_c8_fc_dgrad");
     if (rc) return rc;
     FC8 g{};
@@ -633,7 +662,7 @@ int tn_c8_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B
     g.Np = cdiv(n_out, 64) * 64;
     const Fc8Dz16Keep kp = fc8_dz16_keep;
     fc8_dz16_keep = Fc8Dz16Keep{};
-    if (kp.ctx == ctx && kp.stream == ctx->stream && kp.dz == dz && kp.B == B && kp.n_out == n_out && kp.gs == g.gs &&
+    if (kp.ctx == ctx && kp.stream == ctx->stream && kp.dz == dz && kp.B == B && kp.n_out == n_out && kp.gs == g.gs && kp.mm == ctx->mm_f16 &&
         kp.gen == ctx->scratch_gen) {
         g.dz16 = kp.dz16;                    // the weight-gradient launch right in front of this call wrote it
     } else {
@@ -641,16 +670,19 @@ int tn_c8_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B
         rc = tn_scratch_get(ctx, (size_t)B * g.Np * sizeof(_Float16), reinterpret_cast<float**>(&dz16));
         if (rc) return rc;
         g.dz16 = dz16;
-        fc8_dz16_kernel<<<cdiv((size_t)B * (g.Np / 4), 256), 256, 0, ctx->stream>>>(dz, dz16, B, n_out, g.Np, g.gs);
+        fc8_dz16_kernel<C8E><<<cdiv((size_t)B * (g.Np / 4), 256), 256, 0, ctx->stream>>>(
+            dz, reinterpret_cast<typename C8E::T*>(dz16), B, n_out, g.Np, g.gs);
         TN_LAUNCH_CHECK();
     }
-    fc8_dgrad_kernel<4><<<dim3(g.Kc / 64, cdiv(B, 128)), 512, 0, ctx->stream>>>(g);
+    fc8_dgrad_kernel<C8E, 4><<<dim3(g.Kc / 64, cdiv(B, 128)), 512, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
 // dW (C*HW, n_out), db (n_out) fp32 from x16 and dz (fp32, rounded as fp16(gs * dz) while staged)
-int tn_c8_fc_wgrad(tn_ctx* ctx, const void* x, const float* dz, float* dW, float* db, int B, int C, int HW, int n_out) {
+int C8_API(tn_c8_fc_wgrad)(tn_ctx* ctx, const void* x, const float* dz, float* dW, float* db, int B, int C, int HW,
+                           int n_out) {
+    C8_TO_BF16(tn_c8_fc_wgrad, ctx, x, dz, dW, db, B, C, HW, n_out);
     int rc = fc8_check(ctx, B, C, HW, n_out, "tn_c8_fc_wgrad");
     if (rc) return rc;
     FC8 g{};
@@ -695,18 +727,18 @@ int tn_c8_fc_wgrad(tn_ctx* ctx, const void* x, const float* dz, float* dW, float
     }
     if (keep_on) {
         g.dz16w = reinterpret_cast<_Float16*>(scr + slabf4);
-        fc8_dz16_keep = {ctx, ctx->stream, dz, g.dz16w, B, n_out, ctx->grad_scale, ctx->scratch_gen};
+        fc8_dz16_keep = {ctx, ctx->stream, dz, g.dz16w, B, n_out, ctx->mm_f16, ctx->grad_scale, ctx->scratch_gen};
     }
     if (S == 1) {
         g.ws = dW; g.dbws = db;
         // (channels beyond C own no row of dW: nothing to clear)
-        fc8_wgrad_kernel<<<dim3(kb, nb, 1 + zr), 256, 0, ctx->stream>>>(g, rider, nrider);
+        fc8_wgrad_kernel<C8E><<<dim3(kb, nb, 1 + zr), 256, 0, ctx->stream>>>(g, rider, nrider);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
     g.ws = scr;
     g.dbws = g.ws + (size_t)S * n;
-    fc8_wgrad_kernel<<<dim3(kb, nb, S + zr), 256, 0, ctx->stream>>>(g, rider, nrider);
+    fc8_wgrad_kernel<C8E><<<dim3(kb, nb, S + zr), 256, 0, ctx->stream>>>(g, rider, nrider);
     TN_LAUNCH_CHECK();
     rc = tn_red_push(ctx, g.ws, dW, (uint32_t)n, (uint32_t)S, (uint32_t)n, 0);
     if (rc) return rc;

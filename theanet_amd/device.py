@@ -12,6 +12,11 @@ import numpy as np
 
 from . import _lib
 
+# DTYPE values whose conv stack is 16-bit resident (device.C8Array, the tn_c8_* / tn_fc8_* kernels), and the
+# tn_set_matmul_dtype mode of every DTYPE
+C8_DTYPES = ("float16", "bfloat16")
+_MM_MODES = {"float32": 0, "float16": 1, "bfloat16": 2}
+
 _context = None
 
 
@@ -95,11 +100,11 @@ class Context:
         self.call("tn_sync")
 
     def set_matmul_dtype(self, dtype, grad_scale=1.0):
-        """'float32' (the reference's floatX) or 'float16' = fp16 operands / fp32 accumulation for the
-        3x3 conv products (tn_set_matmul_dtype); a no-op when already in that mode."""
-        want = (dtype, float(grad_scale) if dtype == "float16" else 1.0)
+        """'float32' (the reference's floatX), 'float16' or 'bfloat16' = 16-bit operands / fp32 accumulation for the
+        3x3 conv products (tn_set_matmul_dtype modes 0 / 1 / 2); a no-op when already in that mode."""
+        want = (dtype, float(grad_scale) if dtype in C8_DTYPES else 1.0)
         if want != self._mm_set:
-            self.call("tn_set_matmul_dtype", 1 if dtype == "float16" else 0, want[1])
+            self.call("tn_set_matmul_dtype", _MM_MODES.get(dtype, 0), want[1])
             self._mm_set = want
         self.mm_dtype = dtype
 
@@ -213,26 +218,43 @@ class DeviceArray:
         return "DeviceArray(shape=%s, dtype=%s, ptr=0x%x)" % (self.shape, self.dtype, self.ptr)
 
 
-class C8Array(DeviceArray):
-    """An fp16-RESIDENT activation / gradient tensor (DTYPE 'float16'): logical (N, C, H, W), stored
-    [N][ceil(C/8)][H][W][8] halfs -- one 16-byte cell = the 8 channels of an octet at one pixel, channels beyond C zero
-    (theanet_amd/csrc/conv_c8.hip).  ``get_value`` returns the logical NCHW float32 array."""
+def bf16_bits(x):
+    """float32 -> bf16 bit patterns (uint16), round to nearest even (what v_cvt_pk_bf16_f32 does; NaN stays NaN)."""
+    f = np.ascontiguousarray(x, np.float32)
+    u = f.view(np.uint32)
+    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    return np.where(np.isnan(f), np.uint16(0x7FC0), r)
 
-    def __init__(self, ctx, n, c, h, w):
+
+def bf16_value(bits):
+    """bf16 bit patterns (uint16) -> float32 (exact)."""
+    return (np.asarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+class C8Array(DeviceArray):
+    """A 16-bit-RESIDENT activation / gradient tensor (DTYPE 'float16' / 'bfloat16'): logical (N, C, H, W), stored
+    [N][ceil(C/8)][H][W][8] halfs or bf16 -- one 16-byte cell = the 8 channels of an octet at one pixel, channels beyond
+    C zero (theanet_amd/csrc/conv_c8.hip).  ``elem`` is the element type ('float16' / 'bfloat16'; default: the
+    context's current DTYPE, halfs unless it is 'bfloat16').  ``get_value`` returns the logical NCHW float32 array."""
+
+    def __init__(self, ctx, n, c, h, w, elem=None):
         self.c8 = (int(c), int(h), int(w))
+        self.elem = elem or ("bfloat16" if getattr(ctx, "mm_dtype", None) == "bfloat16" else "float16")
+        assert self.elem in C8_DTYPES, self.elem
         super().__init__(ctx, (n, (c + 7) // 8, h, w, 8), np.uint16)
 
     def get_value(self, borrow=True):
-        raw = DeviceArray.get_value(self).view(np.float16)
+        raw = DeviceArray.get_value(self)
+        raw = bf16_value(raw) if self.elem == "bfloat16" else raw.view(np.float16)
         n, c8, h, w, _ = raw.shape
         return raw.transpose(0, 1, 4, 2, 3).reshape(n, c8 * 8, h, w)[:, :self.c8[0]].astype(np.float32)
 
     def set_value(self, data):
         data = np.asarray(data, np.float32)
         n, c, h, w = data.shape
-        buf = np.zeros((n, self.shape[1] * 8, h, w), np.float16)
-        buf[:, :c] = data.astype(np.float16)
-        DeviceArray.set_value(self, np.ascontiguousarray(buf.reshape(n, self.shape[1], 8, h, w).transpose(0, 1, 3, 4, 2)).view(np.uint16))
+        buf = np.zeros((n, self.shape[1] * 8, h, w), np.uint16)
+        buf[:, :c] = bf16_bits(data) if self.elem == "bfloat16" else data.astype(np.float16).view(np.uint16)
+        DeviceArray.set_value(self, np.ascontiguousarray(buf.reshape(n, self.shape[1], 8, h, w).transpose(0, 1, 3, 4, 2)))
 
 
 class HostBuffer:

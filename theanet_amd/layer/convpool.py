@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from .. import _lib
-from ..device import C8Array
+from ..device import C8_DTYPES, C8Array
 from .layer import Layer, activation_by_name
 from .weights import init_wb
 
@@ -52,7 +52,9 @@ class ConvLayer(Layer):
         # DTYPE 'float16' (NeuralNet training param; BASELINE configs[4]): activations and gradients live in HBM as
         # halfs in the c8 layout (device.C8Array), fp16 MFMA operands / fp32 accumulation, fp32 master weights.  Every
         # conv layer of the net runs that way or construction fails -- no silent fp32 run of an unsupported shape.
-        self.f16 = self.ctx.mm_dtype == "float16"
+        # DTYPE 'bfloat16': the same with bf16 in place of half.  f16: "16-bit resident", either of the two.
+        self.f16 = self.ctx.mm_dtype in C8_DTYPES
+        self.c8_dtype = self.ctx.mm_dtype if self.f16 else None
         self.inpt = inpt
         self.batch_sz, self.num_prev_maps, self.in_sz = batch_sz, num_prev_maps, in_sz
         self.filter_sz, self.stride = filter_sz, stride
@@ -61,12 +63,13 @@ class ConvLayer(Layer):
             ok = lib.tn_c8_conv_supported(batch_sz, num_prev_maps, in_sz, in_sz, num_maps, filter_sz, stride, self.pad_lo) and \
                 lib.tn_c8_conv_wgrad_supported(batch_sz, num_prev_maps, in_sz, in_sz, num_maps)
             assert ok and mode == 'same', (
-                "DTYPE float16 needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of 8, 16, 32 "
+                "DTYPE {} needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of 8, 16, 32 "
                 "or 64 pixels a side (got {}->{} maps, {}x{} {} filter {} stride {})".format(
-                    num_prev_maps, num_maps, in_sz, in_sz, mode, filter_sz, stride))
+                    self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, mode, filter_sz, stride))
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
-            self.x16 = None if getattr(inpt, "c8", None) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz)
-            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz)
+            self.x16 = None if getattr(inpt, "c8", None) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz,
+                                                                      self.c8_dtype)
+            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, self.c8_dtype)
             # the weights as MFMA operand tiles (forward / input gradient): the net arranges every layer's in one launch
             # per step (NeuralNet._c8_arrange) and marks them valid until the next update; otherwise the ops do it per call
             self.wt_fwd = self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16)
@@ -112,7 +115,7 @@ class ConvLayer(Layer):
         """conv -> act -> 2x2 max-pool on small channel counts runs as one fused kernel pair
         (tn_convpool_fwd / tn_convpool_bwd): the conv activation never reaches HBM."""
         if self.f16:
-            assert pool.pool_sz == 2 and self.out_sz % 2 == 0, "DTYPE float16: pooling layers are 2x2 on even maps"
+            assert pool.pool_sz == 2 and self.out_sz % 2 == 0, "DTYPE {}: pooling layers are 2x2 on even maps".format(self.c8_dtype)
             return True
         if self.stride == 1 and self.ctx.lib.tn_convpool_supported(
                 self.num_prev_maps, self.filter_sz, self.stride, pool.pool_sz):
@@ -176,9 +179,9 @@ class ConvLayer(Layer):
             self.ctx.call("tn_c8_conv_wgrad", x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *geom, pooled, mask)
         if not need_gin:
             return None
-        assert self.x16 is None, "DTYPE float16: no trainable layer below the first conv layer"
+        assert self.x16 is None, "DTYPE {}: no trainable layer below the first conv layer".format(self.c8_dtype)
         if self.gin is None:
-            self.gin = C8Array(self.ctx, self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz)
+            self.gin = C8Array(self.ctx, self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.c8_dtype)
         b_out, b_act, b_prm, b_mask = below.act_info()
         assert b_mask is None
         fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
@@ -302,7 +305,7 @@ class PoolLayer(Layer):
         self.batch_sz = inpt.shape[0]
         self.f16 = getattr(inpt, "c8", None) is not None      # DTYPE float16: pooled c8 tensor (only as a fused block)
         if self.f16:
-            self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz)
+            self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem)
         else:
             self.output = self.ctx.empty((self.batch_sz, num_maps, self.out_sz, self.out_sz))
         self.gin = None
@@ -330,7 +333,7 @@ class PoolLayer(Layer):
     def forward(self, train=True):
         conv = self.fused_conv
         if self.f16:
-            assert conv is not None, "DTYPE float16: a PoolLayer must directly follow a ConvLayer"
+            assert conv is not None, "DTYPE {}: a PoolLayer must directly follow a ConvLayer".format(self.output.elem)
             if train and self.mask is None:
                 self.mask = self.ctx.empty(self.output.shape, np.uint8)
             return conv._c8_forward(self.output, self.mask if train else None)

@@ -40,8 +40,8 @@ class HiddenLayer(Layer):
             c, h, wd = self.c8
             assert c * h * wd == n_in, (self.c8, n_in)
             assert self.ctx.lib.tn_c8_fc_supported(inpt.shape[0], c, h * wd, n_out), (
-                "DTYPE float16: a dense layer on {} maps of {}x{} needs a multiple of 64 inputs (c8) and of 32 outputs "
-                "(got {})".format(c, h, wd, n_out))
+                "DTYPE {}: a dense layer on {} maps of {}x{} needs a multiple of 64 inputs (c8) and of 32 outputs "
+                "(got {})".format(inpt.elem, c, h, wd, n_out))
             self.inpt = inpt
         else:
             self.inpt = inpt.flatten(2)
@@ -121,7 +121,7 @@ class HiddenLayer(Layer):
             if not need_gin:
                 return None
             if self.gin is None:
-                self.gin = C8Array(self.ctx, self.batch_sz, c, h, wd)
+                self.gin = C8Array(self.ctx, self.batch_sz, c, h, wd, self.inpt.elem)
             b_out, b_act, b_prm, b_mask = below.act_info()
             assert b_mask is None
             fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR

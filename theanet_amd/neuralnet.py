@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib, comm, layer
 from .plan import StepPlan
-from .device import DeviceArray, get_context, share
+from .device import C8_DTYPES, DeviceArray, get_context, share
 from .layer import (AuxConcatLayer, SoftAuxLayer, CenteredOutLayer, ColorLayer, ConvLayer, DropOutLayer, ElasticLayer, ExpLossLayer, HiddenLayer,
                     HingeLayer, InputLayer, InputSlot, MeanLayer, OutputLayer, PoolLayer, SoftmaxLayer)
 
@@ -111,12 +111,13 @@ class NeuralNet():
         # the SoftmaxLayer's training step as one kernel (tn_fc_softmax_train) or as its three ops: a choice of kernels
         # (results agree to rounding, not bit for bit), read once per net
         self._softmax_train = os.environ.get("TN_SOFTMAX_TRAIN", "1") != "0"
-        # DTYPE: 'float32' (default = the reference's floatX, weights.py:8) or 'float16' = fp16 operands /
-        # fp32 accumulation for the conv products, fp32 master weights; GRAD_SCALE: power of two applied
-        # to dz before it is rounded to fp16 (results are scaled back: exact)
+        # DTYPE: 'float32' (default = the reference's floatX, weights.py:8), 'float16' = fp16 operands /
+        # fp32 accumulation for the conv products, fp32 master weights, or 'bfloat16' = the same with bf16 (fp32's
+        # exponent range); GRAD_SCALE: power of two applied to dz before it is rounded to the 16-bit type (results are
+        # scaled back: exact), default 4096 for float16 and 1 for bfloat16 (which needs none)
         self.dtype = training_params.get('DTYPE', 'float32')
-        assert self.dtype in ('float32', 'float16'), "DTYPE must be 'float32' or 'float16'"
-        self.grad_scale = float(training_params.get('GRAD_SCALE', 4096.))
+        assert self.dtype in ('float32', 'float16', 'bfloat16'), "DTYPE must be 'float32', 'float16' or 'bfloat16'"
+        self.grad_scale = float(training_params.get('GRAD_SCALE', 1. if self.dtype == 'bfloat16' else 4096.))
         # MATMUL: 'float32' (default: exact fp32 MFMA) or 'bf16x3' -- the dense layers' products as six bf16 MFMA
         # products of exactly split operands (fp32-grade accuracy, not the same bits; gemm_b3.hip)
         self.matmul = training_params.get('MATMUL', 'float32')
@@ -215,9 +216,11 @@ class NeuralNet():
             num_prev_maps = use_tr_layer.num_maps
             prev_out_sz = use_tr_layer.out_sz
             if getattr(tr_inpt, "c8", None) is not None:
-                # DTYPE float16: fp16-resident tensors of the conv stack (device.C8Array) pass from layer to layer as they are
+                # DTYPE float16 / bfloat16: 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to
+                # layer as they are
                 assert curr_layer_type in (ConvLayer, PoolLayer), \
-                    "DTYPE float16: only Conv / Pool layers take the conv stack's fp16-resident tensors (got {})".format(layer_type)
+                    "DTYPE {}: only Conv / Pool layers take the conv stack's 16-bit-resident tensors (got {})".format(
+                        self.dtype, layer_type)
             elif tr_inpt.ndim != 4:
                 tr_inpt = tr_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
                 te_inpt = te_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
@@ -273,7 +276,7 @@ class NeuralNet():
 
         elif curr_layer_type in (AuxConcatLayer, HiddenLayer, SoftmaxLayer, SoftAuxLayer, HingeLayer, ExpLossLayer):
             assert getattr(tr_inpt, "c8", None) is None, \
-                "DTYPE float16: a HiddenLayer must follow the conv stack (got {})".format(layer_type)
+                "DTYPE {}: a HiddenLayer must follow the conv stack (got {})".format(self.dtype, layer_type)
             te_inpt = te_inpt.flatten(2)
             curr_layer = curr_layer_type(tr_inpt.flatten(2),
                                          wts,
@@ -299,7 +302,7 @@ class NeuralNet():
                 conv.fused_pool, pool.fused_conv = pool, conv
         for lyr in lyrs:
             assert not (isinstance(lyr, PoolLayer) and lyr.f16 and lyr.fused_conv is None), \
-                "DTYPE float16: a PoolLayer must directly follow a ConvLayer"
+                "DTYPE {}: a PoolLayer must directly follow a ConvLayer".format(lyr.output.elem)
         # DTYPE float16: the first conv layer packs its c8 input straight from the dataset window
         if len(lyrs) >= 2 and isinstance(lyrs[0], InputLayer) and isinstance(lyrs[1], ConvLayer) and lyrs[1].f16:
             lyrs[1]._pack_from, lyrs[0]._packed_by_conv = lyrs[0].inpt, True
@@ -577,7 +580,7 @@ class NeuralNet():
             self._dp_tune_tick()
         if self._dp_can_delay:
             self._dp_bind(self._dp_cur if self._dp_delayed else 0)
-        if self.dtype == 'float16':
+        if self.dtype in C8_DTYPES:
             self._c8_arrange(self.tr_layers, True)
         for lyr in self.tr_layers[:-1]:
             lyr.forward(True)
@@ -699,7 +702,7 @@ class NeuralNet():
                 self._group().allreduce_sum_async(self.flat_grads, n, getattr(self, "_ar_done_ev", None))
             if ahead:
                 first._cur, first._pre_valid = nxt, True
-            if self.dtype == 'float16':
+            if self.dtype in C8_DTYPES:
                 self._c8_stale()
             return
         delayed = self._dp_delayed
@@ -761,7 +764,7 @@ class NeuralNet():
             first._cur, first._pre_valid = nxt, True
         if not mn_done:
             self._apply_maxnorm_all()
-        if self.dtype == 'float16':
+        if self.dtype in C8_DTYPES:
             self._c8_stale()
 
     def _update_and_maxnorm(self, *args):
@@ -945,13 +948,14 @@ class NeuralNet():
         for index in get_output_of_layers:          # a requested conv map must be materialised
             lyr = self.te_layers[index]
             if isinstance(lyr, ConvLayer) and lyr.fused_pool is not None:
-                assert not lyr.f16, "DTYPE float16: the conv map of a fused conv + pool block is never materialised"
+                assert not lyr.f16, "DTYPE {}: the conv map of a fused conv + pool block is never materialised".format(
+                    lyr.c8_dtype)
                 lyr.fused_pool.fused_conv, lyr.fused_pool = None, None
 
         def fn(x, aux=None):
             self._sync_weights()
             self._apply_dtype()
-            if self.dtype == 'float16':
+            if self.dtype in C8_DTYPES:
                 self._c8_arrange(self.te_layers, False)
             x = np.ascontiguousarray(x, np.float32).reshape(stage.shape)
             stage.set_value(x)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Per-layer timings of the fp16-resident ("c8") conv kernels at the wide6 / cifar_like layer shapes.
 
-    python tools/bench_c8.py [--iters N] [--n 128] [--only conv2]
+    python tools/bench_c8.py [--iters N] [--n 128] [--only conv2] [--dtype f16|bf16]
 
 us/launch, TFLOP/s and the fraction of the HBM roof (algorithmic bytes of the op on fp16 tensors / 6.3 TB/s) for
-forward, pooled forward, input gradient (plain and gathered from a pooled gradient) and both weight gradients."""
+forward, pooled forward, input gradient (plain and gathered from a pooled gradient) and both weight gradients.
+--dtype bf16: the same kernels on bf16 cells (DTYPE 'bfloat16', tn_set_matmul_dtype mode 2, grad scale 1)."""
 import argparse
 import ctypes
 import os
@@ -14,12 +15,13 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from theanet_amd import _lib  # noqa: E402
-from theanet_amd.device import get_context  # noqa: E402
+from theanet_amd.device import bf16_bits, get_context  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--n", type=int, default=128)
 ap.add_argument("--only", default="")
+ap.add_argument("--dtype", choices=("f16", "bf16"), default="f16")
 args = ap.parse_args()
 ctx = get_context()
 lib = ctx.lib
@@ -43,7 +45,8 @@ def timeit(fn, iters):
 
 
 def rnd16(shape, scale=1.0):
-    return ctx.array((rng.standard_normal(shape) * scale).astype(np.float16).view(np.uint16))
+    v = (rng.standard_normal(shape) * scale).astype(np.float32)
+    return ctx.array(bf16_bits(v) if args.dtype == "bf16" else v.astype(np.float16).view(np.uint16))
 
 
 SHAPES = [  # name, N-scale, C, H, K
@@ -52,7 +55,8 @@ SHAPES = [  # name, N-scale, C, H, K
     ("cifar conv1", 16, 3, 32, 32), ("cifar conv2", 16, 32, 16, 64), ("cifar conv3", 16, 64, 8, 128),
 ]
 LEAKY = _lib.TN_ACT_LEAKY
-ctx.call("tn_set_matmul_dtype", 1, 4096.0)
+ctx.call("tn_set_matmul_dtype", *((2, 1.0) if args.dtype == "bf16" else (1, 4096.0)))
+print("dtype %s" % args.dtype)
 print("%-12s %-22s %8s %8s %8s" % ("layer", "op", "us", "TFLOP/s", "HBM frac"))
 for name, ns, C, H, K in SHAPES:
     if args.only and args.only not in name:
