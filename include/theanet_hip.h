@@ -80,7 +80,7 @@ int tn_d2h_early(tn_ctx* ctx, void* host_dst, const void* src, size_t bytes);
 int tn_copy_sync(tn_ctx* ctx);
 /* the same copy with an event (tn_event_create) recorded behind it on the copy stream: the host waits for THAT copy
  * (tn_event_sync) instead of for all of them -- a step's cost picked up a few steps later by train.py's loop
- * (theanet_amd/trainfn.py _CostRing; polling the destination instead is not an option: a 4-byte copy was observed
+ * (theanet_amd/trainfn.py _CostLedger; polling the destination instead is not an option: a 4-byte copy was observed
  * half-written from the host) */
 int tn_d2h_early_ev(tn_ctx* ctx, void* host_dst, const void* src, size_t bytes, void* done_event);
 int tn_d2d(tn_ctx* ctx, void* dst, const void* src, size_t bytes);   /* enqueued                */

@@ -533,11 +533,17 @@ def test_step_cost_hands_out_every_cost_in_order(pipeline, monkeypatch):
 
 
 @pytest.mark.parametrize("pipeline", ["1", "0"])
-def test_step_cost_loop_keeps_its_costs_across_plain_enqueues(pipeline, monkeypatch):
-    """A plain enqueue() / fn(i) in the MIDDLE of a step_cost() loop (the docstring says "do not", a caller may): the
-    costs the loop is still owed at that point (up to `lag` of them; two steps in flight: four) are collected then and
-    handed out by the next step_cost() / drain_costs() -- not dropped, a NaN among them would slip past the guard of
-    train.py:225.  Every step_cost() step's cost arrives once, in order, equal to fn(i)'s."""
+@pytest.mark.parametrize("pattern", [pytest.param("c" * 9 + "e" * 3 + "c" * 7 + "f" + "c" * 6 + "e" * 9 + "c" * 5,
+                                                  id="mid_loop"),
+                                     "ccccDeccccc", "ccccDeeccccc", "ccccDfccccc", "ccccDeeeccccc",
+                                     "cccccceiccceccDcc", "ccccDeiccc"])
+def test_step_cost_loop_keeps_its_costs_across_plain_enqueues(pipeline, pattern, monkeypatch):
+    """Plain enqueue() / fn(i) calls in the MIDDLE of a step_cost() loop or right after a drain (the docstring says
+    "do not", a caller may): their costs are nobody's, and the costs the loop is still owed are handed out by the next
+    step_cost() / drain_costs() -- not dropped, a NaN among them would slip past the guard of train.py:225.  Between
+    two drains every step_cost() step's cost arrives once, in order, under keys 0..n-1, equal to fn(i)'s.  Letters:
+    c = step_cost, e = enqueue, f = fn(i), i = step_cost with injected draws (falls back to one step at a time),
+    D = drain_costs; the run ends with a drain."""
     from theanet_amd import NeuralNet
     monkeypatch.setenv("TN_PIPELINE", pipeline)
     prms = load_prms("mnist.prms", 28, batch=16)
@@ -548,11 +554,27 @@ def test_step_cost_loop_keeps_its_costs_across_plain_enqueues(pipeline, monkeypa
     ref_fn = ref_net.get_trin_model(x, y)
     net = NeuralNet(copy.deepcopy(prms["layers"]), dict(prms["training_params"]))
     fn = net.get_trin_model(x, y)
-    plan = ["c"] * 9 + ["e"] * 3 + ["c"] * 7 + ["f"] + ["c"] * 6 + ["e"] * 9 + ["c"] * 5
+    inj = dict(transln=[.5, -.25], noise=np.zeros((2, 28, 28), np.float32), origin_u=[.5, .5], zoom_u=[0, 0], theta_u=0.1)
+
+    def check(want, got):
+        assert sorted(got) == list(range(len(want))), sorted(got)
+        np.testing.assert_array_equal(np.array([got[k] for k in range(len(want))], np.float32),
+                                      np.array(want, np.float32))
+
     want, got = [], {}
-    for s, kind in enumerate(plan):
+    for s, kind in enumerate(pattern + "D"):
+        if kind == "D":
+            for k, v in fn.drain_costs():
+                assert k not in got
+                got[k] = v
+            check(want, got)
+            want, got = [], {}
+            continue
+        if kind == "i":
+            for n_ in (ref_net, net):
+                n_.tr_layers[0].inject(**inj)
         c = ref_fn(s % 6)[0]
-        if kind == "c":
+        if kind in "ci":
             want.append(c)
             for k, v in fn.step_cost(s % 6):
                 assert k not in got
@@ -561,11 +583,9 @@ def test_step_cost_loop_keeps_its_costs_across_plain_enqueues(pipeline, monkeypa
             fn.enqueue(s % 6)
         else:
             assert fn(s % 6)[0] == c
-    for k, v in fn.drain_costs():
-        assert k not in got
-        got[k] = v
-    assert sorted(got) == list(range(len(want))), sorted(got)
-    np.testing.assert_array_equal(np.array([got[k] for k in range(len(want))], np.float32), np.array(want, np.float32))
+        if kind == "i":
+            for n_ in (ref_net, net):
+                n_.tr_layers[0].inject()
 
 
 def test_take_index_list_mode():

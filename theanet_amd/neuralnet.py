@@ -779,7 +779,7 @@ class NeuralNet():
 
     def _guard_cost(self):
         """In front of a launch that writes ``d_cost``: a step_cost() loop may still owe the host the previous value (a
-        4-byte copy on the copy stream, _CostRing.send) -- the stream waits for that copy's event."""
+        4-byte copy on the copy stream, _CostLedger.issue) -- the stream waits for that copy's event."""
         ev = getattr(self, "_cost_guard_ev", None)
         if ev is not None:
             self.ctx.call("tn_event_wait", ev)

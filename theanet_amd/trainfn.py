@@ -39,52 +39,95 @@ def _step_outputs(net, out):
     return [cost] + _features_logprob(out)
 
 
-class _CostRing:
+class _CostLedger:
     """The costs of enqueued steps, read a few steps LATER so that the loop of train.py (train.py:207-226: it sums the
     cost of every step and raises on NaN) never waits for the GPU: a step's cost (4 bytes) leaves for one of four
     page-locked slots as soon as it exists (tn_d2h_early_ev: copy stream, behind the launch that sums it, an event
     behind the copy) and the host picks it up ``lag`` calls later -- by then it has long arrived; if not, the host
-    waits for that slot's event only."""
+    waits for that slot's event only.
+
+    Which costs belong to a step_cost() loop is recorded when a step is issued: the slot of step t (t % R) holds the
+    number k of the step_cost() call that issued it, or None (enqueue(), fn(i): nobody's).  The costs handed out are
+    the owned ones, in order, with their k; k counts the step_cost() calls since the last drain_costs().  ONE ledger
+    per training function: the one-step-at-a-time fallback of a pipelined function shares it and its numbering."""
     R = 4
 
-    def __init__(self, ctx, lag):
-        import ctypes
-        from .device import HostBuffer
-        self.ctx, self.lag = ctx, lag
-        self.buf = HostBuffer(ctx, (self.R,), np.float32)
-        self.ev = []
-        for _ in range(self.R):
-            e = ctypes.c_void_p()
-            ctx.call("tn_event_create", ctypes.byref(e))
-            self.ev.append(e)
-        self.next_take = 0          # first step number whose cost the caller has not been handed yet
-        self.sent_upto = 0          # copies have been issued for the steps below
-        self.strict = False         # True while a step_cost() call is enqueueing
-        self.stale = False          # steps were enqueued outside step_cost() since the last one
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.k = 0                  # step_cost() calls since the last drain_costs()
+        self.cur = None             # the k of the step being issued (None: not a step_cost() call's)
+        self.owed = []              # owned costs taken off the ring early, handed out first
+        self.live = False           # the ring is on (a step_cost() loop has started)
+        self.buf, self.ev = None, []
 
-    def send(self, step, d_cost, net=None):
-        """The copy is ordered behind the launch that summed the cost, on the copy stream; nothing else holds the
-        compute stream back, so the NEXT launch that writes ``d_cost`` must wait for the slot's event first:
-        ``net._guard_cost()`` (NeuralNet) does, in front of every such launch -- a step or two later in the lazy
-        schedules (the copy has long run), a few tens of microseconds later where the cost is summed mid-step
-        (data-parallel pipelined steps, weight-cost nets)."""
-        assert step == self.sent_upto, "cost ring out of step"
-        if step - self.next_take >= self.R:
-            # nobody is collecting: plain enqueue() calls while the ring is kept for the next step_cost() loop (drain_costs
-            # leaves it in place) -- the oldest cost is dropped; inside a step_cost() loop this would be a bug
-            assert not self.strict, "cost ring overrun"
-            self.next_take = step - self.R + 1
-        s = step % self.R
-        self.ctx.call("tn_d2h_early_ev", self.buf.ptr + 4 * s, d_cost.ptr, 4, self.ev[s])
-        if net is not None:
-            net._cost_guard_ev = self.ev[s]
-        self.sent_upto = step + 1
+    def open(self, t, lag):
+        """Ring on from step t (the steps before it are nobody's)."""
+        if self.buf is None:
+            import ctypes
+            from .device import HostBuffer
+            self.buf = HostBuffer(self.ctx, (self.R,), np.float32)
+            for _ in range(self.R):
+                e = ctypes.c_void_p()
+                self.ctx.call("tn_event_create", ctypes.byref(e))
+                self.ev.append(e)
+        self.live, self.lag = True, lag
+        self.own = [None] * self.R
+        self.next = self.sent = t   # steps below `next` are handed out or nobody's; copies are issued below `sent`
 
-    def take(self, step):
-        s = step % self.R
-        self.ctx.lib.tn_event_sync(self.ctx.h, self.ev[s])
-        self.next_take = step + 1
-        return np.float32(self.buf.array[s])
+    def issue(self, t, s, d_cost, net):
+        """Step t is issued (its owner: ``cur``) and the cost of step s (t itself, or t - 2 with two steps in flight)
+        has been summed into ``d_cost``: off it goes to slot s % R -- unless it is not the ring's to send (s below
+        ``sent``: summed before the ring was on, or read directly by ``rest``).  ``d_cost`` None: a replayed step,
+        whose C call has issued the copy already.  The copy is ordered behind the launch that summed the cost, on the
+        copy stream; nothing else holds the compute stream back, so the NEXT launch that writes ``d_cost`` must wait
+        for the slot's event first: ``net._guard_cost()`` (NeuralNet) does, in front of every such launch -- a step or
+        two later in the lazy schedules (the copy has long run), a few tens of microseconds later where the cost is
+        summed mid-step (data-parallel pipelined steps, weight-cost nets)."""
+        old = t - self.R
+        if old >= self.next:
+            # slot t % R passes from step t - R to step t: an owned cost nobody has taken yet (plain enqueue() calls
+            # behind a step_cost() loop) is taken now; inside a loop the lag has handed it out already
+            if self.own[t % self.R] is not None:
+                assert self.cur is None, "cost ring overrun"
+                self.owed.append((self.own[t % self.R], self._take(old)))
+            self.next = old + 1
+        self.own[t % self.R] = self.cur
+        if s >= self.sent:
+            assert s == self.sent, "cost ring out of step"
+            if d_cost is not None:
+                self.ctx.call("tn_d2h_early_ev", self.buf.ptr + 4 * (s % self.R), d_cost.ptr, 4, self.ev[s % self.R])
+            net._cost_guard_ev = self.ev[s % self.R]
+            self.sent = s + 1
+
+    def step(self, t, enqueue, i):
+        """One step_cost() call: the owned costs that have become due (t steps issued so far), then step i."""
+        out, self.owed = self.owed, []
+        while self.next <= t - self.lag:
+            if self.own[self.next % self.R] is not None:
+                out.append((self.own[self.next % self.R], self._take(self.next)))
+            self.next += 1
+        self.cur = self.k
+        try:
+            enqueue(i)
+        finally:
+            self.cur = None
+        self.k += 1
+        return out
+
+    def rest(self, t, read=None):
+        """Everything still owed, in order (t steps issued so far): the costs taken early, the copies under way, then
+        ``read(s)`` for the steps whose cost nobody has sent.  What follows starts from step t."""
+        out, self.owed = self.owed, []
+        if self.live:
+            for s in range(self.next, t):
+                if self.own[s % self.R] is not None:
+                    out.append((self.own[s % self.R], self._take(s) if s < self.sent else read(s)))
+            self.next = self.sent = t
+        return out
+
+    def _take(self, s):
+        self.ctx.lib.tn_event_sync(self.ctx.h, self.ev[s % self.R])
+        return np.float32(self.buf.array[s % self.R])
 
     def __del__(self):
         try:
@@ -107,7 +150,7 @@ class _TrainFn:
     (neuralnet.py:236-241).  ``enqueue(i)`` issues the step without reading anything
     back (the GPU runs ahead of the host); ``fetch()`` copies the last step's outputs."""
 
-    def __init__(self, net, x_data, y_data, take_index_list, aux_data=None):
+    def __init__(self, net, x_data, y_data, take_index_list, aux_data=None, ledger=None):
         self.net, self.x_data, self.y_data = net, x_data, y_data
         self.aux_data = aux_data
         self.take_index_list = take_index_list
@@ -122,14 +165,14 @@ class _TrainFn:
                 self.aux_stage = ctx.empty((net.local_bsz,) + tuple(aux_data.shape[1:]))
         # the step as one C call once its calls have been seen to repeat (plan.py); index-list batches upload per step
         self._plan = None if take_index_list else StepPlan(ctx, net.batch_sz, net.shard_lo)
-        self._ring, self._n = None, 0          # step_cost(): costs read two calls late; steps enqueued so far
-        self._sc_n, self._owed = 0, []
+        self._n = 0                            # steps enqueued so far
+        self._led = ledger or _CostLedger(ctx)  # step_cost(): costs read two calls late
 
     def _plan_state(self):
         net = self.net
         first = net.tr_layers[0]
         return (getattr(first, "_cur", None), getattr(first, "_pre_valid", None), getattr(net, "_cost_pending", None),
-                net._dp_cur, net._dp_pending, (self._n & 3) if self._ring is not None else -1)
+                net._dp_cur, net._dp_pending, (self._n & 3) if self._led.live else -1)
 
     def _plan_set_state(self, st):
         net = self.net
@@ -139,13 +182,8 @@ class _TrainFn:
         if st[2] is not None:
             net._cost_pending = st[2]
         net._dp_cur, net._dp_pending = st[3], st[4]
-        if self._ring is not None:                # (the replayed step has sent its cost like an interpreted one)
-            r = self._ring
-            r.sent_upto = self._n + 1
-            if not r.strict:
-                r.stale = True
-                r.next_take = max(r.next_take, self._n + 1 - r.R)      # (as send(): the last R steps stay)
-            net._cost_guard_ev = r.ev[self._n % r.R]
+        if self._led.live:                        # (the replayed step has sent its cost like an interpreted one)
+            self._led.issue(self._n, self._n, None, net)
         self._n += 1
 
     def _plannable(self):
@@ -161,13 +199,6 @@ class _TrainFn:
                                  % (self.net.batch_sz, self.x_data.shape[0]))
         else:
             _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
-        r = self._ring
-        if r is not None and not r.strict and self._n == getattr(self, "_sc_hi", -1) and r.next_take < self._n:
-            # a plain enqueue() / fn(i) in the middle of a step_cost() loop: the costs that loop is still owed are
-            # collected NOW (the ring only keeps the last R steps) and handed out by the next step_cost() / drain_costs()
-            # -- dropped, a NaN among them would slip past train.py's guard (train.py:225)
-            self._owed += self._ring_rest(keep=True)
-            r.stale = True                        # (the next step_cost() call starts its numbering behind the plain steps)
         pl = self._plan
         if pl is not None and not pl.off:
             ok = self._plannable()
@@ -219,60 +250,32 @@ class _TrainFn:
         if self.aux_data is not None:
             net.aux_inpt_tr.row_global0 = int(i) * B + lo if not self.take_index_list else lo
         net._train_step(y, y_row0)
-        if self._ring is not None:                # the step's cost exists behind its last launch: off it goes
-            self._ring.send(self._n, net.d_cost, net)
-            if not self._ring.strict:
-                self._ring.stale = True
+        if self._led.live:                        # the step's cost exists behind its last launch: off it goes
+            self._led.issue(self._n, self._n, net.d_cost, net)
         self._n += 1
 
-    # -- costs a few calls late (what train.py's loop needs of a step; see _CostRing) ----------------------------
+    # -- costs a few calls late (what train.py's loop needs of a step; see _CostLedger) --------------------------
     def step_cost(self, i):
         """Enqueue step i; return [(step number, cost), ...] of the steps whose cost has become due (step numbers count
         the step_cost calls since the last drain_costs()).  Do not mix with enqueue() / fn(i) before drain_costs()."""
-        net = self.net
-        pre, self._owed = self._owed, []
+        net, led = self.net, self._led
         if net._dp_delayed or net._dp_tune is not None or self.take_index_list or net._injecting():
-            out = pre + self._ring_rest()             # (the cost travels on the second stream / per-step host work)
-            out.append((self._sc_n, np.float32(self(i)[0])))
-            self._sc_n += 1
+            out = self._ring_rest()               # (the cost travels on the second stream / per-step host work)
+            out.append((led.k, np.float32(self(i)[0])))
+            led.k += 1
             return out
-        if self._ring is None:
-            self._ring = _CostRing(net.ctx, 2)
-            self._ring.sent_upto = self._ring.next_take = self._n
-            self._ring_base = self._n - self._sc_n
-            if self._plan is not None:
-                self._plan.restart("cost ring on")
-        r, out = self._ring, pre
-        if r.stale:                               # plain enqueue() calls in between: their costs are nobody's
-            r.next_take = r.sent_upto = self._n   # (what step_cost() calls before them were owed is in `pre`)
-            self._ring_base = self._n - self._sc_n
-            r.stale = False
-        if self._n - r.next_take >= r.lag:
-            out.append((r.next_take - self._ring_base, r.take(r.next_take)))
-        r.strict = True
-        try:
-            self.enqueue(i)
-        finally:
-            r.strict = False
-        self._sc_n += 1
-        self._sc_hi = self._n                     # (a plain enqueue() right behind this step finds the loop's costs owed)
-        return out
+        if not led.live:
+            led.open(self._n, 2)
+            self._plan.restart("cost ring on")
+        return led.step(self._n, self.enqueue, i)
 
     def _ring_rest(self, keep=False):
-        """Everything the ring still owes, in order.  ``keep``: the ring (and with it the recorded steps, whose baked
+        """Everything the ledger still owes, in order.  ``keep``: the ring (and with it the recorded steps, whose baked
         slot and event pointers follow the step number modulo 4) stays for the next loop."""
-        r, out = self._ring, []
-        if r is None:
-            return out
-        if r.stale:                               # only plain enqueue() calls since the last loop: nothing is owed
-            r.next_take = r.sent_upto
-            r.stale = False
-        while r.next_take < r.sent_upto:
-            out.append((r.next_take - self._ring_base, r.take(r.next_take)))
-        if keep:
-            return out
-        self._ring = None
-        if self._plan is not None:
+        led = self._led
+        out = led.rest(self._n)
+        if led.live and not keep:
+            led.live = False
             self._plan.restart("cost ring off")
         return out
 
@@ -280,11 +283,8 @@ class _TrainFn:
         """The costs step_cost() has not handed out yet, in order; afterwards step numbers start from 0 again.  train.py
         calls this at the end of every epoch: ring and plan survive it (an epoch of mnist.prms at batch 4096 is 12
         steps -- fewer than it takes to watch and record a step)."""
-        out, self._owed = self._owed, []
-        out += self._ring_rest(keep=True)
-        self._sc_n = 0
-        if self._ring is not None:
-            self._ring_base = self._n
+        out = self._ring_rest(keep=True)
+        self._led.k = 0
         return out
 
     def fetch(self):
@@ -330,8 +330,7 @@ class _PipeTrainFn:
         net._pipe_fn = self
         self._ctypes = ctypes
         self._plan = StepPlan(net.ctx, net.batch_sz, net.shard_lo)
-        self._ring = None            # step_cost(): costs read four calls late (_CostRing)
-        self._sc_n, self._owed = 0, []
+        self._led = _CostLedger(net.ctx)     # step_cost(): costs read four calls late
 
     # -- set-up of the twin on first use ---------------------------------------------------------
     def _build(self):
@@ -415,7 +414,7 @@ class _PipeTrainFn:
         for X in self.nets:
             first = X.tr_layers[0]
             per_net.append((X._cost_pending, getattr(first, "_cur", None), getattr(first, "_pre_valid", None)))
-        return (self.nets.index(self._last), tuple(per_net), (self.t & 3) if self._ring is not None else (self.t & 1))
+        return (self.nets.index(self._last), tuple(per_net), (self.t & 3) if self._led.live else (self.t & 1))
 
     def _plan_set_state(self, st):
         self._last = self.nets[st[0]]
@@ -425,13 +424,8 @@ class _PipeTrainFn:
                 first = X.tr_layers[0]
                 first._cur, first._pre_valid = cur, pv
         self._updated = False
-        r = self._ring
-        if r is not None and self.t - 2 >= r.sent_upto:
-            r.sent_upto = self.t - 1              # (the replayed step has sent the cost of step t - 2)
-            if not r.strict:
-                r.stale = True
-                r.next_take = max(r.next_take, self.t - 1 - r.R)       # (as send(): the last R sent steps stay)
-            self.nets[self.t & 1]._cost_guard_ev = r.ev[(self.t - 2) % r.R]
+        if self._led.live:                        # (the replayed step has sent the cost of step t - 2)
+            self._led.issue(self.t, self.t - 2, None, self.nets[self.t & 1])
         self.t += 1
 
     def _plannable(self):
@@ -496,8 +490,8 @@ class _PipeTrainFn:
     def _fall_back(self):
         """Leave the pipelined schedule for good: bring weights AND velocity to the sequential state."""
         net, ctx = self.net, self.net.ctx
-        if self._ring is not None:                # costs still owed to a step_cost() loop: collect them first
-            self._owed = self._owed + self._leave_ring()
+        if self._led.live:                        # costs still owed to a step_cost() loop: collect them first
+            self._led.owed = self._leave_ring()
         self._flush_parked()
         if self._twin is not None and self.t > 0:
             self.sync_weights()
@@ -515,17 +509,11 @@ class _PipeTrainFn:
         first = net.tr_layers[0]
         if isinstance(first, ElasticLayer):
             first._pre_valid = False              # a field built ahead was for this stream's step t+2
-        self._seq = _TrainFn(net, self.x_data, self.y_data, False)
+        self._seq = _TrainFn(net, self.x_data, self.y_data, False, ledger=self._led)
 
     # -- the step ---------------------------------------------------------------------------------
     def enqueue(self, i):
         _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
-        r = self._ring
-        if r is not None and self._seq is None and not r.strict and self.t == getattr(self, "_sc_hi", -1) and r.next_take < self.t:
-            # a plain enqueue() / fn(i) in the middle of a step_cost() loop: what that loop is still owed is collected now
-            # (as at the end of an epoch) instead of being dropped -- see _TrainFn.enqueue
-            self._owed = self._owed + self._leave_ring(keep=True)
-            r.stale = True                        # (the next step_cost() call starts its numbering behind the plain steps)
         pl = self._plan
         if pl is None or pl.off:
             return self._enqueue(i)
@@ -567,14 +555,10 @@ class _PipeTrainFn:
             ctx.call("tn_event_record", self._ev[0])
         else:
             ctx.call("tn_stream_select", k)
-        r = self._ring
-        if r is not None and t >= 2 and t - 2 >= r.sent_upto:
+        if self._led.live:
             # the update that opens step t has summed the cost of this stream's previous step (t - 2): off it goes
             # -- also when that update already ran because something read the weights in between (sync_weights)
-            r.sent_upto = t - 2
-            r.send(t - 2, X.d_cost, X)
-            if not r.strict:
-                r.stale = True
+            self._led.issue(t, t - 2, X.d_cost, X)
         self._updated = False
         self._lr_prev = self._lr_now()
         slot = X.x
@@ -591,7 +575,7 @@ class _PipeTrainFn:
         self._last = X
         self.t = t + 1
 
-    # -- costs a few calls late (what train.py's loop needs of a step; see _CostRing) ----------------------------
+    # -- costs a few calls late (what train.py's loop needs of a step; see _CostLedger) --------------------------
     def step_cost(self, i):
         """Enqueue step i; return [(step number, cost), ...] of the steps whose cost has become due (step numbers count
         the step_cost calls since the last drain_costs()).  With two steps in flight the cost of step t is summed by
@@ -599,70 +583,35 @@ class _PipeTrainFn:
         drain_costs()."""
         if self._seq is None and self._blocked():
             self._fall_back()                     # (collects what the ring owes) one step at a time from here on
-        pre, self._owed = self._owed, []
         if self._seq is not None:
-            off = self._sc_n - getattr(self._seq, "_sc_n", 0)
-            return pre + [(k + off, c) for k, c in self._seq.step_cost(i)] + self._count()
-        if self._ring is None:
-            self._ring = _CostRing(self.net.ctx, 4)
-            self._ring.sent_upto = self._ring.next_take = self.t
-            self._ring_base = self.t - self._sc_n
+            return self._seq.step_cost(i)         # (the same ledger: the numbering goes on)
+        if not self._led.live:
+            self._led.open(self.t, 4)
             self._plan.restart("cost ring on")
-        r, out = self._ring, []
-        if r.stale:                               # plain enqueue() calls in between: their costs are nobody's
-            r.next_take = r.sent_upto = self.t
-            self._ring_base = self.t - self._sc_n
-            r.stale = False
-        if self.t - r.next_take >= r.lag:
-            out.append((r.next_take - self._ring_base, r.take(r.next_take)))
-        r.strict = True
-        try:
-            self.enqueue(i)
-        finally:
-            r.strict = False
-        self._count()
-        self._sc_hi = self.t                      # (a plain enqueue() right behind this step finds the loop's costs owed)
-        return pre + out
-
-    def _count(self):
-        self._sc_n += 1
-        return []
+        return self._led.step(self.t, self.enqueue, i)
 
     def _leave_ring(self, keep=False):
-        """Everything the ring still owes, in order: the copies already under way, then the last two steps' costs read
-        directly (nothing would ever open the steps that sum them).  ``keep`` (drain_costs at the end of an epoch): ring
-        and recorded steps stay -- the next steps go through the interpreter until both streams have a cost pending
-        again (two steps), then the recorded phases match and replay resumes."""
-        r, out = self._ring, []
-        if r is None:
-            return out
+        """Everything the ledger still owes, in order: the costs taken early, the copies already under way, then the
+        last two steps' costs read directly (nothing would ever open the steps that sum them).  ``keep`` (drain_costs
+        at the end of an epoch): ring and recorded steps stay -- the next steps go through the interpreter until both
+        streams have a cost pending again (two steps), then the recorded phases match and replay resumes."""
+        led = self._led
+        if not led.live:
+            return led.rest(self.t)
         assert self._seq is None
-        if r.stale:                               # only plain enqueue() calls since the last loop: nothing is owed
-            r.next_take = r.sent_upto = self.t
-            r.stale = False
-        if not keep:
-            self._ring = None
         self._flush_parked()
         self.net.ctx.sync()
-        while r.next_take < r.sent_upto:
-            out.append((r.next_take - self._ring_base, r.take(r.next_take)))
-        for t in range(r.next_take, self.t):
-            out.append((t - self._ring_base, np.float32(self.nets[t & 1].d_cost.get_value()[0])))
-        if keep:
-            r.next_take = r.sent_upto = self.t
-            self._ring_base = self.t
-        else:
+        out = led.rest(self.t, lambda s: np.float32(self.nets[s & 1].d_cost.get_value()[0]))
+        if not keep:
+            led.live = False
             self._plan.restart("cost ring off")
         return out
 
     def drain_costs(self):
-        out, self._owed = self._owed, []
-        if self._seq is None:
-            out += self._leave_ring(keep=True)
         if self._seq is not None:
-            off = self._sc_n - getattr(self._seq, "_sc_n", 0)
-            out += [(k + off, c) for k, c in self._seq.drain_costs()]
-        self._sc_n = 0
+            return self._seq.drain_costs()
+        out = self._leave_ring(keep=True)
+        self._led.k = 0
         return out
 
     def fetch(self):
