@@ -238,6 +238,15 @@ int tn_c8_elastic_apply(tn_ctx* ctx, const float* x, int64_t x_row0, const int64
                         const float* map_fy, const float* map_fx, float pflip, const uint8_t* flipmask,
                         uint64_t seed, uint32_t step, const uint32_t* d_step, int64_t row_global0);
 int tn_c8_unpack(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, float scale);
+/* MeanLayer on a c8 tensor (replaces tt.mean(inpt, axis=(2,3)) and its gradient, convpool.py:129-144, for a Mean layer
+ * on top of the 16-bit stack; theanet_amd/csrc/mean_c8.hip).  fwd: y (N, C) fp32 row-major = the fp32 mean over H x W of
+ * the STORED values of x (not rounded: the input of the fp32 dense layers above).  bwd: dx (c8, same shape as x) =
+ * R(grad_scale * dy[n, c] / (H W) * act'(b_out)), R = rounding to the context's 16-bit type, act' taken from b_out =
+ * the stored output of the block below (its pooled output for a pooled block; NULL: linear) as in tn_c8_fc_dgrad;
+ * channels past C are written as 0.  Any N, C, H, W >= 1 (bwd: fewer than 2^32 cells).  Deterministic: no atomics. */
+int tn_c8_mean_fwd(tn_ctx* ctx, const void* x, float* y, int N, int C, int H, int W);
+int tn_c8_mean_bwd(tn_ctx* ctx, const float* dy, void* dx, int N, int C, int H, int W, const void* b_out, int b_act,
+                   float b_prm);
 
 /* 1 if tn_conv2d_* run this shape on the implicit-im2col fp32-MFMA kernels (stride 1, reduction
  * C*f*f >= 32, >= 16 output maps); otherwise the direct VALU kernels are used.              */

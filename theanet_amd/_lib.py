@@ -98,6 +98,8 @@ SIGNATURES = {
     "tn_c8_fc_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 4),
     "tn_c8_pack": (c_int, [CTX, P, c_int64, P, c_int, c_int, c_int, c_float]),
     "tn_c8_unpack": (c_int, [CTX, P, P, c_int, c_int, c_int, c_float]),
+    "tn_c8_mean_fwd": (c_int, [CTX, P, P] + [c_int] * 4),
+    "tn_c8_mean_bwd": (c_int, [CTX, P, P] + [c_int] * 4 + [P, c_int, c_float]),
     "tn_pool_fwd": (c_int, [CTX, P, P] + [c_int] * 6),
     "tn_pool_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 6 + [c_int, c_float]),
     "tn_mean_fwd": (c_int, [CTX, P, P, c_int, c_int]),

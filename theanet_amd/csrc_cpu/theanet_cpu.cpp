@@ -204,6 +204,8 @@ int tn_c8_elastic_apply(tn_ctx* ctx, const float*, int64_t, const int64_t*, void
     NOT_HERE("tn_c8_elastic_apply");
 }
 int tn_c8_unpack(tn_ctx* ctx, const void*, float*, int, int, int, float) { NOT_HERE("tn_c8_unpack"); }
+int tn_c8_mean_fwd(tn_ctx* ctx, const void*, float*, int, int, int, int) { NOT_HERE("tn_c8_mean_fwd"); }
+int tn_c8_mean_bwd(tn_ctx* ctx, const float*, void*, int, int, int, int, const void*, int, float) { NOT_HERE("tn_c8_mean_bwd"); }
 
 int tn_alloc(tn_ctx* ctx, size_t bytes, void** dptr) {
     void* p = nullptr;

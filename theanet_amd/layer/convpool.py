@@ -386,6 +386,9 @@ class MeanLayer(Layer):
         self.out_sz = 1
         self.n_out = num_maps
         self.batch_sz = inpt.shape[0]
+        # DTYPE float16 / bfloat16: the input is the 16-bit-resident c8 tensor of the conv stack (tn_c8_mean_*); the
+        # output stays the fp32 (N, C) matrix the dense layers above take
+        self.f16 = getattr(inpt, "c8", None) is not None
         self.output = self.ctx.empty((self.batch_sz, num_maps))
         self.gin = None
         self.representation = (
@@ -396,12 +399,30 @@ class MeanLayer(Layer):
         return MeanLayer(inpt, self.num_maps, self.in_sz)
 
     def forward(self, train=True):
+        if self.f16:
+            self.ctx.call("tn_c8_mean_fwd", self.inpt.ptr, self.output.ptr, self.batch_sz, self.num_maps,
+                          self.in_sz, self.in_sz)
+            return
         self.ctx.call("tn_mean_fwd", self.inpt.ptr, self.output.ptr,
                       self.batch_sz * self.num_maps, self.in_sz * self.in_sz)
+
+    def _c8_backward(self, gout, below):
+        """The c8 gradient of the block below (an unpooled ConvLayer, or a fused 2x2 PoolLayer standing for its block):
+        grad_scale * gout / (H W) * act'(its stored output), rounded when stored."""
+        if self.gin is None:
+            self.gin = C8Array(self.ctx, self.batch_sz, self.num_maps, self.in_sz, self.in_sz, self.inpt.elem)
+        b_out, b_act, b_prm, b_mask = below.act_info()
+        assert b_mask is None
+        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
+        self.ctx.call("tn_c8_mean_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps, self.in_sz, self.in_sz,
+                      b_out.ptr if fuse else None, b_act, b_prm)
+        return self.gin
 
     def backward(self, gout, need_gin, below):
         if not need_gin:
             return None
+        if self.f16:
+            return self._c8_backward(gout, below)
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
         b_out, b_act, b_prm, b_mask = below.act_info()

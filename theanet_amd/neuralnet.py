@@ -217,9 +217,9 @@ class NeuralNet():
             prev_out_sz = use_tr_layer.out_sz
             if getattr(tr_inpt, "c8", None) is not None:
                 # DTYPE float16 / bfloat16: 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to
-                # layer as they are
-                assert curr_layer_type in (ConvLayer, PoolLayer), \
-                    "DTYPE {}: only Conv / Pool layers take the conv stack's 16-bit-resident tensors (got {})".format(
+                # layer as they are; a MeanLayer closes the stack with an fp32 (N, C) output
+                assert curr_layer_type in (ConvLayer, PoolLayer, MeanLayer), \
+                    "DTYPE {}: only Conv / Pool / Mean layers take the conv stack's 16-bit-resident tensors (got {})".format(
                         self.dtype, layer_type)
             elif tr_inpt.ndim != 4:
                 tr_inpt = tr_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
