@@ -51,6 +51,9 @@ typedef struct tn_ctx tn_ctx;
 
 /* ---- lifecycle (replaces: theano device init; neuralnet.py:236 theano.function) ---- */
 int tn_version(void);
+/* "TN_<name>=<value>" of every environment switch (theanet_amd/csrc/knobs.h) that data-parallel ranks must agree on,
+ * as this process resolved it: space-separated, in table order, NUL-terminated.  TN_E_ARG if len is too small. */
+int tn_knobs(char* buf, int len);
 int tn_device_count(int* count);
 int tn_ctx_create(int device, tn_ctx** ctx);
 int tn_ctx_destroy(tn_ctx* ctx);

@@ -41,6 +41,87 @@ def test_cpu_backend_library_exports_the_same_abi():
     assert lib.tn_version() >= 100
 
 
+CSRC = os.path.join(ROOT, "theanet_amd", "csrc")
+# the library's switches that data-parallel ranks must agree on, with the defaults the code had before they became one
+# table (theanet_amd/csrc/knobs.h)
+KNOB_DEFAULTS = {
+    "TN_C8_WTR": 1, "TN_C8_ROLL": 1, "TN_C8_WSLAB_DIV": 2, "TN_C8_EXP": 0, "TN_FC8_XCD": 1, "TN_FC8_FWD_HALF": 0,
+    "TN_FC8_FIN": 1, "TN_FC8_WSLABS": 2, "TN_FC8_DZ16": 1, "TN_CONV_TILE": 1, "TN_CONV_TILE_WGRAD": 1,
+    "TN_CONV_TILE_POOL": 1, "TN_CONV_TILE_SMALLC": 1, "TN_CONVPOOL_KS": 0, "TN_CB_W44": 1, "TN_ELASTIC_CONV": 1,
+    "TN_FC_SKINNY": 1, "TN_GEMM_DEEP": 1, "TN_GEMM_DMA": 1, "TN_GEMM_DMA_PAD": 0, "TN_GEMM_DMA_NS": 0, "TN_FC_WSPLIT": 0,
+    "TN_FC_DGRAD_SPLIT": 0, "TN_SOFTMAX_TRAIN": 1, "TN_PAIR_DMA": 26, "TN_PAIR_LDS_PAD": -1,
+}
+KNOB_DEBUG = ("TN_C8_DBG", "TN_CB_DBG", "TN_CM_DBG", "TN_GEMM_DBG", "TN_CT_DBG")
+
+
+def knob_rows():
+    """(name, agreed) of every row of knobs.h, in table order."""
+    rows = re.findall(r"^\s*X\((\w+), -?\d+, \w+, ([01]),", open(os.path.join(CSRC, "knobs.h")).read(), re.M)
+    assert len(rows) > 30
+    return [("TN_" + n, a == "1") for n, a in rows]
+
+
+def tn_knobs(libs, **env):
+    """tn_knobs of each library in ``libs``, loaded in that order into one fresh process whose environment holds no
+    TN_* variable but ``env`` (each library resolves its switches once per process)."""
+    import subprocess
+    import sys
+    code = ("import ctypes, sys\n"
+            "for p in sys.argv[1:]:\n"
+            "    b = ctypes.create_string_buffer(4096)\n"
+            "    assert ctypes.CDLL(p, mode=ctypes.RTLD_GLOBAL).tn_knobs(b, len(b)) == 0\n"
+            "    print(b.value.decode())\n")
+    e = {k: v for k, v in os.environ.items() if not k.startswith("TN_")}
+    e.update(env)
+    r = subprocess.run([sys.executable, "-c", code] + list(libs), env=e, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return [{k: int(v) for k, v in (kv.split("=") for kv in line.split())} for line in r.stdout.splitlines()]
+
+
+def test_knobs_table_is_the_only_reader_of_the_environment():
+    """Every TN_* switch of the HIP library is one row of knobs.h: no other source calls getenv, every switch a source
+    reads is a row, and every row is read somewhere."""
+    rows = {n for n, _ in knob_rows()}
+    read = set()
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith((".hip", ".h")) and f != "knobs.h":
+            src = open(os.path.join(CSRC, f)).read()
+            assert "getenv(" not in src, f
+            read |= {"TN_" + n for n in re.findall(r"\btn_knob\(TN_K_(\w+)\)", src)}
+    assert read == rows, (sorted(read - rows), sorted(rows - read))
+
+
+def test_tn_knobs_resolves_the_defaults_and_parse_forms():
+    """tn_knobs of the CPU library (the same knobs.h): the agreed rows in table order with today's defaults, the edge
+    values of each parse form, debug rows never; a short buffer is refused."""
+    from theanet_amd import _lib
+    if not os.path.isfile(_lib.CPU_LIB_PATH):
+        pytest.skip("libtheanet_cpu.so not built")
+    agreed = [n for n, a in knob_rows() if a]
+    assert sorted(agreed) == sorted(KNOB_DEFAULTS) and not set(agreed) & set(KNOB_DEBUG)
+    got, = tn_knobs([_lib.CPU_LIB_PATH])
+    assert list(got) == agreed and got == KNOB_DEFAULTS
+    dbg = {n: "1" for n in KNOB_DEBUG}
+    edge, = tn_knobs([_lib.CPU_LIB_PATH], TN_C8_WSLAB_DIV="0", TN_CONV_TILE="0x", TN_CONV_TILE_POOL="", TN_C8_WTR="abc",
+                     TN_PAIR_DMA="31", **dbg)
+    assert edge == dict(KNOB_DEFAULTS, TN_C8_WSLAB_DIV=2, TN_CONV_TILE=0, TN_C8_WTR=0, TN_PAIR_DMA=31)
+    edge, = tn_knobs([_lib.CPU_LIB_PATH], TN_C8_WSLAB_DIV="3", TN_CONV_TILE="abc", TN_CONV_TILE_SMALLC="0",
+                     TN_SOFTMAX_TRAIN="00", TN_PAIR_LDS_PAD="8192")
+    assert edge == dict(KNOB_DEFAULTS, TN_C8_WSLAB_DIV=3, TN_SOFTMAX_TRAIN=0, TN_CONV_TILE_SMALLC=0, TN_PAIR_LDS_PAD=8192)
+    lib = _lib.bind(_lib.CPU_LIB_PATH, ctypes.RTLD_LOCAL)
+    assert lib.tn_knobs(ctypes.create_string_buffer(64), 64) == -2 and lib.tn_knobs(None, 0) == -2
+
+
+def test_both_libraries_resolve_the_same_knobs():
+    from theanet_amd import _lib
+    if not os.path.isfile(_lib.CPU_LIB_PATH):
+        pytest.skip("libtheanet_cpu.so not built")
+    hip = os.path.join(ROOT, "theanet_amd", "lib", "libtheanet_hip.so")
+    for env in ({}, {"TN_C8_WSLAB_DIV": "-1", "TN_FC8_WSLABS": "4", "TN_CONV_TILE_WGRAD": "0", "TN_GEMM_DMA": "2"}):
+        a, b = tn_knobs([hip, _lib.CPU_LIB_PATH], **env)
+        assert a == b and a["TN_FC8_WSLABS"] == int(env.get("TN_FC8_WSLABS", 2))
+
+
 def test_struct_layout_matches_header():
     import numpy as np
     seg = np.dtype([('p', 'u8'), ('v', 'u8'), ('g', 'u8'), ('n', 'u8'),

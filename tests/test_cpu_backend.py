@@ -134,6 +134,41 @@ def test_product_data_parallel_step_world_size_2(tmp_path, pipe, overlap):
     assert str(two["schedule"]) == want, str(two["schedule"])
 
 
+@pytest.mark.parametrize("knob,agree", [("TN_C8_WTR=0", False), ("TN_C8_WSLAB_DIV=2", True)])
+def test_data_parallel_ranks_agree_on_the_resolved_knobs(tmp_path, knob, agree):
+    """NeuralNet compares the library's switches as the library resolved them (tn_knobs) across ranks: a rank with
+    another weight-gradient form refuses to build on both ranks, and a rank that spells the default out builds and
+    steps with one that leaves it unset."""
+    worker = os.path.join(ROOT, "tests", "dp_gpu_worker.py")
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    name, value = knob.split("=")
+    procs = []
+    for rank in range(2):
+        env = _env(RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                   OMP_NUM_THREADS="2")
+        env.pop(name, None)
+        if rank == 1:
+            env[name] = value
+        procs.append(subprocess.Popen([sys.executable, worker, str(tmp_path / "k.npz"), "mnist.prms", "28", "1", "32", "2"],
+                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+    for p in procs:
+        try:
+            o, _ = p.communicate(timeout=600)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        o = o.decode()
+        if agree:
+            assert p.returncode == 0, o[-3000:]
+        else:
+            assert p.returncode != 0 and "kernel tunables" in o and "TN_C8_WTR=" in o, o[-3000:]
+    assert os.path.isfile(tmp_path / "k.npz") == agree
+
+
 @pytest.mark.parametrize("world", [2, 4])
 def test_bucketed_allreduce_equals_single_bucket(tmp_path, world):
     """Two steps in flight, data-parallel: the dense group's gradients (+ cost) leave as a bucket of their own right

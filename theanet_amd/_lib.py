@@ -38,6 +38,7 @@ CTX = c_void_p
 # (tests/test_abi.py parses the header and checks nothing is missing).
 SIGNATURES = {
     "tn_version": (c_int, []),
+    "tn_knobs": (c_int, [c_char_p, c_int]),
     "tn_device_count": (c_int, [POINTER(c_int)]),
     "tn_ctx_create": (c_int, [c_int, POINTER(CTX)]),
     "tn_ctx_destroy": (c_int, [CTX]),

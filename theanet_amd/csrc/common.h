@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/theanet_hip.h"
+#include "knobs.h"
 
 // arguments of the elastic field computation (elastic_field.h)
 struct ElField {       // arguments of the field computation (shared by its two launchers)

@@ -625,6 +625,14 @@ extern "C" int C8_API(tn_c8_dbg_read)(tn_ctx* ctx, unsigned long long* host, int
     (void)ctx;
     return hipMemcpy(host, c8_dbg_buf, (size_t)nblocks * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
 }
+// TN_C8_DBG: a zeroed stamp buffer for a launch of `grid` blocks (none for a grid beyond its 65536 records)
+static int c8_dbg_arm(tn_ctx* ctx, unsigned long long*& dbg, int grid) {
+    if (!tn_knob(TN_K_C8_DBG)) return TN_OK;
+    if (!c8_dbg_buf) TN_HIP(hipMalloc(&c8_dbg_buf, 8 * sizeof(unsigned long long) * 65536));
+    TN_HIP(hipMemsetAsync(c8_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream));
+    dbg = grid <= 65536 ? c8_dbg_buf : nullptr;
+    return TN_OK;
+}
 
 // The instantiation c8_run launches for a shape: c8_conv_kernel<FT, MODE, NS, LK, TK>.  c8_plan makes the whole choice
 // (and fills the geometry); c8_run and c8_launch only map it onto templates, and tn_c8_conv_plan reports it.
@@ -652,16 +660,7 @@ static int c8_launch(tn_ctx* ctx, C8G& g, const C8Plan& p) {
     // LDS allow it): another wave per SIMD under their epilogues
     int grid = 8 * ((FT == 1 && 3 * lds <= 150 * 1024 ? 3 : 2) * ctx->num_cus / 8);
     if (grid > g.nwork) grid = g.nwork;
-    static int dbg_on = -1;
-    if (dbg_on < 0) {
-        const char* e = getenv("TN_C8_DBG");
-        dbg_on = e ? atoi(e) : 0;
-    }
-    if (dbg_on) {
-        if (!c8_dbg_buf) TN_HIP(hipMalloc(&c8_dbg_buf, 8 * sizeof(unsigned long long) * 65536));
-        TN_HIP(hipMemsetAsync(c8_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream));
-        g.dbg = grid <= 65536 ? c8_dbg_buf : nullptr;
-    }
+    if (int rc = c8_dbg_arm(ctx, g.dbg, grid)) return rc;
 #define C8_GO(NS, LK)                                                                                         \
     {                                                                                                         \
         static bool attr_set = false;                                                                         \
@@ -1739,22 +1738,6 @@ static void c8w_tiles(int K, int C, int& NFT, int& NCT) {
     NCT = C > 32 ? 2 : (C > 8 ? 1 : 0);          // 0: one octet, taps packed into the columns (c8_wgrad_kernel)
 }
 
-static int c8w_tr_on() {             // TN_C8_WTR=0: the eight-wave kernel everywhere (A/B)
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("TN_C8_WTR");
-        on = e ? atoi(e) : 1;
-    }
-    return on;
-}
-static int c8w_roll_on() {           // TN_C8_ROLL=0: the halo-tile form everywhere (A/B)
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("TN_C8_ROLL");
-        on = e ? atoi(e) : 1;
-    }
-    return on;
-}
 static int c8w_geometry(C8WG& g, int num_cus, bool pool, int tm = 1) {
     const int lgW = c8w_log2(g.Wd);
     if (lgW < 3 || lgW > 6) return 0;                  // rows of 8..64 pixels
@@ -1792,8 +1775,9 @@ static int c8w_geometry(C8WG& g, int num_cus, bool pool, int tm = 1) {
     g.roll = 0; g.XA = 0;
     // (16-pixel rows: the ring only under the sixteen-wave kernel -- its four loader waves are bound by the NUMBER of LDS-DMAs
     // they issue, 8 per tile with the ring against 10 with halo tiles; under the eight-wave kernel the ring lost there, round 4)
-    const bool tr_shape = NFT == 2 && NCT >= 1 && tm == 1 && c8w_tr_on();
-    if (NCT && tm == 1 && g.NI == 1 && g.RT >= 2 && lgW >= ((c8w_roll_on() == 2 || tr_shape) ? 4 : 5) && c8w_roll_on()) {
+    const bool tr_shape = NFT == 2 && NCT >= 1 && tm == 1 && tn_knob(TN_K_C8_WTR);
+    const int roll = tn_knob(TN_K_C8_ROLL);
+    if (NCT && tm == 1 && g.NI == 1 && g.RT >= 2 && lgW >= ((roll == 2 || tr_shape) ? 4 : 5) && roll) {
         // ROLL (c8_wgrad_kernel): x ring of four TH-row regions + a zero row per plane, no halo columns; three dz stages
         const int xps = (16 + 4 * 2048 + g.Wd * 16 + 16 + 255) / 256 * 256 + 64;
         const int offG = KP * g.DPS, offM = offG;
@@ -1814,14 +1798,9 @@ static int c8w_geometry(C8WG& g, int num_cus, bool pool, int tm = 1) {
     // stream's launches fill the CUs left free, every block amortises its fixed costs over twice the pixels, and the slabs
     // written here and read back by the update halve (wide6: 189 MB per step).  Same count under every schedule (the
     // slab order is part of the result's bits); one step at a time pays ~10 % for it.  TN_C8_WSLAB_DIV=1: every CU (A/B).
-    static int div_ = -1;
-    if (div_ < 0) {
-        const char* e = getenv("TN_C8_WSLAB_DIV");
-        div_ = e && atoi(e) > 0 ? atoi(e) : 2;
-    }
     // (first layers -- one octet plane, taps packed, a slab of a few KB -- keep every CU: cifar_like float16 0.3130 ->
     // 0.3031 ms same-box against half)
-    int S = num_cus / (NCT == 0 ? 1 : div_) / (g.KG * g.CG);
+    int S = num_cus / (NCT == 0 ? 1 : tn_knob(TN_K_C8_WSLAB_DIV)) / (g.KG * g.CG);
     if (S > g.NTILES) S = g.NTILES;
     if (S < 1) S = 1;
     g.tpb = cdiv(g.NTILES, S);
@@ -1843,24 +1822,8 @@ static int c8w_launch(tn_ctx* ctx, C8WG& g) {
         attr_set = true;
     }
     const int grid = 8 * cdiv(g.S, 8) * g.KG * g.CG;
-    static int dbg_on = -1;
-    if (dbg_on < 0) {
-        const char* e = getenv("TN_C8_DBG");
-        dbg_on = e ? atoi(e) : 0;
-    }
-    if (dbg_on) {
-        if (!c8_dbg_buf) TN_HIP(hipMalloc(&c8_dbg_buf, 8 * sizeof(unsigned long long) * 65536));
-        TN_HIP(hipMemsetAsync(c8_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream));
-        g.dbg = grid <= 65536 ? c8_dbg_buf : nullptr;
-    }
-    {
-        static int exp_ = -1;
-        if (exp_ < 0) {
-            const char* e = getenv("TN_C8_EXP");
-            exp_ = e ? atoi(e) : 0;
-        }
-        g.exp = exp_;
-    }
+    if (int rc = c8_dbg_arm(ctx, g.dbg, grid)) return rc;
+    g.exp = tn_knob(TN_K_C8_EXP);
     c8_wgrad_kernel<E, NFT, NCT, POOL, NGX, TM, ROLL><<<grid, 512, c8w_lds_bytes(g), ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
@@ -1876,16 +1839,7 @@ static int c8w_tr_launch(tn_ctx* ctx, C8WG& g) {
         attr_set = true;
     }
     const int grid = 8 * cdiv(g.S, 8) * g.KG * g.CG;
-    static int dbg_on = -1;
-    if (dbg_on < 0) {
-        const char* e = getenv("TN_C8_DBG");
-        dbg_on = e ? atoi(e) : 0;
-    }
-    if (dbg_on) {
-        if (!c8_dbg_buf) TN_HIP(hipMalloc(&c8_dbg_buf, 8 * sizeof(unsigned long long) * 65536));
-        TN_HIP(hipMemsetAsync(c8_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream));
-        g.dbg = grid <= 65536 ? c8_dbg_buf : nullptr;
-    }
+    if (int rc = c8_dbg_arm(ctx, g.dbg, grid)) return rc;
     c8_wgrad_tr_kernel<E, NCT, NGX, POOL, ROLL><<<grid, 1024, c8w_lds_bytes(g), ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
@@ -1923,7 +1877,7 @@ static int c8w_plan(tn_ctx* ctx, C8WG& g, int num_cus, bool pool, C8WPlan& p) {
     c8w_tiles(g.K, g.C, NFT, NCT);
     p.NFT = NFT; p.NCT = NCT; p.TM = tm; p.ROLL = g.roll;
     const int ngx = c8w_ngx(g);
-    p.tr = NFT == 2 && NCT >= 1 && tm == 1 && c8w_tr_on() && c8w_tr_shape_ok(g, NCT);
+    p.tr = NFT == 2 && NCT >= 1 && tm == 1 && tn_knob(TN_K_C8_WTR) && c8w_tr_shape_ok(g, NCT);
     if (p.tr) {
         p.NGX = g.roll ? 2 * NCT : g.nQx / (4 * NCT) * NCT;       // (c8w_tr_shape_ok: 2..5 chunks per plane)
     } else if (NCT == 0) {

@@ -238,18 +238,9 @@ static size_t ct_lds_bytes(const ConvTG& g, int FT) {
 
 static int ct_pick_ft(int K) { return K > 32 ? 2 : 1; }
 
-static bool ct_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("TN_CONV_TILE");
-        on = (e && e[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
-
 // 1 if conv_tile_kernel handles the (gathered tensor N,C,H,Wd; K filters; pad; output Ho,Wo) problem
 int tn_conv_tile_ok(const float* x, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
-    if (!ct_enabled() || f != 3 || pad < 0 || pad > 2) return 0;
+    if (!tn_knob(TN_K_CONV_TILE) || f != 3 || pad < 0 || pad > 2) return 0;
     if (reinterpret_cast<uintptr_t>(x) & 15) return 0;
     ConvTG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
@@ -277,7 +268,7 @@ static int ct_launch(tn_ctx* ctx, ConvTG& g) {
     }
     const int grid = 8 * cdiv(g.MT, 8) * g.KT;
     static unsigned long long* dbgbuf = nullptr;
-    if (getenv("TN_CT_DBG")) {
+    if (tn_knob(TN_K_CT_DBG)) {
         if (!dbgbuf) TN_HIP(hipMalloc(&dbgbuf, 8 * sizeof(unsigned long long) * 65536));
         ct_dbg_buf = dbgbuf;
         g.dbg = grid <= 65536 ? dbgbuf : nullptr;
@@ -574,9 +565,9 @@ static size_t cw_lds_bytes(const ConvWG& g) {
 
 int tn_conv_tile_wgrad_ok(tn_ctx* ctx, const float* x, const float* dz, int N, int C, int H, int Wd, int K,
                           int f, int pad, int Ho, int Wo) {
-    if (!ct_enabled() || f != 3 || pad != 1 || Ho != H || Wo != Wd) return 0;
+    if (!tn_knob(TN_K_CONV_TILE) || f != 3 || pad != 1 || Ho != H || Wo != Wd) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) return 0;
-    if (const char* e = getenv("TN_CONV_TILE_WGRAD")) if (e[0] == '0') return 0;
+    if (!tn_knob(TN_K_CONV_TILE_WGRAD)) return 0;
     ConvWG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
     if (!cw_geometry(g, ctx->num_cus)) return 0;
@@ -634,10 +625,10 @@ extern "C" {
 // forward pools in its epilogue and records the pooling mask, the backward forms dz from that mask.
 int tn_convpool_tile_supported(int N, int C, int H, int Wd, int K, int f, int stride, int pad, int Ho, int Wo,
                                int p, int Hp, int Wp) {
-    if (!ct_enabled() || f != 3 || stride != 1 || p != 2 || pad != 1 || Ho != H || Wo != Wd) return 0;
+    if (!tn_knob(TN_K_CONV_TILE) || f != 3 || stride != 1 || p != 2 || pad != 1 || Ho != H || Wo != Wd) return 0;
     if ((Ho & 1) || (Wo & 3) || Hp * 2 != Ho || Wp * 2 != Wo) return 0;
     if (C * 9 < 32 || K < 16) return 0;
-    if (const char* e = getenv("TN_CONV_TILE_POOL")) if (e[0] == '0') return 0;
+    if (!tn_knob(TN_K_CONV_TILE_POOL)) return 0;
     ConvTG a{};                                   // forward
     a.N = N; a.C = C; a.H = H; a.Wd = Wd; a.K = K; a.pad = 1; a.Ho = Ho; a.Wo = Wo;
     if (!ct_geometry(a, ct_pick_ft(K)) || (a.TH & 1) || ct_lds_bytes(a, ct_pick_ft(K)) > 150 * 1024) return 0;
@@ -850,9 +841,9 @@ static int cs_geometry(ConvSG& g, int num_cus) {
 
 extern "C" int tn_convpool_smallc_supported(int N, int C, int H, int Wd, int K, int f, int pad, int Ho,
                                             int Wo, int p, int Hp, int Wp) {
-    if (!ct_enabled() || f != 3 || p != 2 || pad != 1 || Ho != H || Wo != Wd || C * 9 > 32 || K < 16) return 0;
+    if (!tn_knob(TN_K_CONV_TILE) || f != 3 || p != 2 || pad != 1 || Ho != H || Wo != Wd || C * 9 > 32 || K < 16) return 0;
     if ((Ho & 1) || (Wo & 3) || Hp * 2 != Ho || Wp * 2 != Wo) return 0;
-    if (const char* e = getenv("TN_CONV_TILE_SMALLC")) if (e[0] == '0') return 0;
+    if (!tn_knob(TN_K_CONV_TILE_SMALLC)) return 0;
     ConvSG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
     return cs_geometry(g, 256);
@@ -892,9 +883,9 @@ int tn_conv_tile_smallc_bwd(tn_ctx* ctx, const float* x, const float* g_, const 
 // unfused first layers: dW, db from the plain dz tensor
 int tn_conv_tile_smallc_ok(const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad,
                            int Ho, int Wo) {
-    if (!ct_enabled() || f != 3 || pad != 1 || Ho != H || Wo != Wd || C * 9 > 32 || K < 16) return 0;
+    if (!tn_knob(TN_K_CONV_TILE) || f != 3 || pad != 1 || Ho != H || Wo != Wd || C * 9 > 32 || K < 16) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) return 0;
-    if (const char* e = getenv("TN_CONV_TILE_SMALLC")) if (e[0] == '0') return 0;
+    if (!tn_knob(TN_K_CONV_TILE_SMALLC)) return 0;
     ConvSG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
     return cs_geometry(g, 256);

@@ -13,8 +13,6 @@
 //            per block is written at the end and reduced (fixed order) by conv_wgrad_finish.
 // HBM traffic: x, g read once, dx written once.  Semantics: theanet/layer/convpool.py:54-72,
 // :106-112; Theano MaxPoolGrad tie rule.
-#include <cstdlib>
-
 #include "common.h"
 
 int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
@@ -323,14 +321,7 @@ extern "C" int tn_convblock_bwd(tn_ctx* ctx, const float* x, const float* W, con
     CbGeom q;
     q.N = N; q.H = H; q.Wd = Wd; q.K = K; q.pad = pad_lo; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp;
     q.G = G;
-    {
-        static int dbg = -1;
-        if (dbg < 0) {
-            const char* e = getenv("TN_CB_DBG");
-            dbg = e ? atoi(e) : 0;
-        }
-        q.dbg = dbg;
-    }
+    q.dbg = tn_knob(TN_K_CB_DBG);
     q.Hx = Ho + f - 1; q.Hh = Ho + 2 * f - 2;
     q.Wh = 4 * ((Wo + 3) / 4) + 4;
     q.Wx = q.Wh + 4;      // x rows 4 floats wider: de-phases the (c, u) b128 reads of phase 3

@@ -20,8 +20,6 @@
 // goes to LDS only for the dgrad product, never to HBM.  The filter operands of all three
 // products stay in registers for the whole kernel; the next image's x and g are prefetched
 // into registers while the current one is computed.  HBM traffic: x, g read once, dx written once.
-#include <cstdlib>
-
 #include "common.h"
 
 int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
@@ -831,12 +829,7 @@ static int launch_cm_mask(tn_ctx* ctx, const float* x, const float* W, const flo
     if (rc) return rc;
     float* dbpartial = partial + (size_t)nblk * KCFF;
     float* tdbg = (q.dbg & 16) ? db : nullptr;
-    static int w44 = -1;
-    if (w44 < 0) {
-        const char* e = getenv("TN_CB_W44");
-        w44 = e ? atoi(e) : 1;
-    }
-    if (act == TN_ACT_LEAKY && w44) {
+    if (act == TN_ACT_LEAKY && tn_knob(TN_K_CB_W44)) {
         auto kern = convblock_bwd_mask_mfma<C, KS2, TN_ACT_LEAKY, true>;
         static size_t set_for = 0;
         if (set_for < lds) {
@@ -866,15 +859,6 @@ static int launch_cm_mask(tn_ctx* ctx, const float* x, const float* W, const flo
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, q.K, C, 3);
 }
 
-static int cm_dbg() {
-    static int dbg = -1;
-    if (dbg < 0) {
-        const char* e = getenv("TN_CM_DBG");
-        dbg = e ? atoi(e) : 0;
-    }
-    return dbg;
-}
-
 extern "C" int tn_convblock_mask_supported(int C, int K, int f, int stride, int p, int H, int Wd,
                                            int pad_lo, int Ho, int Wo, int Hp, int Wp) {
     return cm_supported(C, K, f, stride, p, H, Wd, pad_lo, Ho, Wo, Hp, Wp, false);
@@ -890,7 +874,7 @@ extern "C" int tn_convblock_bwd_mask(tn_ctx* ctx, const float* x, const float* W
     CmGeom q;
     q.N = N; q.H = H; q.Wd = Wd; q.K = K; q.pad = pad_lo; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp;
     cm_geometry(q, C, K);
-    q.dbg = cm_dbg();
+    q.dbg = tn_knob(TN_K_CM_DBG);
 #define CM_KS(C_, S_) case S_: return launch_cm_mask<C_, S_>(ctx, x, W, g, y, mask, dx, dW, db, q, act, act_param)
 #define CM_GO(C_)                                                                                  \
     switch ((K + 3) / 4) {                                                                         \
@@ -913,14 +897,7 @@ int tn_convblock_mfma_bwd(tn_ctx* ctx, const float* x, const float* W, const flo
     CmGeom q;
     q.N = N; q.H = H; q.Wd = Wd; q.K = K; q.pad = pad_lo; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp;
     cm_geometry(q, C, K);
-    {
-        static int dbg = -1;
-        if (dbg < 0) {
-            const char* e = getenv("TN_CM_DBG");
-            dbg = e ? atoi(e) : 0;
-        }
-        q.dbg = dbg;
-    }
+    q.dbg = tn_knob(TN_K_CM_DBG);
 #define CM_KS(C_, S_) case S_: return launch_cm<C_, S_>(ctx, x, W, b, g, dx, dW, db, q, act, act_param)
 #define CM_GO(C_)                                                                                  \
     switch ((K + 3) / 4) {                                                                         \

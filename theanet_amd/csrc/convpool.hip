@@ -15,8 +15,6 @@
 //             pool-bwd + wgrad traffic of ~5x that.
 //
 // Semantics: theanet/layer/convpool.py:54-72 (true convolution, flipped W), :106-112 (pool).
-#include <cstdlib>
-
 #include "common.h"
 
 // conv_tile.hip: the matrix-core kernels for wide 3x3 'same' blocks
@@ -445,14 +443,7 @@ static int launch_fwd(tn_ctx* ctx, const float* x, const float* W, const float* 
     // filter slices (blockIdx.y) until the launch has about two blocks per CU
     int ks = 1;
     while (ks < 8 && ks * 2 <= K && (long long)cdiv(total, 256) * ks < 2 * ctx->num_cus) ks *= 2;
-    {
-        static int force = -1;
-        if (force < 0) {
-            const char* e = getenv("TN_CONVPOOL_KS");
-            force = e ? atoi(e) : 0;
-        }
-        if (force > 0) ks = force;
-    }
+    if (tn_knob(TN_K_CONVPOOL_KS) > 0) ks = tn_knob(TN_K_CONVPOOL_KS);
     const dim3 grid(cdiv(total, 256), ks);
 #define CP_L(ACT_, PAD_)                                                                          \
     convpool_fwd_kernel<F, P, C, ACT_, PAD_><<<grid, 256, 0, ctx->stream>>>(                       \

@@ -8,6 +8,7 @@ char g_tn_err[512] = {0};
 extern "C" {
 
 int tn_version(void) { return 100; }
+int tn_knobs(char* buf, int len) { return tn_knobs_format(buf, len); }
 
 int tn_device_count(int* count) {
     tn_ctx* ctx = nullptr;

@@ -4,8 +4,6 @@
 // Coordinates are computed in float64 exactly as the Theano CPU path does (int64 indices +
 // float32 random inputs upcast to float64); the field is tiny (2 x h x w) so fp64 is free.
 // The gather kernel is the HBM-bound part: x read once, out written once.
-#include <cstdlib>
-
 #include "c8_elem.h"
 #include "common.h"
 #include "update_body.h"
@@ -618,12 +616,7 @@ int tn_c8_elastic_apply(tn_ctx* ctx, const float* x, int64_t x_row0, const int64
 
 int tn_elastic_convpool_supported(int h, int w, int K, int f, int pad_lo, int Ho, int Wo, int p, int Hp,
                                   int Wp) {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("TN_ELASTIC_CONV");
-        on = e ? atoi(e) : 1;
-    }
-    if (!on || f != 3 || p != 2 || K < 1 || K > 16 || w % 4 != 0) return 0;
+    if (!tn_knob(TN_K_ELASTIC_CONV) || f != 3 || p != 2 || K < 1 || K > 16 || w % 4 != 0) return 0;
     if (h + 2 * pad_lo > 2 * Hp + 2 || w + 2 * pad_lo > 2 * Wp + 2) return 0;      // image fits the tile
     if (Hp != (Ho + 1) / 2 || Wp != (Wo + 1) / 2) return 0;
     return (size_t)(2 * Hp + 2) * (2 * Wp + 2) * sizeof(float) <= 48 * 1024;

@@ -136,14 +136,6 @@ __device__ __forceinline__ float4 fc8_finish4(float4 v, size_t i, int n, const f
     return make_float4(x[0], x[1], x[2], x[3]);
 }
 
-static int fc8_xcd_on() {             // TN_FC8_XCD=0: plain block decode (A/B)
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("TN_FC8_XCD");
-        on = e ? atoi(e) : 1;
-    }
-    return on;
-}
 #define FC8_NST 4
 #define FC8F_XS 144         // x tile row stride (64 halfs + 16 bytes: 9 x 16 B, every 16-byte read of 32 rows on its own banks)
 #define FC8F_WS 192         // W tile row stride (64 halfs + 64 bytes = 64 (mod 128): the 4 rows of a transposing read on disjoint banks)
@@ -597,24 +589,14 @@ static int fc8_fwd_run(tn_ctx* ctx, const void* x, const float* W, const float* 
     // TN_FC8_FWD_HALF=1 (round 6 A/B): a product whose tiles fill at least half the CUs takes ONE K slab -- no slab written
     // and read back, no finishing launch, and with two steps in flight the other stream's launches fill the idle half
     // (what paid for the fp16 weight gradients, DESIGN.md lesson 18): cifar_like's 2048 x 2048 -> 512 dense layer, 128 tiles
-    static int half_ok = -1;
-    if (half_ok < 0) {
-        const char* e = getenv("TN_FC8_FWD_HALF");
-        half_ok = e ? atoi(e) : 0;
-    }
-    if (half_ok && 2 * colg * rowg >= ctx->num_cus) S = 1;
+    if (tn_knob(TN_K_FC8_FWD_HALF) && 2 * colg * rowg >= ctx->num_cus) S = 1;
     if (S > g.Kc / 256) S = g.Kc / 256;
     if (S < 1) S = 1;
     g.krange = cdiv(cdiv(g.Kc, S), 64) * 64;
     S = cdiv(g.Kc, g.krange);
     g.S = S;
-    g.xcd = fc8_xcd_on() && (S * rowg) % 8 == 0;
-    static int fin_on = -1;                // TN_FC8_FIN=0: the finishing launch also for one slab (A/B)
-    if (fin_on < 0) {
-        const char* e = getenv("TN_FC8_FIN");
-        fin_on = e ? atoi(e) : 1;
-    }
-    if (S == 1 && n_out % 64 == 0 && fin_on && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)mask | (uintptr_t)dr.mask_out) & 15) == 0) {
+    g.xcd = tn_knob(TN_K_FC8_XCD) && (S * rowg) % 8 == 0;
+    if (S == 1 && n_out % 64 == 0 && tn_knob(TN_K_FC8_FIN) && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)mask | (uintptr_t)dr.mask_out) & 15) == 0) {
         g.bias = b; g.mask = mask; g.out = a; g.act = act; g.prm = act_param;
         fc8_fwd_kernel<C8E, true><<<dim3(colg, 1, rowg), 256, 0, ctx->stream>>>(g, dr);
         TN_LAUNCH_CHECK();
@@ -693,12 +675,7 @@ int C8_API(tn_c8_fc_wgrad)(tn_ctx* ctx, const void* x, const float* dz, float* d
     // sample slabs: ONE block per CU (round 5; two per CU until then).  The launch is bound by its traffic, not by its
     // products (cifar_like: 4.3 GFLOP, 83 MB per launch), and every slab is written here and read back by the update:
     // cifar_like float16 step 0.3261 (8 slabs) -> 0.3175 (4) -> 0.3198 (2) ms same-box.  TN_FC8_WSLABS: half blocks per CU.
-    static int half_cu = -1;
-    if (half_cu < 0) {
-        const char* e = getenv("TN_FC8_WSLABS");
-        half_cu = e ? atoi(e) : 2;
-    }
-    int S = cdiv(half_cu * ctx->num_cus / 2, kb * nb);
+    int S = cdiv(tn_knob(TN_K_FC8_WSLABS) * ctx->num_cus / 2, kb * nb);
     if (S > cdiv(B, 64)) S = cdiv(B, 64);
     if (S < 1) S = 1;
     g.krange = cdiv(cdiv(B, S), 64) * 64;
@@ -720,12 +697,7 @@ int C8_API(tn_c8_fc_wgrad)(tn_ctx* ctx, const void* x, const float* dz, float* d
     float* scr;
     rc = tn_scratch_get(ctx, slabf4 * sizeof(float) + (size_t)B * g.Np * sizeof(_Float16), &scr);
     if (rc) return rc;
-    static int keep_on = -1;               // TN_FC8_DZ16=0: the conversion stays a launch of its own (A/B)
-    if (keep_on < 0) {
-        const char* e = getenv("TN_FC8_DZ16");
-        keep_on = e ? atoi(e) : 1;
-    }
-    if (keep_on) {
+    if (tn_knob(TN_K_FC8_DZ16)) {
         g.dz16w = reinterpret_cast<_Float16*>(scr + slabf4);
         fc8_dz16_keep = {ctx, ctx->stream, dz, g.dz16w, B, n_out, ctx->mm_f16, ctx->grad_scale, ctx->scratch_gen};
     }

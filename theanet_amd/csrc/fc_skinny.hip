@@ -8,8 +8,6 @@
 //   dgrad  dx = (dz W^T) act'(a) mask    VALU: thread = 4 input features, dz rows as scalar loads
 // Requires n_in % 4 == 0 and 16-byte aligned rows (tn_fc_skinny_ok); anything else keeps the
 // scalar kernels in gemm.hip.
-#include <cstdlib>
-
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -458,12 +456,7 @@ __global__ __launch_bounds__(256) void fc_skinny_softmax_train(
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 bool tn_fc_skinny_ok(int n_in, int n_out, const void* p0, const void* p1, const void* p2) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("TN_FC_SKINNY");
-        enabled = e ? atoi(e) : 1;
-    }
-    return enabled && n_out <= SK_MAX && n_in % 4 == 0 && n_in >= 4 && al16(p0) && (!p1 || al16(p1)) &&
+    return tn_knob(TN_K_FC_SKINNY) && n_out <= SK_MAX && n_in % 4 == 0 && n_in >= 4 && al16(p0) && (!p1 || al16(p1)) &&
            (!p2 || ((uintptr_t)p2 & 3) == 0);
 }
 

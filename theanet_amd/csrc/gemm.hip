@@ -22,7 +22,6 @@
 //
 // Skinny layers (n_out <= 16, the 10-way softmax layer) would waste >2/3 of a 32-wide MFMA
 // tile and leave most CUs idle; they run on dedicated VALU kernels at the end of this file.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -1075,18 +1074,10 @@ static bool gemm_cvec_ok(const GemmArgs& g) {
 }
 
 // DEEP pays while the 64 x 64 tiles cannot fill the chip and the L2 re-reads (M*N*K/4 bytes) stay small
-static int tn_tune_deep() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("TN_GEMM_DEEP");   // 0 off, 1 auto (default), 4 / 8: force that many waves
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
 template <bool BKC>
 static bool gemm_deep_ok(tn_ctx* ctx, const GemmArgs& g) {
-    if (!tn_tune_deep() || !g.a_vec || !g.b_vec || !gemm_cvec_ok(g) || g.K % 4 != 0 || g.K < 128) return false;
-    if (tn_tune_deep() > 1) return true;
+    if (!tn_knob(TN_K_GEMM_DEEP) || !g.a_vec || !g.b_vec || !gemm_cvec_ok(g) || g.K % 4 != 0 || g.K < 128) return false;
+    if (tn_knob(TN_K_GEMM_DEEP) > 1) return true;
     const long long tiles64 = (long long)cdiv(g.M, 64) * cdiv(g.N, 64);
     return tiles64 <= ctx->num_cus && (long long)g.M * g.N * g.K / 4 <= (128ll << 20);
 }
@@ -1098,7 +1089,8 @@ static void launch_deep(tn_ctx* ctx, GemmArgs& g) {
     g.NT = cdiv(g.N, 32);
     const int grid = g.MT * g.NT;
     int nw = (grid <= 2 * ctx->num_cus && g.K >= 512) ? 8 : 4;
-    if (tn_tune_deep() == 4 || tn_tune_deep() == 8) nw = tn_tune_deep();
+    const int deep = tn_knob(TN_K_GEMM_DEEP);
+    if (deep == 4 || deep == 8) nw = deep;
     if (nw == 8)
         gemm_f32_deep<BKC, 8><<<grid, 512, 0, ctx->stream>>>(g);
     else
@@ -1112,17 +1104,9 @@ extern "C" int tn_gemm_dbg_read(tn_ctx* ctx, unsigned long long* host, int nrec)
     return hipMemcpy(host, gemm_dbg_buf, (size_t)nrec * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
 }
 // DMA kernel: FAST's preconditions, every K slab holds a full tile, per-lane byte offsets fit 32 bits
-static int tn_tune_dma() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("TN_GEMM_DMA");    // 0: register-staged tiles (gemm_f32_fast); 2: the DMA kernel also where 128 x 64 tiles would be taken
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
 template <bool AKC, bool BKC>
 static bool gemm_dma_ok(const GemmArgs& g, int S) {
-    if (!tn_tune_dma() || !gemm_fast_ok<AKC, BKC>(g)) return false;
+    if (!tn_knob(TN_K_GEMM_DMA) || !gemm_fast_ok<AKC, BKC>(g)) return false;
     const long long lastk = (long long)g.K - (long long)(S - 1) * g.kchunk;
     if (g.kchunk < 256 || lastk < 16) return false;      // short reductions (< 16 tiles) gain nothing from the ring: wide6's 128-row weight gradient measured 1.5 % of a step slower
     const long long ea = AKC ? (long long)g.M * g.lda : (long long)g.kchunk * g.lda + g.M;
@@ -1144,22 +1128,14 @@ static void launch_gemm(tn_ctx* ctx, GemmArgs& g, int S) {
     const int grid = (S == 1) ? 8 * cdiv(g.MT, 8) * g.NT : gemm_grid_split(S, g.MT * g.NT);
     if (!fast)
         gemm_f32_generic<AKC, BKC, BSUM><<<grid, 256, 0, ctx->stream>>>(g);
-    else if ((!big || tn_tune_dma() == 2) && gemm_dma_ok<AKC, BKC>(g, S)) {
+    else if ((!big || tn_knob(TN_K_GEMM_DMA) == 2) && gemm_dma_ok<AKC, BKC>(g, S)) {
         g.MT = cdiv(g.M, 64);
         const int nb = (S == 1) ? 8 * cdiv(g.MT, 8) * g.NT : gemm_grid_split(S, g.MT * g.NT);
-        static int dbg_on = -1, pad = 0, nsf = 0;
-        if (dbg_on < 0) {
-            const char* e = getenv("TN_GEMM_DBG");
-            dbg_on = e ? atoi(e) : 0;
-            e = getenv("TN_GEMM_DMA_PAD");
-            pad = e ? atoi(e) : 0;
-            e = getenv("TN_GEMM_DMA_NS");
-            nsf = e ? atoi(e) : 0;
-        }
+        const int pad = tn_knob(TN_K_GEMM_DMA_PAD), nsf = tn_knob(TN_K_GEMM_DMA_NS);
         const int grid = nb + ((BSUM && !BKC) ? S * g.NT : 0);
         // two blocks per CU or fewer: the deep ring; else four stages
         const int ns = nsf ? nsf : (nb <= 2 * ctx->num_cus ? 8 : 4);
-        if (dbg_on) {
+        if (tn_knob(TN_K_GEMM_DBG)) {
             // (cycle stamps: 8 words per wave, 4 waves per block, 65536 records)
             // (this launcher returns nothing: a stamp buffer that cannot be had, or a grid beyond its 65536 records,
             // just runs unstamped -- g.dbg stays NULL and the kernel writes no stamps)
@@ -1199,11 +1175,7 @@ static int wgrad_splits(int B, int n_in, int n_out) {
     // K-slabs (1, 2, 4 or 8; every slab is written here and read back by the update): as few as give four 64 x 64 blocks
     // per CU, each with >= 8 K-tiles.  mnist.prms (96 tiles): 8; cifar_like (256 tiles): 4 (step 1.4038 ms with 8 slabs,
     // 1.3890 with 4, 1.3980 with 2, same box).
-    static int force = -1;
-    if (force < 0) {
-        const char* e = getenv("TN_FC_WSPLIT");
-        force = e ? atoi(e) : 0;
-    }
+    const int force = tn_knob(TN_K_FC_WSPLIT);
     if (force == 1 || force == 2 || force == 4 || force == 8) return B >= force * 8 * BK ? force : 1;
     const long long tiles = (long long)cdiv(n_in, 64) * cdiv(n_out, 64);
     int S = 1;
@@ -1398,12 +1370,7 @@ int tn_fc_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && logits && logprob && y && dz && dW && db && dx && ws,
                "tn_fc_softmax_train: bad arguments");
     TN_REQUIRE(prev_a == nullptr || prev_a == x, "tn_fc_softmax_train: prev_a must be the layer input");
-    static int fused_on = -1;
-    if (fused_on < 0) {
-        const char* e = getenv("TN_SOFTMAX_TRAIN");
-        fused_on = e ? atoi(e) : 1;
-    }
-    if (fused_on && tn_fc_skinny_ok(n_in, n_out, x, dx, prev_mask))
+    if (tn_knob(TN_K_SOFTMAX_TRAIN) && tn_fc_skinny_ok(n_in, n_out, x, dx, prev_mask))
         return tn_fc_skinny_softmax_train(ctx, x, W, b, logits, B, n_in, n_out, y, y_row0, d_row0, logprob,
                                           rowloss, pred, rowp, dz, inv_batch, dW, db, dx, (float*)ws,
                                           prev_a != nullptr, prev_act, prev_act_param, prev_mask);
@@ -1488,12 +1455,7 @@ __global__ __launch_bounds__(256) void fc_dgrad_finish_kernel(const float* __res
 }
 
 static int fc_dgrad_splits(tn_ctx* ctx, int B, int n_in, int n_out) {
-    static int force = -1;
-    if (force < 0) {
-        const char* e = getenv("TN_FC_DGRAD_SPLIT");
-        force = e ? atoi(e) : 0;
-    }
-    if (force > 0) return force;
+    if (tn_knob(TN_K_FC_DGRAD_SPLIT) > 0) return tn_knob(TN_K_FC_DGRAD_SPLIT);
     if (B > 256 || n_out < 32 * BK || n_in < 2048) return 1;
     int S = n_out / (8 * BK);                  // >= 8 K-tiles per slab
     if (S > 8) S = 8;
@@ -1665,11 +1627,7 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
             int nrider = 0;
             size_t rlds = 0;
             ElField rider{};
-            static int pns = -1;
-            if (pns < 0) {
-                const char* e = getenv("TN_PAIR_DMA");      // ring stages * 10 + waves per SIMD (experiments)
-                pns = e ? atoi(e) : 26;
-            }
+            const int pns = tn_knob(TN_K_PAIR_DMA);      // ring stages * 10 + waves per SIMD (experiments)
             const bool use_dma = gemm_dma_ok<false, false>(g1, Sx) && gemm_dma_ok<true, true>(g2, 1);
             // the rider works in the STATIC LDS of the kernel that is launched: the DMA form declares its ring
             // (gemm_dma_smem_floats<NS>: 17 408 bytes at two stages), the register form 20 480 bytes -- a field that needs
@@ -1691,11 +1649,7 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
                 // leave them a fifth of the register file (six leave 32 registers per lane: nothing else fits and the
                 // streams take turns): 176-177 vs 180 us per step.  "In flight" = the second stream was selected
                 // within the last few heavy launches (tn_stream_select); TN_PAIR_LDS_PAD=n forces a pad for an A/B.
-                static int pad = -2;
-                if (pad == -2) {
-                    const char* e = getenv("TN_PAIR_LDS_PAD");
-                    pad = e ? atoi(e) : -1;
-                }
+                const int pad = tn_knob(TN_K_PAIR_LDS_PAD);
                 if (pad >= 0)
                     rlds += (size_t)pad;
                 else if (ctx->heavy_since_side < 3) {

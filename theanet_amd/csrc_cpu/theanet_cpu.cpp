@@ -30,6 +30,7 @@
 #include <omp.h>
 
 #include "../../include/theanet_hip.h"
+#include "../csrc/knobs.h"
 
 struct tn_ctx {
     char err[512] = {0};
@@ -148,6 +149,7 @@ extern "C" {
 
 // ================================== lifecycle / memory ==================================
 int tn_version(void) { return 100; }
+int tn_knobs(char* buf, int len) { return tn_knobs_format(buf, len); }
 int tn_device_count(int* count) { if (count) *count = 1; return TN_OK; }
 int tn_ctx_create(int device, tn_ctx** out) {
     if (!out) return fail(nullptr, TN_E_ARG, "tn_ctx_create: out is NULL");

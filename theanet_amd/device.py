@@ -114,6 +114,12 @@ class Context:
             self.call("tn_set_fc_matmul", 1 if mode == "bf16x3" else 0)
             self._fc_mm = mode
 
+    def knobs(self):
+        """The library's environment switches that data-parallel ranks must agree on, as resolved (tn_knobs): name -> int."""
+        buf = ctypes.create_string_buffer(4096)
+        _lib.check(None, self.lib.tn_knobs(buf, len(buf)), "tn_knobs")
+        return {k: int(v) for k, v in (kv.split("=") for kv in buf.value.decode().split())}
+
     def info(self):
         name = ctypes.create_string_buffer(128)
         cus = ctypes.c_int()

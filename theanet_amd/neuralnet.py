@@ -109,8 +109,8 @@ class NeuralNet():
 
         self.ctx = get_context()             # raises without libtheanet_hip.so / a GPU
         # the SoftmaxLayer's training step as one kernel (tn_fc_softmax_train) or as its three ops: a choice of kernels
-        # (results agree to rounding, not bit for bit), read once per net
-        self._softmax_train = os.environ.get("TN_SOFTMAX_TRAIN", "1") != "0"
+        # (results agree to rounding, not bit for bit) -- the library's TN_SOFTMAX_TRAIN, which gemm.hip reads too
+        self._softmax_train = self.ctx.knobs()["TN_SOFTMAX_TRAIN"] != 0
         # DTYPE: 'float32' (default = the reference's floatX, weights.py:8), 'float16' = fp16 operands /
         # fp32 accumulation for the conv products, fp32 master weights, or 'bfloat16' = the same with bf16 (fp32's
         # exponent range); GRAD_SCALE: power of two applied to dz before it is rounded to the 16-bit type (results are
@@ -388,14 +388,13 @@ class NeuralNet():
                 chk = float(sum(np.float64(w.astype(np.float64).sum()) for l in self.tr_layers for w in l.get_wts()))
                 comm.agree(chk, "the initial weights (checksum)")
                 # The ORDER in which partial sums are added is part of a gradient's bits, and replicas must stay
-                # bit-identical: the process-static knobs that set slab counts / kernel forms and the CU count the slab
-                # geometry is cut for must be the same on every rank (a rank with another TN_C8_WSLAB_DIV or another
-                # device would round differently, silently)
+                # bit-identical: the library's switches that set slab counts / kernel forms (as it resolved them), the
+                # Python-side ones that pick kernels and the CU count the slab geometry is cut for must be the same on
+                # every rank (a rank with another TN_C8_WSLAB_DIV or another device would round differently, silently)
                 import zlib
-                knobs = ("TN_C8_WSLAB_DIV", "TN_C8_ROLL", "TN_FC8_WSLABS", "TN_FC_WSPLIT", "TN_FC_DGRAD_SPLIT", "TN_GEMM_DEEP",
-                         "TN_GEMM_DMA", "TN_GEMM_DMA_NS", "TN_PAIR_DMA", "TN_CONVPOOL_KS", "TN_SOFTMAX_TRAIN", "TN_FC_SKINNY",
-                         "TN_CB_W44", "TN_POOL_MASK", "TN_ELASTIC_CONV", "TN_MN_FUSED", "TN_FC8_FIN", "TN_FC8_XCD")
-                sig = "|".join("%s=%s" % (k, os.environ.get(k, "")) for k in knobs) + "|cus=%s" % self.ctx.info()[1]
+                sig = "|".join("%s=%s" % kv for kv in self.ctx.knobs().items())
+                sig += "".join("|%s=%s" % (k, os.environ.get(k, "")) for k in ("TN_POOL_MASK", "TN_MN_FUSED"))
+                sig += "|cus=%s" % self.ctx.info()[1]
                 comm.agree(float(zlib.crc32(sig.encode())), "the kernel tunables / CU count (%s)" % sig)
         # Optional overlap of the gradient all-reduce with the backward pass (TN_DP_OVERLAP=1): the
         # fully-connected layers sit on top of the net and hold almost all parameters; their gradients
