@@ -250,6 +250,20 @@ int tn_c8_unpack(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, f
 int tn_c8_mean_fwd(tn_ctx* ctx, const void* x, float* y, int N, int C, int H, int W);
 int tn_c8_mean_bwd(tn_ctx* ctx, const float* dy, void* dx, int N, int C, int H, int W, const void* b_out, int b_act,
                    float b_prm);
+/* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
+ * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
+ * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on
+ * their output; tn_c8_conv_plan_pitch reports that whole sequence (theanet_amd/csrc/conv_c8.hip).
+ * pack_pitch: NCHW fp32 (N, C, S, S) rows row0.. -> c8 of pitch P, values times scale, pad and channels past C zero.
+ * pad_zero: clears the pad cells of x (S == P: nothing).  crop: padded -> dense (N, ceil(C/8), S, S, 8), the layout
+ * tn_c8_fc_* / tn_c8_mean_* read; embed: dense -> padded, pad zero.
+ * plan_pitch: S == P: tn_c8_conv_plan's answer; S < P (8 <= P <= 64, pool: S even): tn_c8_conv_plan(op, N, C, P, P, ...)
+ * followed by one more value, 1 (the output's pad cleared after op 0 / 1); TN_E_ARG otherwise.                      */
+int tn_c8_pack_pitch(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int S, int P, float scale);
+int tn_c8_pad_zero(tn_ctx* ctx, void* x, int N, int C, int S, int P);
+int tn_c8_crop(tn_ctx* ctx, const void* x, void* out, int N, int C, int S, int P);
+int tn_c8_embed(tn_ctx* ctx, const void* x, void* out, int N, int C, int S, int P);
+int tn_c8_conv_plan_pitch(int op, int N, int C, int S, int P, int K, int pool, int act, float prm, int* out, int nout);
 
 /* 1 if tn_conv2d_* run this shape on the implicit-im2col fp32-MFMA kernels (stride 1, reduction
  * C*f*f >= 32, >= 16 output maps); otherwise the direct VALU kernels are used.              */

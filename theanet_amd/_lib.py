@@ -101,6 +101,11 @@ SIGNATURES = {
     "tn_c8_unpack": (c_int, [CTX, P, P, c_int, c_int, c_int, c_float]),
     "tn_c8_mean_fwd": (c_int, [CTX, P, P] + [c_int] * 4),
     "tn_c8_mean_bwd": (c_int, [CTX, P, P] + [c_int] * 4 + [P, c_int, c_float]),
+    "tn_c8_pack_pitch": (c_int, [CTX, P, c_int64, P] + [c_int] * 4 + [c_float]),
+    "tn_c8_pad_zero": (c_int, [CTX, P] + [c_int] * 4),
+    "tn_c8_crop": (c_int, [CTX, P, P] + [c_int] * 4),
+    "tn_c8_embed": (c_int, [CTX, P, P] + [c_int] * 4),
+    "tn_c8_conv_plan_pitch": (c_int, [c_int] * 8 + [c_float, POINTER(c_int), c_int]),
     "tn_pool_fwd": (c_int, [CTX, P, P] + [c_int] * 6),
     "tn_pool_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 6 + [c_int, c_float]),
     "tn_mean_fwd": (c_int, [CTX, P, P, c_int, c_int]),

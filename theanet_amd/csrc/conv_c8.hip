@@ -1986,6 +1986,81 @@ __global__ __launch_bounds__(256) void c8_unpack_kernel(const typename E::T* __r
         make_float4(scale * (float)(src[0]), scale * (float)(src[8]), scale * (float)(src[16]), scale * (float)(src[24]));
 }
 
+// ---- padded pitch: maps of S x S pixels stored at a power-of-two side P > S ------------------------------------
+// Rows and columns S..P-1 of every octet plane are zero, so the 'same' 3x3 products above, run on the P x P shape, read
+// zeros exactly where the logical products read their padding: forward, input gradient and weight gradient (with the
+// bias sum) of every logical pixel are the logical results.  The conv kernels themselves do not know S: a forward or
+// input gradient on a padded tensor is followed by c8_pad_zero_kernel on its output (the pad cells the epilogue wrote
+// hold act(bias) / products into the pad).  One thread = one cell; the cell kernels move 16-byte cells and do not
+// depend on the element type, the pack converts.
+// physical cell (n, o, r, c) of a (N, C8, P, P) tensor, pitch l2P = log2 P
+__device__ __forceinline__ void c8p_cell(size_t i, int l2P, size_t& pl, int& r, int& c) {
+    c = (int)(i & ((1u << l2P) - 1));
+    r = (int)((i >> l2P) & ((1u << l2P) - 1));
+    pl = i >> (2 * l2P);
+}
+template <typename E>
+__global__ __launch_bounds__(256) void c8_pack_pitch_kernel(const float* __restrict__ x, typename E::T* __restrict__ out, int C,
+                                                           int C8, int S, int l2P, size_t cells, float scale) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    size_t pl;
+    int r, c;
+    c8p_cell(i, l2P, pl, r, c);
+    const int o = (int)(pl % C8);
+    const size_t n = pl / C8;
+    const bool in = r < S && c < S;
+    typename E::v8 h;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int ch = o * 8 + e;
+        h[e] = (typename E::T)(in && ch < C ? scale * x[((n * C + ch) * S + r) * S + c] : 0.f);
+    }
+    reinterpret_cast<typename E::v8*>(out)[i] = h;
+}
+#ifndef C8_BF16_TU
+// (type-blind: compiled once, in the fp16 unit)
+// pad cells of a padded tensor: per plane, the S rows' columns S..P-1 first, then rows S..P-1 whole
+__global__ __launch_bounds__(256) void c8_pad_zero_kernel(uint4* __restrict__ x, int S, int P, size_t cells) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    const int per = P * P - S * S, side = S * (P - S);
+    const size_t pl = i / per;
+    const int q = (int)(i - pl * per);
+    const int r = q < side ? q / (P - S) : S + (q - side) / P;
+    const int c = q < side ? S + q % (P - S) : (q - side) % P;
+    x[(pl * P + r) * P + c] = make_uint4(0u, 0u, 0u, 0u);
+}
+// padded (N, C8, P, P) -> dense (N, C8, S, S): the layout tn_c8_fc_* / tn_c8_mean_* read
+__global__ __launch_bounds__(256) void c8_crop_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int S, int P,
+                                                      size_t cells) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    const int c = (int)(i % S);
+    const size_t rr = i / S;
+    const int r = (int)(rr % S);
+    const size_t pl = rr / S;
+    out[i] = x[(pl * P + r) * P + c];
+}
+// dense (N, C8, S, S) -> padded (N, C8, P, P), pad cells zero
+__global__ __launch_bounds__(256) void c8_embed_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int S, int l2P,
+                                                       size_t cells) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    size_t pl;
+    int r, c;
+    c8p_cell(i, l2P, pl, r, c);
+    out[i] = r < S && c < S ? x[(pl * S + r) * S + c] : make_uint4(0u, 0u, 0u, 0u);
+}
+#endif
+
+// the pitch a padded tensor of side S may have: a power of two P with S <= P <= 64 and P >= 8 (what every conv kernel
+// takes), log2 P; -1 otherwise
+static int c8_pitch_log2(int S, int P) {
+    if (S < 1 || S > P || P < 4 || P > 64 || (P & (P - 1))) return -1;
+    return c8w_log2(P);
+}
+
 extern "C" {
 
 #ifndef C8_BF16_TU
@@ -1999,6 +2074,7 @@ int c8b_tn_c8_conv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, 
                          int K, int pooled, const uint8_t* mask);
 int c8b_tn_c8_pack(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int HW, float scale);
 int c8b_tn_c8_unpack(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, float scale);
+int c8b_tn_c8_pack_pitch(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int S, int P, float scale);
 #endif
 
 // 1 if the c8 kernels take a 3x3 'same' stride-1 layer of this shape (forward, both gradients)
@@ -2162,5 +2238,67 @@ int C8_API(tn_c8_unpack)(tn_ctx* ctx, const void* x, float* out, int N, int C, i
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
+
+// (N, C, S, S) fp32 rows row0.. of x -> c8 tensor of pitch P (values times scale); pad cells and channels beyond C zero
+int C8_API(tn_c8_pack_pitch)(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int S, int P, float scale) {
+    C8_TO_BF16(tn_c8_pack_pitch, ctx, x, row0, out, N, C, S, P, scale);
+    const int l2P = c8_pitch_log2(S, P);
+    TN_REQUIRE(l2P >= 0, "tn_c8_pack_pitch: maps of %d pixels at pitch %d", S, P);
+    const int C8 = (C + 7) / 8;
+    const size_t cells = (size_t)N * C8 * P * P;
+    if (!cells) return TN_OK;
+    c8_pack_pitch_kernel<C8E><<<(unsigned)cdiv(cells, 256), 256, 0, ctx->stream>>>(
+        x + (size_t)row0 * C * S * S, static_cast<typename C8E::T*>(out), C, C8, S, l2P, cells, scale);
+    TN_LAUNCH_CHECK();
+    return TN_OK;
+}
+
+#ifndef C8_BF16_TU
+// zero the pad cells (rows and columns S..P-1) of a c8 tensor of C channels, pitch P; S == P: nothing to do
+int tn_c8_pad_zero(tn_ctx* ctx, void* x, int N, int C, int S, int P) {
+    TN_REQUIRE(c8_pitch_log2(S, P) >= 0, "tn_c8_pad_zero: maps of %d pixels at pitch %d", S, P);
+    const size_t cells = (size_t)N * ((C + 7) / 8) * (P * P - S * S);
+    if (!cells) return TN_OK;
+    c8_pad_zero_kernel<<<(unsigned)cdiv(cells, 256), 256, 0, ctx->stream>>>(static_cast<uint4*>(x), S, P, cells);
+    TN_LAUNCH_CHECK();
+    return TN_OK;
+}
+// padded c8 (N, C8, P, P, 8) -> dense c8 (N, C8, S, S, 8)
+int tn_c8_crop(tn_ctx* ctx, const void* x, void* out, int N, int C, int S, int P) {
+    TN_REQUIRE(c8_pitch_log2(S, P) >= 0, "tn_c8_crop: maps of %d pixels at pitch %d", S, P);
+    const size_t cells = (size_t)N * ((C + 7) / 8) * S * S;
+    if (!cells) return TN_OK;
+    c8_crop_kernel<<<(unsigned)cdiv(cells, 256), 256, 0, ctx->stream>>>(static_cast<const uint4*>(x), static_cast<uint4*>(out),
+                                                                        S, P, cells);
+    TN_LAUNCH_CHECK();
+    return TN_OK;
+}
+// dense c8 (N, C8, S, S, 8) -> padded c8 (N, C8, P, P, 8), pad cells zero
+int tn_c8_embed(tn_ctx* ctx, const void* x, void* out, int N, int C, int S, int P) {
+    const int l2P = c8_pitch_log2(S, P);
+    TN_REQUIRE(l2P >= 0, "tn_c8_embed: maps of %d pixels at pitch %d", S, P);
+    const size_t cells = (size_t)N * ((C + 7) / 8) * P * P;
+    if (!cells) return TN_OK;
+    c8_embed_kernel<<<(unsigned)cdiv(cells, 256), 256, 0, ctx->stream>>>(static_cast<const uint4*>(x), static_cast<uint4*>(out),
+                                                                         S, l2P, cells);
+    TN_LAUNCH_CHECK();
+    return TN_OK;
+}
+
+// tn_c8_conv_plan for a layer of S x S maps stored at pitch P.  S == P: exactly tn_c8_conv_plan's answer.  S < P: the
+// same kernel on the P x P shape (tn_c8_conv_plan(op, N, C, P, P, ...)) followed by one more value, 1: the output's pad
+// is cleared after the forward / input gradient (tn_c8_pad_zero; the weight gradient needs nothing: its inputs' pads are
+// zero).  S < P needs 8 <= P <= 64 and, with pool, an even S.
+int tn_c8_conv_plan_pitch(int op, int N, int C, int S, int P, int K, int pool, int act, float prm, int* out, int nout) {
+    if (S == P) return tn_c8_conv_plan(op, N, C, P, P, K, pool, act, prm, out, nout);
+    if (c8_pitch_log2(S, P) < 0 || P < 8 || (pool && (S & 1))) return TN_E_ARG;
+    int v[16];
+    const int n = tn_c8_conv_plan(op, N, C, P, P, K, pool, act, prm, v, 15);
+    if (n <= 0) return n;
+    v[n] = 1;
+    for (int i = 0; i <= n && i < nout; ++i) out[i] = v[i];
+    return n + 1;
+}
+#endif
 
 }  // extern "C"

@@ -208,6 +208,11 @@ int tn_c8_elastic_apply(tn_ctx* ctx, const float*, int64_t, const int64_t*, void
 int tn_c8_unpack(tn_ctx* ctx, const void*, float*, int, int, int, float) { NOT_HERE("tn_c8_unpack"); }
 int tn_c8_mean_fwd(tn_ctx* ctx, const void*, float*, int, int, int, int) { NOT_HERE("tn_c8_mean_fwd"); }
 int tn_c8_mean_bwd(tn_ctx* ctx, const float*, void*, int, int, int, int, const void*, int, float) { NOT_HERE("tn_c8_mean_bwd"); }
+int tn_c8_pack_pitch(tn_ctx* ctx, const float*, int64_t, void*, int, int, int, int, float) { NOT_HERE("tn_c8_pack_pitch"); }
+int tn_c8_pad_zero(tn_ctx* ctx, void*, int, int, int, int) { NOT_HERE("tn_c8_pad_zero"); }
+int tn_c8_crop(tn_ctx* ctx, const void*, void*, int, int, int, int) { NOT_HERE("tn_c8_crop"); }
+int tn_c8_embed(tn_ctx* ctx, const void*, void*, int, int, int, int) { NOT_HERE("tn_c8_embed"); }
+int tn_c8_conv_plan_pitch(int, int, int, int, int, int, int, int, float, int*, int) { return TN_E_ARG; }
 
 int tn_alloc(tn_ctx* ctx, size_t bytes, void** dptr) {
     void* p = nullptr;

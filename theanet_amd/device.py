@@ -237,30 +237,52 @@ def bf16_value(bits):
     return (np.asarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
+def c8_pitch(side):
+    """The stored side of a c8 tensor entering the 16-bit conv stack with maps of ``side`` pixels: the smallest power
+    of two >= max(side, 8) (theanet_amd/csrc/conv_c8.hip, "padded pitch")."""
+    p = 8
+    while p < side:
+        p *= 2
+    return p
+
+
 class C8Array(DeviceArray):
     """A 16-bit-RESIDENT activation / gradient tensor (DTYPE 'float16' / 'bfloat16'): logical (N, C, H, W), stored
-    [N][ceil(C/8)][H][W][8] halfs or bf16 -- one 16-byte cell = the 8 channels of an octet at one pixel, channels beyond
-    C zero (theanet_amd/csrc/conv_c8.hip).  ``elem`` is the element type ('float16' / 'bfloat16'; default: the
-    context's current DTYPE, halfs unless it is 'bfloat16').  ``get_value`` returns the logical NCHW float32 array."""
+    [N][ceil(C/8)][P][P][8] halfs or bf16 -- one 16-byte cell = the 8 channels of an octet at one pixel, channels beyond
+    C zero (theanet_amd/csrc/conv_c8.hip).  ``pitch`` P (default H: dense) is the stored side; P > H pads every plane
+    with rows and columns H..P-1 that are always zero (allocated zeroed, kept zero by every op that writes the tensor).
+    ``elem`` is the element type ('float16' / 'bfloat16'; default: the context's current DTYPE, halfs unless it is
+    'bfloat16').  ``get_value`` / ``set_value`` work on the logical NCHW float32 array."""
 
-    def __init__(self, ctx, n, c, h, w, elem=None):
+    def __init__(self, ctx, n, c, h, w, elem=None, pitch=None):
         self.c8 = (int(c), int(h), int(w))
+        self.pitch = int(pitch or h)
+        assert self.pitch >= h and (self.pitch == h or h == w), (h, w, self.pitch)
         self.elem = elem or ("bfloat16" if getattr(ctx, "mm_dtype", None) == "bfloat16" else "float16")
         assert self.elem in C8_DTYPES, self.elem
-        super().__init__(ctx, (n, (c + 7) // 8, h, w, 8), np.uint16)
+        pw = self.pitch if self.padded else w
+        super().__init__(ctx, (n, (c + 7) // 8, self.pitch, pw, 8), np.uint16)
+        if self.padded:
+            self.fill_bytes(0)
+
+    @property
+    def padded(self):
+        return self.pitch != self.c8[1]
 
     def get_value(self, borrow=True):
         raw = DeviceArray.get_value(self)
         raw = bf16_value(raw) if self.elem == "bfloat16" else raw.view(np.float16)
         n, c8, h, w, _ = raw.shape
-        return raw.transpose(0, 1, 4, 2, 3).reshape(n, c8 * 8, h, w)[:, :self.c8[0]].astype(np.float32)
+        c, hl, wl = self.c8
+        return raw.transpose(0, 1, 4, 2, 3).reshape(n, c8 * 8, h, w)[:, :c, :hl, :wl].astype(np.float32)
 
     def set_value(self, data):
         data = np.asarray(data, np.float32)
         n, c, h, w = data.shape
-        buf = np.zeros((n, self.shape[1] * 8, h, w), np.uint16)
-        buf[:, :c] = bf16_bits(data) if self.elem == "bfloat16" else data.astype(np.float16).view(np.uint16)
-        DeviceArray.set_value(self, np.ascontiguousarray(buf.reshape(n, self.shape[1], 8, h, w).transpose(0, 1, 3, 4, 2)))
+        _, c8, ph, pw, _ = self.shape
+        buf = np.zeros((n, c8 * 8, ph, pw), np.uint16)
+        buf[:, :c, :h, :w] = bf16_bits(data) if self.elem == "bfloat16" else data.astype(np.float16).view(np.uint16)
+        DeviceArray.set_value(self, np.ascontiguousarray(buf.reshape(n, c8, 8, ph, pw).transpose(0, 1, 3, 4, 2)))
 
 
 class HostBuffer:

@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from .. import _lib
-from ..device import C8_DTYPES, C8Array
+from ..device import C8_DTYPES, C8Array, c8_pitch
 from .layer import Layer, activation_by_name
 from .weights import init_wb
 
@@ -60,16 +60,22 @@ class ConvLayer(Layer):
         self.filter_sz, self.stride = filter_sz, stride
         if self.f16:
             lib = self.ctx.lib
-            ok = lib.tn_c8_conv_supported(batch_sz, num_prev_maps, in_sz, in_sz, num_maps, filter_sz, stride, self.pad_lo) and \
-                lib.tn_c8_conv_wgrad_supported(batch_sz, num_prev_maps, in_sz, in_sz, num_maps)
+            # maps of S pixels a side are stored at a pitch P: the input's, or -- first conv layer -- the smallest power of
+            # two >= max(S, 8).  The kernels run on the P x P shape; S < P pads every plane with zero rows and columns
+            # (device.C8Array), which the 'same' products read as their padding.
+            self.pitch = inpt.pitch if getattr(inpt, "c8", None) else c8_pitch(in_sz)
+            P = self.pitch
+            ok = (in_sz == P or in_sz <= 64) and P >= 8 and \
+                lib.tn_c8_conv_supported(batch_sz, num_prev_maps, P, P, num_maps, filter_sz, stride, self.pad_lo) and \
+                lib.tn_c8_conv_wgrad_supported(batch_sz, num_prev_maps, P, P, num_maps)
             assert ok and mode == 'same', (
-                "DTYPE {} needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of 8, 16, 32 "
-                "or 64 pixels a side (got {}->{} maps, {}x{} {} filter {} stride {})".format(
-                    self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, mode, filter_sz, stride))
+                "DTYPE {} needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of at most 64 "
+                "pixels a side, stored at a pitch of at least 8 (got {}->{} maps, {}x{} at pitch {}, {} filter {} "
+                "stride {})".format(self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, P, mode, filter_sz, stride))
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
             self.x16 = None if getattr(inpt, "c8", None) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz,
-                                                                      self.c8_dtype)
-            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, self.c8_dtype)
+                                                                      self.c8_dtype, pitch=P)
+            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, self.c8_dtype, pitch=P)
             # the weights as MFMA operand tiles (forward / input gradient): the net arranges every layer's in one launch
             # per step (NeuralNet._c8_arrange) and marks them valid until the next update; otherwise the ops do it per call
             self.wt_fwd = self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16)
@@ -157,15 +163,25 @@ class ConvLayer(Layer):
         slot = getattr(self, "_pack_from", None)
         if slot is not None:
             src, row0 = slot.data, int(slot.row0)
-        self.ctx.call("tn_c8_pack", src.ptr, row0, self.x16.ptr, self.batch_sz, self.num_prev_maps,
-                      self.in_sz * self.in_sz, 1.0)
+        if self.x16.padded:
+            self.ctx.call("tn_c8_pack_pitch", src.ptr, row0, self.x16.ptr, self.batch_sz, self.num_prev_maps, self.in_sz,
+                          self.pitch, 1.0)
+        else:
+            self.ctx.call("tn_c8_pack", src.ptr, row0, self.x16.ptr, self.batch_sz, self.num_prev_maps,
+                          self.in_sz * self.in_sz, 1.0)
         return self.x16
+
+    def _c8_pad_zero(self, t):
+        """After a product that wrote a padded tensor: its pad cells back to zero (tn_c8_pad_zero)."""
+        if t.padded:
+            self.ctx.call("tn_c8_pad_zero", t.ptr, self.batch_sz, t.c8[0], t.c8[1], t.pitch)
 
     def _c8_forward(self, out, mask):
         x = self._c8_input()
         self.ctx.call("tn_c8_conv_fwd", x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None,
-                      self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps, self.act.kind, self.act.prm,
+                      self.batch_sz, self.num_prev_maps, self.pitch, self.pitch, self.num_maps, self.act.kind, self.act.prm,
                       1 if out is not self.output else 0, self.wt_fwd.ptr if self.wt_valid else None)
+        self._c8_pad_zero(out)
 
     def _c8_backward(self, gout, need_gin, below):
         """gout: d cost / d z of this layer as a c8 tensor carrying the gradient scale -- or, for a fused block, the
@@ -174,19 +190,21 @@ class ConvLayer(Layer):
         pool = self.fused_pool
         pooled, mask = (1, pool.mask.ptr) if pool is not None else (0, None)
         x = self.x16 if self.x16 is not None else self.inpt
-        geom = (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps)
+        geom = (self.batch_sz, self.num_prev_maps, self.pitch, self.pitch, self.num_maps)
         if self.has_updates():
             self.ctx.call("tn_c8_conv_wgrad", x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *geom, pooled, mask)
         if not need_gin:
             return None
         assert self.x16 is None, "DTYPE {}: no trainable layer below the first conv layer".format(self.c8_dtype)
         if self.gin is None:
-            self.gin = C8Array(self.ctx, self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.c8_dtype)
+            self.gin = C8Array(self.ctx, self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.c8_dtype,
+                               pitch=self.pitch)
         b_out, b_act, b_prm, b_mask = below.act_info()
         assert b_mask is None
         fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
         self.ctx.call("tn_c8_conv_dgrad", gout.ptr, self.W.ptr, self.gin.ptr, *geom, b_out.ptr if fuse else None,
                       b_act, b_prm, pooled, mask, self.wt_bwd.ptr if self.wt_valid and self.wt_bwd is not None else None)
+        self._c8_pad_zero(self.gin)
         return self.gin
 
     def forward(self, train=True):
@@ -305,7 +323,8 @@ class PoolLayer(Layer):
         self.batch_sz = inpt.shape[0]
         self.f16 = getattr(inpt, "c8", None) is not None      # DTYPE float16: pooled c8 tensor (only as a fused block)
         if self.f16:
-            self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem)
+            self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem,
+                                  pitch=inpt.pitch // 2 if inpt.padded else None)
         else:
             self.output = self.ctx.empty((self.batch_sz, num_maps, self.out_sz, self.out_sz))
         self.gin = None
@@ -389,6 +408,9 @@ class MeanLayer(Layer):
         # DTYPE float16 / bfloat16: the input is the 16-bit-resident c8 tensor of the conv stack (tn_c8_mean_*); the
         # output stays the fp32 (N, C) matrix the dense layers above take
         self.f16 = getattr(inpt, "c8", None) is not None
+        # ... a padded one (S < pitch) is cropped to a dense tensor first (tn_c8_crop), the gradient embedded back
+        self.dense = C8Array(self.ctx, self.batch_sz, num_maps, in_sz, in_sz, inpt.elem) \
+            if self.f16 and inpt.padded else None
         self.output = self.ctx.empty((self.batch_sz, num_maps))
         self.gin = None
         self.representation = (
@@ -400,7 +422,12 @@ class MeanLayer(Layer):
 
     def forward(self, train=True):
         if self.f16:
-            self.ctx.call("tn_c8_mean_fwd", self.inpt.ptr, self.output.ptr, self.batch_sz, self.num_maps,
+            x = self.inpt
+            if self.dense is not None:
+                x = self.dense
+                self.ctx.call("tn_c8_crop", self.inpt.ptr, x.ptr, self.batch_sz, self.num_maps, self.in_sz,
+                              self.inpt.pitch)
+            self.ctx.call("tn_c8_mean_fwd", x.ptr, self.output.ptr, self.batch_sz, self.num_maps,
                           self.in_sz, self.in_sz)
             return
         self.ctx.call("tn_mean_fwd", self.inpt.ptr, self.output.ptr,
@@ -410,12 +437,21 @@ class MeanLayer(Layer):
         """The c8 gradient of the block below (an unpooled ConvLayer, or a fused 2x2 PoolLayer standing for its block):
         grad_scale * gout / (H W) * act'(its stored output), rounded when stored."""
         if self.gin is None:
-            self.gin = C8Array(self.ctx, self.batch_sz, self.num_maps, self.in_sz, self.in_sz, self.inpt.elem)
+            self.gin = C8Array(self.ctx, self.batch_sz, self.num_maps, self.in_sz, self.in_sz, self.inpt.elem,
+                               pitch=self.inpt.pitch)
+            self._gin_dense = self.gin if self.dense is None else \
+                C8Array(self.ctx, self.batch_sz, self.num_maps, self.in_sz, self.in_sz, self.inpt.elem)
         b_out, b_act, b_prm, b_mask = below.act_info()
         assert b_mask is None
         fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-        self.ctx.call("tn_c8_mean_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps, self.in_sz, self.in_sz,
-                      b_out.ptr if fuse else None, b_act, b_prm)
+        if fuse and self.dense is not None:
+            assert b_out is self.inpt
+            b_out = self.dense                  # act' from the cropped copy of the block's output (same values)
+        self.ctx.call("tn_c8_mean_bwd", gout.ptr, self._gin_dense.ptr, self.batch_sz, self.num_maps, self.in_sz,
+                      self.in_sz, b_out.ptr if fuse else None, b_act, b_prm)
+        if self.dense is not None:
+            self.ctx.call("tn_c8_embed", self._gin_dense.ptr, self.gin.ptr, self.batch_sz, self.num_maps, self.in_sz,
+                          self.gin.pitch)
         return self.gin
 
     def backward(self, gout, need_gin, below):

@@ -43,6 +43,11 @@ class HiddenLayer(Layer):
                 "DTYPE {}: a dense layer on {} maps of {}x{} needs a multiple of 64 inputs (c8) and of 32 outputs "
                 "(got {})".format(inpt.elem, c, h, wd, n_out))
             self.inpt = inpt
+            # a padded stack tensor (maps stored at a pitch > their side): the products read a dense copy, cropped in
+            # front of them (tn_c8_crop); the input gradient is embedded back into the padded layout (tn_c8_embed)
+            self.c8_src = inpt if inpt.padded else None
+            if self.c8_src is not None:
+                self.inpt = C8Array(self.ctx, inpt.shape[0], c, h, wd, inpt.elem)
         else:
             self.inpt = inpt.flatten(2)
             assert self.inpt.shape[1] == n_in, (self.inpt.shape, n_in)
@@ -85,6 +90,8 @@ class HiddenLayer(Layer):
         drop = self.drop
         if self.c8 is not None:
             c, h, wd = self.c8
+            if self.c8_src is not None:
+                self.ctx.call("tn_c8_crop", self.c8_src.ptr, self.inpt.ptr, self.batch_sz, c, h, self.c8_src.pitch)
             if drop is not None and not drop.injected and not drop.ready:
                 # the mask is drawn by the product's finishing kernel (and kept for the backward pass)
                 self.ctx.call("tn_c8_fc_fwd_dropout", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz,
@@ -120,14 +127,23 @@ class HiddenLayer(Layer):
                               self.batch_sz, c, h * wd, self.n_out)
             if not need_gin:
                 return None
+            src = self.c8_src
             if self.gin is None:
                 self.gin = C8Array(self.ctx, self.batch_sz, c, h, wd, self.inpt.elem)
+                self._gin_padded = None if src is None else \
+                    C8Array(self.ctx, self.batch_sz, c, h, wd, self.inpt.elem, pitch=src.pitch)
             b_out, b_act, b_prm, b_mask = below.act_info()
             assert b_mask is None
             fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
+            if fuse and src is not None:
+                assert b_out is src
+                b_out = self.inpt                   # act' from the cropped copy of the block's output (same values)
             self.ctx.call("tn_c8_fc_dgrad", gout.ptr, self.w.ptr, self.gin.ptr, self.batch_sz, c, h * wd, self.n_out,
                           b_out.ptr if fuse else None, b_act, b_prm)
-            return self.gin
+            if src is None:
+                return self.gin
+            self.ctx.call("tn_c8_embed", self.gin.ptr, self._gin_padded.ptr, self.batch_sz, c, h, src.pitch)
+            return self._gin_padded
         if self.has_updates() and need_gin:
             # weight gradient and input gradient only share dz: one op, one launch
             if self.wgrad_ws is None:
