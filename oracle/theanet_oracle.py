@@ -417,6 +417,31 @@ def centered_head(v, centers, y, kind, junk_dist=np.inf):
     return lp, p.argmax(1), p[r, y], -lp[r, y].mean(), dv, dc
 
 
+def head_rowloss(head, a, y, loss="nll", centers=None, junk_dist=np.inf):
+    """The per-sample loss of the heads above: their cost is ``head_rowloss(...).mean()``.  head: 'softmax' (with
+    ``loss``), 'exploss', 'hinge', 'LOGIT' or 'RBF' (a = the hidden features, with ``centers``)."""
+    r = np.arange(len(y))
+    if head == "softmax":
+        lp = log_softmax(a)
+        p = np.exp(lp)
+        name, thr = parse_loss(loss)
+        if name == "nll":
+            return -lp[r, y]
+        if name == "nllsq":
+            return lp[r, y] ** 2
+        if name == "nlltrunc":
+            with np.errstate(divide="ignore"):
+                return np.maximum(0, np.log(thr) - lp[r, y])
+        if name == "hinge":
+            return np.maximum(0, p + 1 - p[r, y][:, None]).mean(1)
+        return np.exp(-p[r, y])
+    if head == "exploss":
+        return np.exp(-(a - a.mean(1, keepdims=True))[r, y])
+    if head == "hinge":
+        return np.maximum(0, a + 1 - a[r, y][:, None]).mean(1)
+    return -centered_head(a, centers, y, head, junk_dist)[0][r, y]
+
+
 # --------------------------------------------------------------------------- #
 # update  (layer.py:70-117)
 # --------------------------------------------------------------------------- #
@@ -616,34 +641,45 @@ class ElasticStage:
 # --------------------------------------------------------------------------- #
 
 
-def elastic_apply_bwd(g, target, nearest, flipmask=None, invert=False):
-    """Gradient of ``elastic_apply(1 - x if invert else x, ...)`` w.r.t. x (Theano's grad through the
-    advanced-indexing gather = scatter-add, inlayers.py:126-142, :63-64)."""
-    N, C, h, w = g.shape
+def elastic_scatter(g, i00, fy, fx, w, flipmask=None, invert=False):
+    """Scatter-add of g (N, C, h, w) along explicit sample maps over the h*w output pixels: ``i00`` the flat index of
+    the (top-left) source pixel (None: identity), ``fy`` / ``fx`` the bilinear fractions (None: nearest neighbour,
+    the whole of g goes to i00).  The flip and the inversion negate the gradient."""
+    N, C, h, _ = g.shape
     g = np.asarray(g, np.float64)
     if flipmask is not None:
         g = g * (1 - 2 * np.asarray(flipmask, np.float64))          # d/dout [(1-out) m + out (1-m)]
     dx = np.zeros((N, C, h * w))
     gf = g.reshape(N, C, h * w)
-    if target is None:
+    if i00 is None:
         dx += gf
+    elif fy is None:
+        np.add.at(dx, (slice(None), slice(None), np.asarray(i00, np.int64)), gf)
     else:
-        transy = np.clip(target[0], 0, h - 1 - .001)
-        transx = np.clip(target[1], 0, w - 1 - .001)
-        if nearest:
-            idx = (np.rint(transy).astype(np.int64) * w + np.rint(transx).astype(np.int64)).reshape(-1)
-            for k, wt in ((idx, 1.0),):
-                np.add.at(dx, (slice(None), slice(None), k), gf * wt)
-        else:
-            topp, left = transy.astype(np.int64), transx.astype(np.int64)
-            fy = (transy - topp).astype(np.float32).astype(np.float64).reshape(-1)
-            fx = (transx - left).astype(np.float32).astype(np.float64).reshape(-1)
-            i00 = (topp * w + left).reshape(-1)
-            for off, wt in ((0, (1 - fy) * (1 - fx)), (1, (1 - fy) * fx), (w, fy * (1 - fx)), (w + 1, fy * fx)):
-                np.add.at(dx, (slice(None), slice(None), i00 + off), gf * wt)
+        i00 = np.asarray(i00, np.int64)
+        fy, fx = np.asarray(fy, np.float64), np.asarray(fx, np.float64)
+        for off, wt in ((0, (1 - fy) * (1 - fx)), (1, (1 - fy) * fx), (w, fy * (1 - fx)), (w + 1, fy * fx)):
+            np.add.at(dx, (slice(None), slice(None), i00 + off), gf * wt)
     if invert:
         dx = -dx
     return dx.reshape(N, C, h, w)
+
+
+def elastic_apply_bwd(g, target, nearest, flipmask=None, invert=False):
+    """Gradient of ``elastic_apply(1 - x if invert else x, ...)`` w.r.t. x (Theano's grad through the
+    advanced-indexing gather = scatter-add, inlayers.py:126-142, :63-64)."""
+    N, C, h, w = g.shape
+    if target is None:
+        return elastic_scatter(g, None, None, None, w, flipmask, invert)
+    transy = np.clip(target[0], 0, h - 1 - .001)
+    transx = np.clip(target[1], 0, w - 1 - .001)
+    if nearest:
+        idx = (np.rint(transy).astype(np.int64) * w + np.rint(transx).astype(np.int64)).reshape(-1)
+        return elastic_scatter(g, idx, None, None, w, flipmask, invert)
+    topp, left = transy.astype(np.int64), transx.astype(np.int64)
+    fy = (transy - topp).astype(np.float32).astype(np.float64).reshape(-1)
+    fx = (transx - left).astype(np.float32).astype(np.float64).reshape(-1)
+    return elastic_scatter(g, (topp * w + left).reshape(-1), fy, fx, w, flipmask, invert)
 
 
 class ColorStage:
@@ -674,6 +710,10 @@ class ColorStage:
         if u is None:
             u = self.draw(x.shape[0])
         b, g1, g2 = [f.astype(np.float32).astype(x.dtype) for f in self.factors(u)]   # .astype(float_x), :35
+        return self.apply(x, b, g1, g2)
+
+    def apply(self, x, b, g1, g2):
+        """The colour map with given factors b, g1, g2 (broadcastable to x)."""
         o1 = x / x.dtype.type(self.maxval) * b                                        # :38-39
         o2 = np.clip(o1, 0, 1)                                                        # :40
         o3 = o2 ** g1                                                                 # :41
