@@ -250,6 +250,24 @@ int tn_c8_unpack(tn_ctx* ctx, const void* x, float* out, int N, int C, int HW, f
 int tn_c8_mean_fwd(tn_ctx* ctx, const void* x, float* y, int N, int C, int H, int W);
 int tn_c8_mean_bwd(tn_ctx* ctx, const float* dy, void* dx, int N, int C, int H, int W, const void* b_out, int b_act,
                    float b_prm);
+/* DropOutLayer on a c8 tensor (replaces srng.binomial(n=1, p=1-pdrop) * output, dropout.py:10-13 and :21-26, and the test
+ * version's (1 - pdrop) * inpt, dropout.py:28-31, for a DropOut layer between the blocks of the 16-bit stack;
+ * theanet_amd/csrc/drop_c8.hip).  x, y, gout, gin: c8 tensors of N x C maps of S pixels a side stored at pitch P (P == S,
+ * or a power of two > S), either element type; mask8: one byte per 16-byte cell, N * ceil(C/8) * P * P bytes, bit k =
+ * channel 8 * octet + k of that pixel kept.
+ * fwd: y = x (.) m, a stored value or +0 (exact); pad cells and channels past C are written as 0.  draw != 0: m is drawn
+ *   in the same launch and written to mask8 -- element (n, c, h, w) is kept iff tn_dropout_mask(seed, step, d_step, elem0)
+ *   keeps element ((n C + c) S + h) S + w of the logical (N, C, S, S) tensor (dropout.py:10-12; no 1/(1-p) rescale, :13),
+ *   whatever the element type, the pitch or elem0's alignment.  draw == 0: m is read from mask8 (injected masks).
+ * bwd: gin = gout (.) m (the gradient of :13), exact; the activation derivative of the block below is NOT applied here
+ *   (the producer of gout has applied it: DropOutLayer.act_info looks through).  y may be x, gin may be gout.
+ * scale: y = R(scale * x), the product in fp32, one nearest-even rounding to the context's 16-bit type (dropout.py:28-31
+ *   with scale = 1 - pdrop).  Bad geometry, NULL tensors, pdrop outside [0, 1] or 2^32 cells: TN_E_ARG, nothing launched.
+ * No atomics: deterministic.                                                                                          */
+int tn_c8_dropout_fwd(tn_ctx* ctx, const void* x, void* y, uint8_t* mask8, int N, int C, int S, int P, float pdrop,
+                      uint64_t seed, uint32_t step, const uint32_t* d_step, uint64_t elem0, int draw);
+int tn_c8_dropout_bwd(tn_ctx* ctx, const void* gout, const uint8_t* mask8, void* gin, int N, int C, int S, int P);
+int tn_c8_scale(tn_ctx* ctx, const void* x, void* y, int N, int C, int S, int P, float scale);
 /* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
  * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
  * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on

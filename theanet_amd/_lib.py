@@ -101,6 +101,9 @@ SIGNATURES = {
     "tn_c8_unpack": (c_int, [CTX, P, P, c_int, c_int, c_int, c_float]),
     "tn_c8_mean_fwd": (c_int, [CTX, P, P] + [c_int] * 4),
     "tn_c8_mean_bwd": (c_int, [CTX, P, P] + [c_int] * 4 + [P, c_int, c_float]),
+    "tn_c8_dropout_fwd": (c_int, [CTX, P, P, P] + [c_int] * 4 + [c_float, c_uint64, c_uint32, P, c_uint64, c_int]),
+    "tn_c8_dropout_bwd": (c_int, [CTX, P, P, P] + [c_int] * 4),
+    "tn_c8_scale": (c_int, [CTX, P, P] + [c_int] * 4 + [c_float]),
     "tn_c8_pack_pitch": (c_int, [CTX, P, c_int64, P] + [c_int] * 4 + [c_float]),
     "tn_c8_pad_zero": (c_int, [CTX, P] + [c_int] * 4),
     "tn_c8_crop": (c_int, [CTX, P, P] + [c_int] * 4),

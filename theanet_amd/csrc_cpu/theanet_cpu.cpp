@@ -208,6 +208,12 @@ int tn_c8_elastic_apply(tn_ctx* ctx, const float*, int64_t, const int64_t*, void
 int tn_c8_unpack(tn_ctx* ctx, const void*, float*, int, int, int, float) { NOT_HERE("tn_c8_unpack"); }
 int tn_c8_mean_fwd(tn_ctx* ctx, const void*, float*, int, int, int, int) { NOT_HERE("tn_c8_mean_fwd"); }
 int tn_c8_mean_bwd(tn_ctx* ctx, const float*, void*, int, int, int, int, const void*, int, float) { NOT_HERE("tn_c8_mean_bwd"); }
+int tn_c8_dropout_fwd(tn_ctx* ctx, const void*, void*, uint8_t*, int, int, int, int, float, uint64_t, uint32_t, const uint32_t*,
+                      uint64_t, int) {
+    NOT_HERE("tn_c8_dropout_fwd");
+}
+int tn_c8_dropout_bwd(tn_ctx* ctx, const void*, const uint8_t*, void*, int, int, int, int) { NOT_HERE("tn_c8_dropout_bwd"); }
+int tn_c8_scale(tn_ctx* ctx, const void*, void*, int, int, int, int, float) { NOT_HERE("tn_c8_scale"); }
 int tn_c8_pack_pitch(tn_ctx* ctx, const float*, int64_t, void*, int, int, int, int, float) { NOT_HERE("tn_c8_pack_pitch"); }
 int tn_c8_pad_zero(tn_ctx* ctx, void*, int, int, int, int) { NOT_HERE("tn_c8_pad_zero"); }
 int tn_c8_crop(tn_ctx* ctx, const void*, void*, int, int, int, int) { NOT_HERE("tn_c8_crop"); }

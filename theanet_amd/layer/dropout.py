@@ -7,10 +7,18 @@ so the numpy seed chain stays in step; the mask itself comes from an on-device
 Philox4x32-10 generator keyed by (seed, step, GLOBAL element index) -- so it does
 not depend on how the batch is sharded over GPUs -- or is injected for parity
 tests (``inject_mask``).
+
+DTYPE 'float16' / 'bfloat16': a DropOutLayer between the blocks of the 16-bit-resident conv stack takes and returns
+``device.C8Array`` tensors (tn_c8_dropout_fwd / _bwd, tn_c8_scale; theanet_amd/csrc/drop_c8.hip).  The mask is the one the
+fp32 layer draws for the same seed, step and LOGICAL (N, C, S, S) shape, kept packed (a byte per 16-byte cell) and drawn
+inside the forward launch.  The backward only applies the mask: ``act_info`` looks through to the block below, so the
+producer of the incoming gradient has already applied that block's act' (from this layer's own output, which differs from
+the block's only where the mask is zero) and rounded once.
 """
 import numpy as np
 
 from .. import _lib
+from ..device import C8Array
 from .layer import Layer
 
 
@@ -46,6 +54,47 @@ class DropStream:
                       0, self.d_step.ptr if self.d_step is not None else None, self.elem0)
 
 
+class C8DropStream(DropStream):
+    """The stream of a DropOutLayer on a c8 tensor: ``shape`` is the logical (N, C, S, S) one (it keys the numbers and the
+    shard offset), ``mask`` the packed bytes (N, ceil(C/8), P, P), bit k = channel 8 * octet + k kept, pad cells 0.  The
+    draw happens inside tn_c8_dropout_fwd: nothing is generated ahead of the forward."""
+
+    def __init__(self, ctx, shape, pitch, pdrop, rand_gen=None):
+        self.ctx, self.shape, self.pdrop = ctx, tuple(shape), float(pdrop)
+        self.seed = int(rand_gen.randint(1e6)) if rand_gen is not None \
+            else int(np.random.randint(0, 1e6))
+        n, c, s, _ = self.shape
+        self.pitch = int(pitch)
+        self.mask = ctx.zeros((n, (c + 7) // 8, self.pitch, self.pitch), np.uint8)
+        self.injected = False
+        self.ready = False
+        self.d_step = None
+        self.elem0 = 0
+
+    def inject(self, mask):
+        """Parity hook: the same NCHW 0/1 host array the fp32 layer takes, packed to cell bytes.  None: back to the
+        generator."""
+        if mask is None:
+            self.injected = False
+            return
+        n, c, s, _ = self.shape
+        m = np.zeros((n, 8 * ((c + 7) // 8), self.pitch, self.pitch), np.uint8)
+        m[:, :c, :s, :s] = np.asarray(mask).reshape(self.shape) != 0
+        packed = np.packbits(m.reshape(n, -1, 8, self.pitch, self.pitch), axis=2, bitorder="little")
+        self.mask.set_value(np.ascontiguousarray(packed.reshape(self.mask.shape)))
+        self.injected = True
+
+    def unpacked(self):
+        """The mask of the last forward as the logical NCHW 0/1 array."""
+        n, c, s, _ = self.shape
+        b = np.asarray(self.mask.get_value(), np.uint8)
+        bits = np.unpackbits(b[:, :, None], axis=2, bitorder="little")          # (n, C8, 8, P, P)
+        return bits.reshape(n, -1, self.pitch, self.pitch)[:, :c, :s, :s]
+
+    def generate(self):
+        raise RuntimeError("the mask of a DropOutLayer on the 16-bit stack is drawn by its forward launch")
+
+
 def drop_output(layer, output, pdrop, rand_gen=None):
     """dropout.py:9-13 -- attaches a DropStream to ``layer`` for ``output``."""
     layer.drop = DropStream(output.ctx, output.shape, pdrop, rand_gen)
@@ -61,7 +110,14 @@ class DropOutLayer(Layer):
         self.pdrop = pdrop
         self.test_scale = 1.0
         self.drop = None
-        if pdrop:
+        # DTYPE float16 / bfloat16: a 16-bit-resident tensor of the conv stack in, one of the same geometry out
+        self.c8 = getattr(inpt, "c8", None)
+        self.below = None           # (c8) the layer below, set by the net: act_info() looks through to it
+        if pdrop and self.c8 is not None:
+            c, s, _ = self.c8
+            self.drop = C8DropStream(self.ctx, (inpt.shape[0], c, s, s), inpt.pitch, pdrop, rand_gen)
+            self.output = self._c8_like(inpt)
+        elif pdrop:
             drop_output(self, inpt, pdrop, rand_gen)
             self.output = self.ctx.empty(inpt.shape)
         else:
@@ -73,10 +129,36 @@ class DropOutLayer(Layer):
         test_version = DropOutLayer(inpt, n_in=self.n_in, pdrop=0)
         if self.pdrop:
             test_version.test_scale = 1 - self.pdrop
-            test_version.output = self.ctx.empty(inpt.shape)
+            test_version.output = self._c8_like(inpt) if test_version.c8 is not None else self.ctx.empty(inpt.shape)
         return test_version
 
+    def _c8_like(self, t):
+        c, s, _ = t.c8
+        return C8Array(self.ctx, t.shape[0], c, s, s, t.elem, pitch=t.pitch)
+
+    def _c8_geom(self):
+        c, s, _ = self.c8
+        return self.inpt.shape[0], c, s, self.inpt.pitch
+
+    def act_info(self):
+        """On the 16-bit stack the layer stands for the block below it, the way a fused PoolLayer stands for its block:
+        the producer of this layer's incoming gradient applies that block's act', taken from THIS layer's output (the
+        block's stored output where the mask keeps it; zero, and a zero gradient after the mask, elsewhere)."""
+        if self.c8 is None or self.below is None:
+            return Layer.act_info(self)
+        _, b_act, b_prm, b_mask = self.below.act_info()
+        assert b_mask is None
+        return self.output, b_act, b_prm, None
+
     def forward(self, train=True):
+        if self.c8 is not None:
+            if self.drop is not None:
+                d = self.drop
+                self.ctx.call("tn_c8_dropout_fwd", self.inpt.ptr, self.output.ptr, d.mask.ptr, *self._c8_geom(), d.pdrop,
+                              d.seed, 0, d.d_step.ptr if d.d_step is not None else None, d.elem0, 0 if d.injected else 1)
+            elif self.test_scale != 1.0:
+                self.ctx.call("tn_c8_scale", self.inpt.ptr, self.output.ptr, *self._c8_geom(), float(self.test_scale))
+            return
         if self.drop is not None:
             self.drop.generate()
             self.ctx.call("tn_scale_mask", self.inpt.ptr, self.drop.mask.ptr, 1.0,
@@ -88,6 +170,11 @@ class DropOutLayer(Layer):
     def backward(self, gout, need_gin, below):
         if not need_gin:
             return None
+        if self.c8 is not None:
+            # mask only, in place on the producer's gradient tensor: act' of the block below is already in it (act_info)
+            if self.drop is not None:
+                self.ctx.call("tn_c8_dropout_bwd", gout.ptr, self.drop.mask.ptr, gout.ptr, *self._c8_geom())
+            return gout
         b_out, b_act, b_prm, b_mask = below.act_info()
         fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
         if self.drop is None and not fuse and b_mask is None:

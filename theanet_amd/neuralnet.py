@@ -209,18 +209,22 @@ class NeuralNet():
         curr_layer_type = getattr(layer, layer_type)
 
         if curr_layer_type in (ElasticLayer, ColorLayer, ConvLayer, PoolLayer, MeanLayer):
-            if type(prev_tr_layer) is DropOutLayer:
-                use_tr_layer = self.tr_layers[self.num_layers - 2]
-            else:
-                use_tr_layer = prev_tr_layer
+            use_tr_layer, k = prev_tr_layer, self.num_layers - 1
+            while type(use_tr_layer) is DropOutLayer:
+                k -= 1
+                use_tr_layer = self.tr_layers[k]
             num_prev_maps = use_tr_layer.num_maps
             prev_out_sz = use_tr_layer.out_sz
             if getattr(tr_inpt, "c8", None) is not None:
                 # DTYPE float16 / bfloat16: 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to
-                # layer as they are; a MeanLayer closes the stack with an fp32 (N, C) output
+                # layer as they are (a DropOutLayer too: the branch below); a MeanLayer closes the stack with an fp32
+                # (N, C) output
                 assert curr_layer_type in (ConvLayer, PoolLayer, MeanLayer), \
-                    "DTYPE {}: only Conv / Pool / Mean layers take the conv stack's 16-bit-resident tensors (got {})".format(
-                        self.dtype, layer_type)
+                    "DTYPE {}: only Conv / Pool / Mean / DropOut layers take the conv stack's 16-bit-resident tensors " \
+                    "(got {})".format(self.dtype, layer_type)
+                assert not (curr_layer_type is PoolLayer and type(prev_tr_layer) is DropOutLayer), \
+                    "DTYPE {}: a DropOutLayer between a ConvLayer and its PoolLayer breaks the fused conv + pool block " \
+                    "of the 16-bit stack; put the DropOutLayer after the PoolLayer".format(self.dtype)
             elif tr_inpt.ndim != 4:
                 tr_inpt = tr_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
                 te_inpt = te_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
@@ -255,6 +259,8 @@ class NeuralNet():
                                       self.rand_gen,
                                       prev_tr_layer.n_out,
                                       **layer_args)
+            # on the 16-bit stack the layer stands for the block below it (DropOutLayer.act_info)
+            curr_layer.below = prev_tr_layer
 
         elif curr_layer_type is CenteredOutLayer:
             # Needs the hidden layer's weights (or a seed) and CENTERS (n_classes x n_features): neuralnet.py:175-194
