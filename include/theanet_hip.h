@@ -268,6 +268,31 @@ int tn_c8_dropout_fwd(tn_ctx* ctx, const void* x, void* y, uint8_t* mask8, int N
                       uint64_t seed, uint32_t step, const uint32_t* d_step, uint64_t elem0, int draw);
 int tn_c8_dropout_bwd(tn_ctx* ctx, const void* gout, const uint8_t* mask8, void* gin, int N, int C, int S, int P);
 int tn_c8_scale(tn_ctx* ctx, const void* x, void* y, int N, int C, int S, int P, float scale);
+/* 1x1 stride-1 ConvLayers on c8 tensors (replace conv2d(inpt, W) + b, the activation and -- fused -- the 2x2 max-pool of
+ * convpool.py:54-72, 106-107 with filter_sz 1, and their gradients, for a 1x1 layer on the 16-bit stack;
+ * theanet_amd/csrc/conv1_c8.hip).  Tensors: N x C (x, dx) / N x K (y, dz) maps of S pixels a side stored at pitch P (P == S,
+ * or a power of two > S) as in tn_c8_dropout_*, either element type; W (K, C, 1, 1) fp32 master weights, b (K) fp32.  C and K
+ * need not be multiples of 8: channels past C read as zero (the layout's contract), channels past K are WRITTEN as zero.
+ * Arithmetic: tn_c8_conv_fwd's -- operands rounded to the 16-bit type (nearest even), exact products, fp32 accumulation on
+ * the matrix core, bias / activation / pooling on the fp32 sums, one rounding on store.  Every op writes the pad cells of
+ * its output as zero itself (no tn_c8_pad_zero).
+ * fwd: y = act(W . x + b); pool != 0 (S even): followed by the 2x2 max-pool, y (N, K, S/2, S/2) at pitch P / 2, and mask
+ *   (NULL: none) gets tn_c8_conv_fwd's bytes (bits 0-3 window elements equal to the maximum, bit 4 / 5 pooled value > 0 /
+ *   < 0; pad cells and channels past K: 0) in y's cell order.
+ * dgrad: dx = R(W^T . dz * act'(prev_a)), pad cells and channels past C zero; prev_a as in tn_c8_conv_dgrad (the stored
+ *   output of the block below, dx's shape; NULL: no derivative).  pooled != 0: `dz` is the pooled gradient (N, K, S/2, S/2)
+ *   at pitch P / 2 and dz = (bit of the window element in the block's mask) ? pooled gradient : 0 is formed while loading.
+ * wgrad: dW (K, C), db (K) fp32, OVERWRITE, the gradient scale removed in the fp32 epilogue; db is summed from the stored dz.
+ *   Slab sums in context scratch finished by the context's reduction: no atomics, one order, the same bits every run.
+ * supported: 1 for every N, C, K >= 1 and geometry above whose tensors have fewer than 2^32 cells.  Bad geometry, NULL
+ * tensors, pool / pooled with odd S, a pooled gradient without its mask, or 2^32 cells: TN_E_ARG, nothing launched.      */
+int tn_c8_conv1_supported(int N, int C, int S, int P, int K);
+int tn_c8_conv1_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, uint8_t* mask, int N, int C, int S,
+                    int P, int K, int act, float prm, int pool);
+int tn_c8_conv1_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int S, int P, int K,
+                      const void* prev_a, int prev_act, float prev_prm, int pooled, const uint8_t* mask);
+int tn_c8_conv1_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int K,
+                      int pooled, const uint8_t* mask);
 /* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
  * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
  * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on

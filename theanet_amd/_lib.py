@@ -104,6 +104,10 @@ SIGNATURES = {
     "tn_c8_dropout_fwd": (c_int, [CTX, P, P, P] + [c_int] * 4 + [c_float, c_uint64, c_uint32, P, c_uint64, c_int]),
     "tn_c8_dropout_bwd": (c_int, [CTX, P, P, P] + [c_int] * 4),
     "tn_c8_scale": (c_int, [CTX, P, P] + [c_int] * 4 + [c_float]),
+    "tn_c8_conv1_supported": (c_int, [c_int] * 5),
+    "tn_c8_conv1_fwd": (c_int, [CTX, P, P, P, P, P] + [c_int] * 6 + [c_float, c_int]),
+    "tn_c8_conv1_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 5 + [P, c_int, c_float, c_int, P]),
+    "tn_c8_conv1_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_int, P]),
     "tn_c8_pack_pitch": (c_int, [CTX, P, c_int64, P] + [c_int] * 4 + [c_float]),
     "tn_c8_pad_zero": (c_int, [CTX, P] + [c_int] * 4),
     "tn_c8_crop": (c_int, [CTX, P, P] + [c_int] * 4),

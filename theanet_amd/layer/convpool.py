@@ -65,23 +65,33 @@ class ConvLayer(Layer):
             # (device.C8Array), which the 'same' products read as their padding.
             self.pitch = inpt.pitch if getattr(inpt, "c8", None) else c8_pitch(in_sz)
             P = self.pitch
-            ok = (in_sz == P or in_sz <= 64) and P >= 8 and \
-                lib.tn_c8_conv_supported(batch_sz, num_prev_maps, P, P, num_maps, filter_sz, stride, self.pad_lo) and \
-                lib.tn_c8_conv_wgrad_supported(batch_sz, num_prev_maps, P, P, num_maps)
-            assert ok and mode == 'same', (
+            # two shapes run on the stack: 3x3 stride-1 'same' (conv_c8.hip) and 1x1 stride-1 (conv1_c8.hip: 'valid' and
+            # 'same' are the same layer, any number of filters)
+            self.c8_1x1 = filter_sz == 1 and stride == 1 and mode in ('valid', 'same')
+            if self.c8_1x1:
+                ok = bool(lib.tn_c8_conv1_supported(batch_sz, num_prev_maps, in_sz, P, num_maps))
+            else:
+                ok = (in_sz == P or in_sz <= 64) and P >= 8 and mode == 'same' and \
+                    lib.tn_c8_conv_supported(batch_sz, num_prev_maps, P, P, num_maps, filter_sz, stride, self.pad_lo) and \
+                    lib.tn_c8_conv_wgrad_supported(batch_sz, num_prev_maps, P, P, num_maps)
+            assert ok, (
                 "DTYPE {} needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of at most 64 "
-                "pixels a side, stored at a pitch of at least 8 (got {}->{} maps, {}x{} at pitch {}, {} filter {} "
-                "stride {})".format(self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, P, mode, filter_sz, stride))
+                "pixels a side, stored at a pitch of at least 8, or 1x1 stride-1 conv layers (got {}->{} maps, {}x{} at "
+                "pitch {}, {} filter {} stride {})".format(self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, P, mode,
+                                                           filter_sz, stride))
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
             self.x16 = None if getattr(inpt, "c8", None) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz,
                                                                       self.c8_dtype, pitch=P)
             self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, self.c8_dtype, pitch=P)
             # the weights as MFMA operand tiles (forward / input gradient): the net arranges every layer's in one launch
             # per step (NeuralNet._c8_arrange) and marks them valid until the next update; otherwise the ops do it per call
-            self.wt_fwd = self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16)
+            # (a 1x1 layer has none: tn_c8_conv1_* round their operand tiles per call)
+            self.wt_fwd = None if self.c8_1x1 else \
+                self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16)
             self.wt_bwd = None
             self.wt_valid = False
         else:
+            self.c8_1x1 = False
             self.output = self.ctx.empty((batch_sz, num_maps, self.out_sz, self.out_sz))
         self.gin = None
         self.fused_pool = None     # set by NeuralNet: conv+act+pool run as ONE kernel
@@ -178,6 +188,12 @@ class ConvLayer(Layer):
 
     def _c8_forward(self, out, mask):
         x = self._c8_input()
+        if self.c8_1x1:
+            # (writes its output's pad cells itself)
+            self.ctx.call("tn_c8_conv1_fwd", x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None,
+                          self.batch_sz, self.num_prev_maps, self.in_sz, self.pitch, self.num_maps, self.act.kind,
+                          self.act.prm, 1 if out is not self.output else 0)
+            return
         self.ctx.call("tn_c8_conv_fwd", x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None,
                       self.batch_sz, self.num_prev_maps, self.pitch, self.pitch, self.num_maps, self.act.kind, self.act.prm,
                       1 if out is not self.output else 0, self.wt_fwd.ptr if self.wt_valid else None)
@@ -191,8 +207,12 @@ class ConvLayer(Layer):
         pooled, mask = (1, pool.mask.ptr) if pool is not None else (0, None)
         x = self.x16 if self.x16 is not None else self.inpt
         geom = (self.batch_sz, self.num_prev_maps, self.pitch, self.pitch, self.num_maps)
+        wgrad, dgrad = "tn_c8_conv_wgrad", "tn_c8_conv_dgrad"
+        if self.c8_1x1:
+            geom = (self.batch_sz, self.num_prev_maps, self.in_sz, self.pitch, self.num_maps)
+            wgrad, dgrad = "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad"
         if self.has_updates():
-            self.ctx.call("tn_c8_conv_wgrad", x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *geom, pooled, mask)
+            self.ctx.call(wgrad, x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *geom, pooled, mask)
         if not need_gin:
             return None
         assert self.x16 is None, "DTYPE {}: no trainable layer below the first conv layer".format(self.c8_dtype)
@@ -202,7 +222,11 @@ class ConvLayer(Layer):
         b_out, b_act, b_prm, b_mask = below.act_info()
         assert b_mask is None
         fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-        self.ctx.call("tn_c8_conv_dgrad", gout.ptr, self.W.ptr, self.gin.ptr, *geom, b_out.ptr if fuse else None,
+        if self.c8_1x1:
+            self.ctx.call(dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *geom, b_out.ptr if fuse else None, b_act, b_prm,
+                          pooled, mask)
+            return self.gin
+        self.ctx.call(dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *geom, b_out.ptr if fuse else None,
                       b_act, b_prm, pooled, mask, self.wt_bwd.ptr if self.wt_valid and self.wt_bwd is not None else None)
         self._c8_pad_zero(self.gin)
         return self.gin

@@ -95,9 +95,11 @@ class NeuralNet():
     # False = the generic schedule, one launch per piece of work -- what the fused schedules are tested against
     fused_step = True
     # the C-ABI ops that carry a net's conv products (bench.py brackets them for the conv roofline legs)
-    CONV_FWD_OPS = ("tn_conv2d_fwd", "tn_convpool_fwd_mask", "tn_elastic_convpool_fwd_mask", "tn_c8_conv_fwd")
+    CONV_FWD_OPS = ("tn_conv2d_fwd", "tn_convpool_fwd_mask", "tn_elastic_convpool_fwd_mask", "tn_c8_conv_fwd",
+                    "tn_c8_conv1_fwd")
     CONV_BWD_OPS = ("tn_conv2d_wgrad", "tn_conv2d_dgrad", "tn_convpool_bwd_mask_dx", "tn_convpool_bwd_mask",
-                    "tn_convblock_bwd_mask", "tn_convblock_bwd", "tn_convpool_bwd", "tn_c8_conv_wgrad", "tn_c8_conv_dgrad")
+                    "tn_convblock_bwd_mask", "tn_convblock_bwd", "tn_convpool_bwd", "tn_c8_conv_wgrad", "tn_c8_conv_dgrad",
+                    "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad")
 
     def __init__(self, layers, training_params, allwts=None,
                  test_x=None):
@@ -812,7 +814,7 @@ class NeuralNet():
             assert dt.itemsize == 32          # tn_c8_wt_seg
             rows, convs = [], []
             for idx, lyr in enumerate(lyrs):
-                if isinstance(lyr, ConvLayer) and lyr.f16:
+                if isinstance(lyr, ConvLayer) and lyr.f16 and not lyr.c8_1x1:      # (K, C, 3, 3) weights only
                     convs.append(lyr)
                     rows.append((lyr.W.ptr, lyr.wt_fwd.ptr, lyr.num_maps, lyr.num_prev_maps, 0, 0))
                     if train and self._need_gin[idx]:
