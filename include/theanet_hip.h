@@ -163,7 +163,15 @@ int tn_get_matmul_dtype(tn_ctx* ctx);
 /* MATMUL 'bf16x3' (opt-in, this build's extension; the reference is float32, weights.py:8): mode 1 runs the products of
  * tn_fc_fwd / tn_fc_wgrad / tn_fc_dgrad / tn_fc_bwd of layers with more than 16 outputs as six bf16 MFMA products of
  * exactly split operands (x = x0 + x1 + x2, 8 mantissa bits each) with fp32 accumulation -- fp32-grade accuracy
- * (the same tolerances hold), not the same bits as mode 0's exact fp32 MFMA.  theanet_amd/csrc/gemm_b3.hip.        */
+ * (the same tolerances hold), not the same bits as mode 0's exact fp32 MFMA.  theanet_amd/csrc/gemm_b3.hip.
+ * MATMUL 'bfloat16' (opt-in): mode 2 runs the products of tn_fc_fwd / tn_fc_fwd_dropout / tn_fc_wgrad / tn_fc_dgrad /
+ * tn_fc_bwd of EVERY shape (ragged edges are masked in the kernel; nothing falls back to fp32) with both operands
+ * rounded to bf16 (nearest even) as they are staged, exact products, fp32 accumulation on v_mfma_f32_32x32x16_bf16 and
+ * the fp32 epilogues of mode 0 -- the arithmetic of the 16-bit conv stack; tensors in memory stay fp32, db is the fp32
+ * column sum of dz, tn_fc_fwd_dropout draws tn_dropout_mask's bits.  A reduced-precision mode (~2^-9 relative per
+ * operand).  The output heads stay fp32 by design: tn_fc_softmax_train / tn_fc_softmax_nll (also where they fall back
+ * to the generic products), tn_softmax_nll*, tn_head_rows.  theanet_amd/csrc/gemm_bf16.hip.
+ * Modes other than 0 / 1 / 2 are refused; the CPU backend accepts 0 only.                                          */
 int tn_set_fc_matmul(tn_ctx* ctx, int mode);
 
 /* ---- DTYPE 'float16' on fp16-RESIDENT tensors (theanet_amd/csrc/conv_c8.hip, fc_c8.hip) --------------------

@@ -54,6 +54,7 @@ struct tn_ctx {
     // power of two applied to dz before it is rounded to the 16-bit type
     int mm_f16 = 0;
     int fc_b3 = 0;                         // tn_set_fc_matmul: 1 = FC products as bf16 triplets (gemm_b3.hip)
+    int fc_bf16 = 0;                       // tn_set_fc_matmul: 2 = FC products on bf16-rounded operands (gemm_bf16.hip)
     float grad_scale = 1.f;
     char err[512] = {0};
     // RCCL (loaded lazily, comm.hip)
@@ -100,6 +101,14 @@ int tn_b3_fc_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, fl
 int tn_b3_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in, int n_out, const float* prev_a,
                    int act, float prm, const uint8_t* mask);
 int tn_b3_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in, int n_out, float* ws,
+                   int S);
+// MATMUL 'bfloat16' products of a fully-connected layer (gemm_bf16.hip): operands rounded to bf16 as they are staged,
+// fp32 accumulation; the tn_fc_* entry points dispatch here for EVERY shape while tn_set_fc_matmul(ctx, 2) is in force
+int tn_bf_fc_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B, int n_in, int n_out, int act,
+                 float prm, const uint8_t* mask);
+int tn_bf_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in, int n_out, const float* prev_a,
+                   int act, float prm, const uint8_t* mask);
+int tn_bf_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in, int n_out, float* ws,
                    int S);
 int tn_red_flush(tn_ctx* ctx);
 int tn_red_flush_inc(tn_ctx* ctx, uint32_t* inc);

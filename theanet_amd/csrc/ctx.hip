@@ -95,8 +95,10 @@ int tn_set_matmul_dtype(tn_ctx* ctx, int dtype, float grad_scale) {
 int tn_get_matmul_dtype(tn_ctx* ctx) { return ctx->mm_f16; }
 
 int tn_set_fc_matmul(tn_ctx* ctx, int mode) {
-    TN_REQUIRE(mode == 0 || mode == 1, "tn_set_fc_matmul: mode %d (0 exact fp32 MFMA, 1 bf16 triplets)", mode);
-    ctx->fc_b3 = mode;
+    TN_REQUIRE(mode >= 0 && mode <= 2,
+               "tn_set_fc_matmul: mode %d (0 exact fp32 MFMA, 1 bf16 triplets 'bf16x3', 2 bf16-rounded operands 'bfloat16')", mode);
+    ctx->fc_b3 = mode == 1;
+    ctx->fc_bf16 = mode == 2;
     return TN_OK;
 }
 

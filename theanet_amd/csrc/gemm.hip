@@ -1360,6 +1360,15 @@ int tn_fc_skinny_softmax(tn_ctx* ctx, const float* x, const float* W, const floa
                          const int64_t* d_row0, float* logprob, float* rowloss, int32_t* pred,
                          float* rowp, float* dz, float inv_batch);
 
+// The output heads stay fp32 under MATMUL 'bfloat16' (gemm_bf16.hip): while a head's entry point runs, the generic
+// products it falls back to for a wide head (tn_fc_fwd / tn_fc_bwd) do not dispatch to the bf16 kernels.
+struct FcHeadExact {
+    tn_ctx* ctx;
+    int keep;
+    explicit FcHeadExact(tn_ctx* c) : ctx(c), keep(c->fc_bf16) { c->fc_bf16 = 0; }
+    ~FcHeadExact() { ctx->fc_bf16 = keep; }
+};
+
 extern "C" {
 
 int tn_fc_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float* b, float* logits, int B,
@@ -1370,6 +1379,7 @@ int tn_fc_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && logits && logprob && y && dz && dW && db && dx && ws,
                "tn_fc_softmax_train: bad arguments");
     TN_REQUIRE(prev_a == nullptr || prev_a == x, "tn_fc_softmax_train: prev_a must be the layer input");
+    const FcHeadExact head(ctx);
     if (tn_knob(TN_K_SOFTMAX_TRAIN) && tn_fc_skinny_ok(n_in, n_out, x, dx, prev_mask))
         return tn_fc_skinny_softmax_train(ctx, x, W, b, logits, B, n_in, n_out, y, y_row0, d_row0, logprob,
                                           rowloss, pred, rowp, dz, inv_batch, dW, db, dx, (float*)ws,
@@ -1388,6 +1398,7 @@ int tn_fc_softmax_nll(tn_ctx* ctx, const float* x, const float* W, const float* 
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && logits && logprob, "tn_fc_softmax_nll: bad arguments");
     TN_REQUIRE(y != nullptr || (rowloss == nullptr && dz == nullptr && rowp == nullptr),
                "tn_fc_softmax_nll: labels required for loss/gradient outputs");
+    const FcHeadExact head(ctx);
     if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr))
         return tn_fc_skinny_softmax(ctx, x, W, b, logits, B, n_in, n_out, y, y_row0, d_row0, logprob,
                                     rowloss, pred, rowp, dz, inv_batch);
@@ -1465,6 +1476,7 @@ static int fc_dgrad_splits(tn_ctx* ctx, int B, int n_in, int n_out) {
 int tn_fc_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B, int n_in,
               int n_out, int act, float act_param, const uint8_t* mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0, "tn_fc_fwd: bad shape");
+    if (ctx->fc_bf16) return tn_bf_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);      // any shape
     if (ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out))
         return tn_b3_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
     if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr))
@@ -1497,6 +1509,7 @@ int tn_fc_fwd_dropout(tn_ctx* ctx, const float* x, const float* W, const float* 
                       int n_in, int n_out, int act, float act_param, uint8_t* mask_out, float pdrop,
                       uint64_t seed, uint32_t step, const uint32_t* d_step, uint64_t elem0) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && mask_out != nullptr, "tn_fc_fwd_dropout: bad arguments");
+    TN_REQUIRE(!ctx->fc_bf16 || (x && W && b && a), "tn_fc_fwd_dropout (MATMUL 'bfloat16'): bad arguments");    // before the mask is drawn
     GemmArgs g{};
     g.A = x; g.B = W; g.C = a;
     g.M = B; g.N = n_out; g.K = n_in;
@@ -1506,7 +1519,8 @@ int tn_fc_fwd_dropout(tn_ctx* ctx, const float* x, const float* W, const float* 
     g.a_vec = vec_ok(x, n_in); g.b_vec = vec_ok(W, n_out);
     g.drop_out = mask_out; g.pdrop = pdrop; g.dk0 = (uint32_t)seed; g.dk1 = (uint32_t)(seed >> 32);
     g.dstep = step; g.d_step = d_step; g.elem0 = elem0;
-    if (!(ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out)) && n_out > SK_MAX && fc_fwd_splits(ctx, B, n_in, n_out) == 1 && gemm_fast_ok<true, false>(g) &&
+    // (MATMUL 'bfloat16': the mask from its own launch -- the same bits -- then the product with that mask)
+    if (!ctx->fc_bf16 && !(ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out)) && n_out > SK_MAX && fc_fwd_splits(ctx, B, n_in, n_out) == 1 && gemm_fast_ok<true, false>(g) &&
         gemm_cvec_ok(g)) {
         if (gemm_deep_ok<false>(ctx, g))
             launch_deep<false>(ctx, g);
@@ -1534,6 +1548,8 @@ size_t tn_fc_wgrad_ws_bytes(int B, int n_in, int n_out) {
 int tn_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in,
                 int n_out, void* ws) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && ws != nullptr, "tn_fc_wgrad: bad arguments");
+    if (ctx->fc_bf16)
+        return tn_bf_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
     if (ctx->fc_b3 && tn_b3_fc_ok(x, dz, B, n_in, n_out))
         return tn_b3_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
     if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr))
@@ -1588,6 +1604,12 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
               float* dx, int B, int n_in, int n_out, void* ws, const float* prev_a, int prev_act,
               float prev_act_param, const uint8_t* prev_mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && ws != nullptr && dx != nullptr, "tn_fc_bwd: bad arguments");
+    if (ctx->fc_bf16) {
+        TN_REQUIRE(x && dz && W && dW && db, "tn_fc_bwd (MATMUL 'bfloat16'): bad arguments");      // before either product
+        int rc = tn_bf_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
+        if (rc) return rc;
+        return tn_bf_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
+    }
     if (ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out) && tn_b3_fc_ok(dz, W, B, n_in, n_out)) {
         int rc = tn_b3_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
         if (rc) return rc;
@@ -1692,6 +1714,8 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
 int tn_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in, int n_out,
                 const float* prev_a, int prev_act, float prev_act_param, const uint8_t* prev_mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0, "tn_fc_dgrad: bad shape");
+    if (ctx->fc_bf16)
+        return tn_bf_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     if (ctx->fc_b3 && tn_b3_fc_ok(dz, W, B, n_in, n_out))
         return tn_b3_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     if (tn_fc_skinny_ok(n_in, n_out, dx, prev_a, prev_mask))

@@ -175,7 +175,8 @@ int tn_set_matmul_dtype(tn_ctx* ctx, int dtype, float grad_scale) {
 }
 int tn_get_matmul_dtype(tn_ctx*) { return 0; }
 int tn_set_fc_matmul(tn_ctx* ctx, int mode) {
-    REQUIRE(mode == 0, "tn_set_fc_matmul: the CPU backend computes the dense products in float32 only");
+    REQUIRE(mode == 0, "tn_set_fc_matmul: mode %d (%s): the CPU backend computes the dense products in float32 only (MATMUL 'float32')",
+            mode, mode == 1 ? "MATMUL 'bf16x3'" : mode == 2 ? "MATMUL 'bfloat16'" : "unknown");
     return TN_OK;
 }
 // DTYPE 'float16' on fp16-resident tensors (conv_c8.hip): MI355X only; the capability queries answer 0 and

@@ -16,6 +16,8 @@ from . import _lib
 # tn_set_matmul_dtype mode of every DTYPE
 C8_DTYPES = ("float16", "bfloat16")
 _MM_MODES = {"float32": 0, "float16": 1, "bfloat16": 2}
+# MATMUL values (the dense layers' products) and their tn_set_fc_matmul modes
+_FC_MODES = {"float32": 0, "bf16x3": 1, "bfloat16": 2}
 
 _context = None
 
@@ -60,6 +62,7 @@ class Context:
             fn = self._fns[name] = getattr(self.lib, name)
         rc = fn(self.h, *args)
         if rc != 0:
+            self._fc_mm = None          # (a step may have stopped inside a head's fc_head bracket: set the mode afresh)
             _lib.check(self.h, rc, name)
 
     # -- per-kernel timing with HIP events on the compute stream (bench.py roofline leg) --
@@ -109,10 +112,25 @@ class Context:
         self.mm_dtype = dtype
 
     def set_fc_matmul(self, mode):
-        """'float32' (exact fp32 MFMA) or 'bf16x3' (six bf16 MFMA products of exactly split operands: tn_set_fc_matmul)."""
+        """'float32' (exact fp32 MFMA), 'bf16x3' (six bf16 MFMA products of exactly split operands) or 'bfloat16'
+        (operands rounded to bf16, fp32 accumulation: the conv stack's 16-bit arithmetic) -- tn_set_fc_matmul 0 / 1 / 2."""
         if mode != getattr(self, "_fc_mm", "float32"):
-            self.call("tn_set_fc_matmul", 1 if mode == "bf16x3" else 0)
+            self.call("tn_set_fc_matmul", _FC_MODES[mode])
             self._fc_mm = mode
+
+    def fc_head(self, inside):
+        """The output heads stay fp32 under MATMUL 'bfloat16': the net brackets a head's forward / backward with
+        fc_head(True) ... fc_head(False), between which the dense products are the exact fp32 ones.  (Host-side state
+        of the library; the two calls are part of a recorded step plan.)  Nothing happens in the other modes."""
+        if inside:
+            self._fc_head_open = getattr(self, "_fc_mm", "float32") == "bfloat16"
+            if self._fc_head_open:
+                self.call("tn_set_fc_matmul", 0)
+        elif getattr(self, "_fc_head_open", False):
+            # (also after the head raised inside the bracket: a failing call drops the mode record, see call())
+            self._fc_head_open = False
+            self.call("tn_set_fc_matmul", _FC_MODES["bfloat16"])
+            self._fc_mm = "bfloat16"
 
     def knobs(self):
         """The library's environment switches that data-parallel ranks must agree on, as resolved (tn_knobs): name -> int."""

@@ -120,10 +120,13 @@ class NeuralNet():
         self.dtype = training_params.get('DTYPE', 'float32')
         assert self.dtype in ('float32', 'float16', 'bfloat16'), "DTYPE must be 'float32', 'float16' or 'bfloat16'"
         self.grad_scale = float(training_params.get('GRAD_SCALE', 1. if self.dtype == 'bfloat16' else 4096.))
-        # MATMUL: 'float32' (default: exact fp32 MFMA) or 'bf16x3' -- the dense layers' products as six bf16 MFMA
-        # products of exactly split operands (fp32-grade accuracy, not the same bits; gemm_b3.hip)
+        # MATMUL: 'float32' (default: exact fp32 MFMA), 'bf16x3' -- the dense layers' products as six bf16 MFMA
+        # products of exactly split operands (fp32-grade accuracy, not the same bits; gemm_b3.hip) -- or 'bfloat16':
+        # every HiddenLayer's three products on bf16-rounded operands with fp32 accumulation (gemm_bf16.hip; reduced
+        # precision, the conv stack's 16-bit arithmetic; any layer shape; the output heads stay fp32).  Independent
+        # of DTYPE: the dense layer directly on a 16-bit conv stack keeps tn_c8_fc_*.
         self.matmul = training_params.get('MATMUL', 'float32')
-        assert self.matmul in ('float32', 'bf16x3'), "MATMUL must be 'float32' or 'bf16x3'"
+        assert self.matmul in ('float32', 'bf16x3', 'bfloat16'), "MATMUL must be 'float32', 'bf16x3' or 'bfloat16'"
         self._apply_dtype()
         self.world = comm.get_world()
         self._dev_group = None
@@ -599,12 +602,15 @@ class NeuralNet():
         n_lyr = len(self.tr_layers)
         fuse_out = self._softmax_train and n_lyr >= 2 and self._need_gin[n_lyr - 1] \
             and isinstance(out, SoftmaxLayer) and out.loss == "nll"
+        ctx.fc_head(True)
         try:
             out.forward(True, y=y, y_row0=y_row0, d_row0=d_row0,
                         below=self.tr_layers[-2] if fuse_out else None)
         except Exception:
             ctx.call("tn_defer_reductions", 0)
             raise
+        finally:
+            ctx.fc_head(False)
         want = getattr(self, "_want_outputs", False)
         cost_sent = False
         if want:
@@ -661,7 +667,14 @@ class NeuralNet():
             for idx in range(len(self.tr_layers) - 1, -1, -1):
                 lyr = self.tr_layers[idx]
                 below = self.tr_layers[idx - 1] if idx > 0 else None
-                g = lyr.backward(g, self._need_gin[idx], below)
+                if lyr is out:
+                    ctx.fc_head(True)
+                    try:
+                        g = lyr.backward(g, self._need_gin[idx], below)
+                    finally:
+                        ctx.fc_head(False)
+                else:
+                    g = lyr.backward(g, self._need_gin[idx], below)
                 if idx == self._dp_split and g is not None:
                     # the top (fully-connected) group is done: finish its slab sums and send its
                     # gradients through the all-reduce on the second stream, under the conv backward
@@ -979,7 +992,11 @@ class NeuralNet():
             for lyr in self.te_layers[:-1]:
                 lyr.forward(False)
             out = self.te_layers[-1]
-            out.forward(False)
+            self.ctx.fc_head(True)
+            try:
+                out.forward(False)
+            finally:
+                self.ctx.fc_head(False)
             res = [out.features.get_value(), out.y_preds.get_value().astype(np.int64)]
             for index in get_output_of_layers:
                 res.append(self.te_layers[index].output.get_value())

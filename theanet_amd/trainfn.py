@@ -675,7 +675,11 @@ class _TestFn:
         out = net.te_layers[-1]
         for lyr in net.te_layers[:-1]:
             lyr.forward(False)
-        out.forward(False, y=self.y_data, y_row0=slot.row0)
+        ctx.fc_head(True)
+        try:
+            out.forward(False, y=self.y_data, y_row0=slot.row0)
+        finally:
+            ctx.fc_head(False)
         ctx.call("tn_error_stats", out.y_preds.ptr, self.y_data.ptr, slot.row0, out.rowp.ptr,
                  net.local_bsz, out.d_stats.ptr)
         if net.world.size > 1:
