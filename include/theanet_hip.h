@@ -240,6 +240,29 @@ int tn_c8_fc_fwd_dropout(tn_ctx* ctx, const void* x, const float* W, const float
 int tn_c8_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B, int C, int HW, int n_out, const void* y,
                    int act, float act_param);
 int tn_c8_fc_wgrad(tn_ctx* ctx, const void* x, const float* dz, float* dW, float* db, int B, int C, int HW, int n_out);
+/* The same products for ANY layer shape (theanet_amd/csrc/fcg_c8.hip): the tiled family above wants the c8 input length
+ * ceil(C/8)*HW*8 a multiple of 64 and n_out a multiple of 32 (tn_c8_fc_supported) and keeps those shapes; a HiddenLayer
+ * whose shape it refuses (n_out 500, 32 maps of 7x7, ...) takes tn_c8_fcg_*.  Argument for argument tn_c8_fc_*, and the same
+ * arithmetic: x as stored, W rounded nearest-even to the element type E (half or bf16) while it is loaded through the row
+ * map k -> (8 o + e) * HW + p, dz as E(grad_scale * dz), exact products, fp32 accumulation on the 32x32x16 matrix core; a,
+ * dW, db fp32 (OVERWRITE, the gradient scale removed); dgrad stores E(acc * act'(y16)) (y16 NULL: E(acc)) in c8 order and
+ * writes EVERY c8 cell of dx, channels past C as exact +0.  A ragged reduction tail is fed as zeros, a ragged output tail
+ * is not stored, rows of W for channels past C are never read, and no alignment of n_out is assumed for W, b, mask, a
+ * or dz.  fwd_dropout draws tn_dropout_mask's bits for the logical (B, n_out) matrix at any elem0 and any n_out; its
+ * masked output equals tn_c8_fcg_fwd with that mask bit for bit.  No atomics: K slabs (forward) and sample slabs (weight
+ * gradient) meet in context scratch in a fixed order, the same call gives the same bits.
+ * supported: 1 for every B, C, HW, n_out >= 1 with, Kc = ceil(C/8)*HW*8: B*Kc, B*n_out and C*HW*n_out < 2^31,
+ * (Kc/8)*HW < 2^32, B and n_out at most 65535 * 64.  Anything else, or a NULL x, W, b, a, dz, dx, dW, db (mask_out for
+ * fwd_dropout): TN_E_ARG by name, nothing launched.                                                                  */
+int tn_c8_fcg_supported(int B, int C, int HW, int n_out);
+int tn_c8_fcg_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW, int n_out,
+                  int act, float act_param, const uint8_t* mask);
+int tn_c8_fcg_fwd_dropout(tn_ctx* ctx, const void* x, const float* W, const float* b, float* a, int B, int C, int HW,
+                          int n_out, int act, float act_param, uint8_t* mask_out, float pdrop, uint64_t seed, uint32_t step,
+                          const uint32_t* d_step, uint64_t elem0);
+int tn_c8_fcg_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B, int C, int HW, int n_out, const void* y,
+                    int act, float act_param);
+int tn_c8_fcg_wgrad(tn_ctx* ctx, const void* x, const float* dz, float* dW, float* db, int B, int C, int HW, int n_out);
 /* NCHW fp32 (rows row0.. of a dataset) -> c8 fp16 and back; values are multiplied by scale                        */
 int tn_c8_pack(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int HW, float scale);
 /* tn_elastic_apply (below; inlayers.py:126-142) whose output is the c8 tensor the first conv layer consumes: the same

@@ -201,6 +201,15 @@ int tn_c8_fc_dgrad(tn_ctx* ctx, const float*, const float*, void*, int, int, int
     NOT_HERE("tn_c8_fc_dgrad");
 }
 int tn_c8_fc_wgrad(tn_ctx* ctx, const void*, const float*, float*, float*, int, int, int, int) { NOT_HERE("tn_c8_fc_wgrad"); }
+int tn_c8_fcg_supported(int, int, int, int) { return 0; }
+int tn_c8_fcg_fwd(tn_ctx* ctx, const void*, const float*, const float*, float*, int, int, int, int, int, float,
+                  const uint8_t*) { NOT_HERE("tn_c8_fcg_fwd"); }
+int tn_c8_fcg_fwd_dropout(tn_ctx* ctx, const void*, const float*, const float*, float*, int, int, int, int, int, float,
+                          uint8_t*, float, uint64_t, uint32_t, const uint32_t*, uint64_t) { NOT_HERE("tn_c8_fcg_fwd_dropout"); }
+int tn_c8_fcg_dgrad(tn_ctx* ctx, const float*, const float*, void*, int, int, int, int, const void*, int, float) {
+    NOT_HERE("tn_c8_fcg_dgrad");
+}
+int tn_c8_fcg_wgrad(tn_ctx* ctx, const void*, const float*, float*, float*, int, int, int, int) { NOT_HERE("tn_c8_fcg_wgrad"); }
 int tn_c8_pack(tn_ctx* ctx, const float*, int64_t, void*, int, int, int, float) { NOT_HERE("tn_c8_pack"); }
 int tn_c8_elastic_apply(tn_ctx* ctx, const float*, int64_t, const int64_t*, void*, int, int, int, int, int, int, const int32_t*,
                         const float*, const float*, float, const uint8_t*, uint64_t, uint32_t, const uint32_t*, int64_t) {

@@ -33,15 +33,21 @@ class HiddenLayer(Layer):
         self.ctx = self.w.ctx
 
         self.act = activation_by_name(actvn)
-        # DTYPE float16: the layer above the conv stack consumes the c8 tensor as it is stored (tn_c8_fc_*: fp16
+        # DTYPE float16: the layer above the conv stack consumes the c8 tensor as it is stored (tn_c8_fc_* / tn_c8_fcg_*: fp16
         # operands through the NCHW row map, fp32 output); further dense layers are fp32 like the reference
         self.c8 = getattr(inpt, "c8", None)
         if self.c8 is not None:
             c, h, wd = self.c8
             assert c * h * wd == n_in, (self.c8, n_in)
-            assert self.ctx.lib.tn_c8_fc_supported(inpt.shape[0], c, h * wd, n_out), (
-                "DTYPE {}: a dense layer on {} maps of {}x{} needs a multiple of 64 inputs (c8) and of 32 outputs "
-                "(got {})".format(inpt.elem, c, h, wd, n_out))
+            # the family is picked once: the tiled products where they take the shape (a multiple of 64 c8 inputs and of
+            # 32 outputs), the general ones (tn_c8_fcg_*: any shape) otherwise -- same arguments, same arithmetic
+            lib, shape = self.ctx.lib, (inpt.shape[0], c, h * wd, n_out)
+            self.c8_fc = "tn_c8_fc" if lib.tn_c8_fc_supported(*shape) else \
+                "tn_c8_fcg" if lib.tn_c8_fcg_supported(*shape) else None
+            assert self.c8_fc is not None, (
+                "DTYPE {}: a dense layer of {} samples on {} maps of {}x{} with {} outputs is beyond what the 16-bit dense "
+                "products index (tn_c8_fcg_supported: fewer than 2^31 input, output and weight elements)".format(
+                    inpt.elem, inpt.shape[0], c, h, wd, n_out))
             self.inpt = inpt
             # a padded stack tensor (maps stored at a pitch > their side): the products read a dense copy, cropped in
             # front of them (tn_c8_crop); the input gradient is embedded back into the padded layout (tn_c8_embed)
@@ -94,13 +100,13 @@ class HiddenLayer(Layer):
                 self.ctx.call("tn_c8_crop", self.c8_src.ptr, self.inpt.ptr, self.batch_sz, c, h, self.c8_src.pitch)
             if drop is not None and not drop.injected and not drop.ready:
                 # the mask is drawn by the product's finishing kernel (and kept for the backward pass)
-                self.ctx.call("tn_c8_fc_fwd_dropout", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz,
+                self.ctx.call(self.c8_fc + "_fwd_dropout", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz,
                               c, h * wd, self.n_out, self.act.kind, self.act.prm, drop.mask.ptr, drop.pdrop, drop.seed, 0,
                               drop.d_step.ptr if drop.d_step is not None else None, drop.elem0)
             else:
                 if drop is not None:
                     drop.generate()
-                self.ctx.call("tn_c8_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz, c, h * wd,
+                self.ctx.call(self.c8_fc + "_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz, c, h * wd,
                               self.n_out, self.act.kind, self.act.prm, drop.mask.ptr if drop is not None else None)
         elif drop is not None and not drop.injected and not drop.ready:
             # the mask is drawn inside the layer's own launch (and kept for the backward pass)
@@ -123,7 +129,7 @@ class HiddenLayer(Layer):
         if self.c8 is not None:
             c, h, wd = self.c8
             if self.has_updates():
-                self.ctx.call("tn_c8_fc_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr,
+                self.ctx.call(self.c8_fc + "_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr,
                               self.batch_sz, c, h * wd, self.n_out)
             if not need_gin:
                 return None
@@ -138,7 +144,7 @@ class HiddenLayer(Layer):
             if fuse and src is not None:
                 assert b_out is src
                 b_out = self.inpt                   # act' from the cropped copy of the block's output (same values)
-            self.ctx.call("tn_c8_fc_dgrad", gout.ptr, self.w.ptr, self.gin.ptr, self.batch_sz, c, h * wd, self.n_out,
+            self.ctx.call(self.c8_fc + "_dgrad", gout.ptr, self.w.ptr, self.gin.ptr, self.batch_sz, c, h * wd, self.n_out,
                           b_out.ptr if fuse else None, b_act, b_prm)
             if src is None:
                 return self.gin
