@@ -255,6 +255,11 @@ def bf16_value(bits):
     return (np.asarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
+def is_c8(t):
+    """True for a 16-bit-resident tensor of the conv stack (a C8Array): the one test for "on the 16-bit stack"."""
+    return getattr(t, "c8", None) is not None
+
+
 def c8_pitch(side):
     """The stored side of a c8 tensor entering the 16-bit conv stack with maps of ``side`` pixels: the smallest power
     of two >= max(side, 8) (theanet_amd/csrc/conv_c8.hip, "padded pitch")."""
@@ -282,6 +287,14 @@ class C8Array(DeviceArray):
         super().__init__(ctx, (n, (c + 7) // 8, self.pitch, pw, 8), np.uint16)
         if self.padded:
             self.fill_bytes(0)
+
+    @classmethod
+    def like(cls, t):                   # same geometry, element type and pitch as ``t``
+        return cls(t.ctx, t.shape[0], *t.c8, t.elem, pitch=t.pitch)
+
+    @classmethod
+    def dense_like(cls, t):             # ... stored without padding (the target of tn_c8_crop)
+        return cls(t.ctx, t.shape[0], *t.c8, t.elem)
 
     @property
     def padded(self):

@@ -11,7 +11,7 @@ import numpy as np
 
 from .. import _lib
 from .hidden import HiddenLayer
-from .layer import Layer, activation_by_name
+from .layer import Layer, activation_by_name, below_info
 from .outlayers import HEAD_SOFTMAX, OutputLayer, loss_code
 from .weights import init_wb
 
@@ -127,12 +127,11 @@ class AuxConcatLayer(Layer):
     def backward(self, gout, need_gin, below):
         if not need_gin:
             return None
-        b_out, b_act, b_prm, b_mask = below.act_info()
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
         self.ctx.call("tn_copy_cols", gout.ptr, self.n_out, 0, self.gin.ptr, self.n_in, 0, self.n_in, self.batch_sz,
-                      b_out.ptr if fuse else None, b_act, b_prm)
+                      b_ptr, b_act, b_prm)
         if b_mask is not None:        # a Hidden layer with dropout right below: its mask, after the copy
             self.ctx.call("tn_scale_mask", self.gin.ptr, b_mask.ptr, 1.0, self.gin.ptr, self.gin.size,
                           None, _lib.TN_ACT_LINEAR, 0.0)

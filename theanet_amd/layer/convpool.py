@@ -6,9 +6,9 @@ import os
 
 import numpy as np
 
-from .. import _lib
-from ..device import C8_DTYPES, C8Array, c8_pitch
-from .layer import Layer, activation_by_name
+from ..device import C8_DTYPES, C8Array, c8_pitch, is_c8
+from .c8 import DenseDetour, conv_family
+from .layer import Layer, activation_by_name, below_info
 from .weights import init_wb
 
 
@@ -18,7 +18,8 @@ class ConvLayer(Layer):
                  num_maps, filter_sz, stride,
                  mode='valid',
                  actvn='relu50',
-                 reg=()):
+                 reg=(),
+                 dtype='float32'):
         assert (wts is not None or rand_gen is not None)
         assert mode in ("valid", "full", "same")
         if mode == "full":
@@ -49,12 +50,12 @@ class ConvLayer(Layer):
         self.act = activation_by_name(actvn)
         assert self.act.kind is not None, "softmax is not a conv activation"
         self.ctx = self.W.ctx
-        # DTYPE 'float16' (NeuralNet training param; BASELINE configs[4]): activations and gradients live in HBM as
-        # halfs in the c8 layout (device.C8Array), fp16 MFMA operands / fp32 accumulation, fp32 master weights.  Every
-        # conv layer of the net runs that way or construction fails -- no silent fp32 run of an unsupported shape.
-        # DTYPE 'bfloat16': the same with bf16 in place of half.  f16: "16-bit resident", either of the two.
-        self.f16 = self.ctx.mm_dtype in C8_DTYPES
-        self.c8_dtype = self.ctx.mm_dtype if self.f16 else None
+        # ``dtype`` (the net's DTYPE training param; BASELINE configs[4]) 'float16' / 'bfloat16': activations and
+        # gradients live in HBM as halfs / bf16 in the c8 layout (device.C8Array), 16-bit MFMA operands / fp32
+        # accumulation, fp32 master weights.  Every conv layer of the net runs that way or construction fails -- no
+        # silent fp32 run of an unsupported shape.  f16: "16-bit resident", either of the two.
+        self.f16 = dtype in C8_DTYPES
+        self.c8_dtype = dtype if self.f16 else None
         self.inpt = inpt
         self.batch_sz, self.num_prev_maps, self.in_sz = batch_sz, num_prev_maps, in_sz
         self.filter_sz, self.stride = filter_sz, stride
@@ -63,7 +64,7 @@ class ConvLayer(Layer):
             # maps of S pixels a side are stored at a pitch P: the input's, or -- first conv layer -- the smallest power of
             # two >= max(S, 8).  The kernels run on the P x P shape; S < P pads every plane with zero rows and columns
             # (device.C8Array), which the 'same' products read as their padding.
-            self.pitch = inpt.pitch if getattr(inpt, "c8", None) else c8_pitch(in_sz)
+            self.pitch = inpt.pitch if is_c8(inpt) else c8_pitch(in_sz)
             P = self.pitch
             # two shapes run on the stack: 3x3 stride-1 'same' (conv_c8.hip) and 1x1 stride-1 (conv1_c8.hip: 'valid' and
             # 'same' are the same layer, any number of filters)
@@ -80,18 +81,16 @@ class ConvLayer(Layer):
                 "pitch {}, {} filter {} stride {})".format(self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, P, mode,
                                                            filter_sz, stride))
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
-            self.x16 = None if getattr(inpt, "c8", None) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz,
-                                                                      self.c8_dtype, pitch=P)
-            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, self.c8_dtype, pitch=P)
+            self.x16 = None if is_c8(inpt) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz, dtype, pitch=P)
+            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, dtype, pitch=P)
+            self.c8_fam = conv_family(self.c8_1x1, batch_sz, num_prev_maps, in_sz, P, num_maps)
             # the weights as MFMA operand tiles (forward / input gradient): the net arranges every layer's in one launch
-            # per step (NeuralNet._c8_arrange) and marks them valid until the next update; otherwise the ops do it per call
-            # (a 1x1 layer has none: tn_c8_conv1_* round their operand tiles per call)
-            self.wt_fwd = None if self.c8_1x1 else \
-                self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16)
-            self.wt_bwd = None
-            self.wt_valid = False
+            # per step (c8.OperandTiles) and marks them valid until the next update; otherwise the ops do it per call
+            self.wt_fwd = self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16) \
+                if self.c8_fam.tiles else None
+            self.wt_bwd, self.wt_valid = None, False
         else:
-            self.c8_1x1 = False
+            self.c8_1x1, self.c8_fam = False, None
             self.output = self.ctx.empty((batch_sz, num_maps, self.out_sz, self.out_sz))
         self.gin = None
         self.fused_pool = None     # set by NeuralNet: conv+act+pool run as ONE kernel
@@ -110,7 +109,7 @@ class ConvLayer(Layer):
         self.reg.update(reg)
 
         self.args = (batch_sz, num_prev_maps, in_sz, num_maps, filter_sz,
-                     stride, mode, actvn, reg)
+                     stride, mode, actvn, reg, dtype)
         self.representation = (
             "Conv Maps:{:2d} Filter:{} Stride:{} Mode:{} Output:{:2d} "
             "Act:{}\n\t  L1:{L1} L2:{L2} Momentum:{momentum} Rate:{rate} Max Norm:{maxnorm}"
@@ -131,8 +130,7 @@ class ConvLayer(Layer):
         """conv -> act -> 2x2 max-pool on small channel counts runs as one fused kernel pair
         (tn_convpool_fwd / tn_convpool_bwd): the conv activation never reaches HBM."""
         if self.f16:
-            assert pool.pool_sz == 2 and self.out_sz % 2 == 0, "DTYPE {}: pooling layers are 2x2 on even maps".format(self.c8_dtype)
-            return True
+            return True                  # (the only way a PoolLayer runs on the 16-bit stack: c8.check_follows)
         if self.stride == 1 and self.ctx.lib.tn_convpool_supported(
                 self.num_prev_maps, self.filter_sz, self.stride, pool.pool_sz):
             return True
@@ -159,7 +157,7 @@ class ConvLayer(Layer):
                 self.filter_sz, self.pad_lo, self.out_sz, self.out_sz, pool.pool_sz,
                 pool.out_sz, pool.out_sz, self.act.kind, self.act.prm)
 
-    # -- DTYPE float16: the fp16-resident kernels (include/theanet_hip.h, tn_c8_*) --------------------------------
+    # -- the 16-bit stack: the 16-bit-resident kernels (include/theanet_hip.h, tn_c8_*) ---------------------------
     _c8_prefilled = False
 
     def _c8_input(self, below=None):
@@ -186,49 +184,37 @@ class ConvLayer(Layer):
         if t.padded:
             self.ctx.call("tn_c8_pad_zero", t.ptr, self.batch_sz, t.c8[0], t.c8[1], t.pitch)
 
+    def _c8_tiles(self, wt):
+        """The trailing argument of a product that takes the weights as arranged operand tiles: the tiles while valid."""
+        return (wt.ptr if self.wt_valid and wt is not None else None,) if self.c8_fam.tiles else ()
+
     def _c8_forward(self, out, mask):
-        x = self._c8_input()
-        if self.c8_1x1:
-            # (writes its output's pad cells itself)
-            self.ctx.call("tn_c8_conv1_fwd", x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None,
-                          self.batch_sz, self.num_prev_maps, self.in_sz, self.pitch, self.num_maps, self.act.kind,
-                          self.act.prm, 1 if out is not self.output else 0)
-            return
-        self.ctx.call("tn_c8_conv_fwd", x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None,
-                      self.batch_sz, self.num_prev_maps, self.pitch, self.pitch, self.num_maps, self.act.kind, self.act.prm,
-                      1 if out is not self.output else 0, self.wt_fwd.ptr if self.wt_valid else None)
-        self._c8_pad_zero(out)
+        x, fam = self._c8_input(), self.c8_fam
+        self.ctx.call(fam.fwd, x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None, *fam.geom,
+                      self.act.kind, self.act.prm, 1 if out is not self.output else 0, *self._c8_tiles(self.wt_fwd))
+        if fam.pad_zero:
+            self._c8_pad_zero(out)
 
     def _c8_backward(self, gout, need_gin, below):
         """gout: d cost / d z of this layer as a c8 tensor carrying the gradient scale -- or, for a fused block, the
         gradient w.r.t. the POOLED output (act' already applied by its producer), dz being formed from it and the
         pooling mask inside the kernels."""
-        pool = self.fused_pool
+        pool, fam = self.fused_pool, self.c8_fam
         pooled, mask = (1, pool.mask.ptr) if pool is not None else (0, None)
         x = self.x16 if self.x16 is not None else self.inpt
-        geom = (self.batch_sz, self.num_prev_maps, self.pitch, self.pitch, self.num_maps)
-        wgrad, dgrad = "tn_c8_conv_wgrad", "tn_c8_conv_dgrad"
-        if self.c8_1x1:
-            geom = (self.batch_sz, self.num_prev_maps, self.in_sz, self.pitch, self.num_maps)
-            wgrad, dgrad = "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad"
         if self.has_updates():
-            self.ctx.call(wgrad, x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *geom, pooled, mask)
+            self.ctx.call(fam.wgrad, x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *fam.geom, pooled, mask)
         if not need_gin:
             return None
         assert self.x16 is None, "DTYPE {}: no trainable layer below the first conv layer".format(self.c8_dtype)
         if self.gin is None:
-            self.gin = C8Array(self.ctx, self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.c8_dtype,
-                               pitch=self.pitch)
-        b_out, b_act, b_prm, b_mask = below.act_info()
+            self.gin = C8Array.like(self.inpt)
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-        if self.c8_1x1:
-            self.ctx.call(dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *geom, b_out.ptr if fuse else None, b_act, b_prm,
-                          pooled, mask)
-            return self.gin
-        self.ctx.call(dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *geom, b_out.ptr if fuse else None,
-                      b_act, b_prm, pooled, mask, self.wt_bwd.ptr if self.wt_valid and self.wt_bwd is not None else None)
-        self._c8_pad_zero(self.gin)
+        self.ctx.call(fam.dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *fam.geom, b_ptr, b_act, b_prm, pooled, mask,
+                      *self._c8_tiles(self.wt_bwd))
+        if fam.pad_zero:
+            self._c8_pad_zero(self.gin)
         return self.gin
 
     def forward(self, train=True):
@@ -247,8 +233,7 @@ class ConvLayer(Layer):
         if self._tile_pool:
             # wide block: dW, db and the input gradient straight from the pooled gradient + mask
             assert pool.mask is not None
-            b_out, b_act, b_prm, b_mask = below.act_info() if (need_gin and below is not None) \
-                else (None, 0, 0., None)
+            b_ptr, b_act, b_prm, b_mask = below_info(below if need_gin else None)
             assert b_mask is None
             if need_gin and self.gin is None:
                 self.gin = self.ctx.empty(self.inpt.shape)
@@ -256,16 +241,12 @@ class ConvLayer(Layer):
             self.ctx.call("tn_convpool_bwd_mask_dx", self.inpt.ptr, self.W.ptr, gpool.ptr, pool.output.ptr,
                           pool.mask.ptr, self.gin.ptr if need_gin else None,
                           self.grads[0].ptr if upd else None, self.grads[1].ptr if upd else None,
-                          *self._fused_geom(),
-                          b_out.ptr if b_out is not None and b_act != _lib.TN_ACT_LINEAR else None,
-                          b_act, b_prm)
+                          *self._fused_geom(), b_ptr, b_act, b_prm)
             self._gin_done = True
             return self.gin if need_gin else None
         if pool.mask is not None:
             # the forward recorded where every pooled value came from: no conv recompute
-            b_out, b_act, b_prm, b_mask = below.act_info() if below is not None else (None, 0, 0., None)
-            fuse_below = need_gin and b_out is not None and b_act != _lib.TN_ACT_LINEAR
-            if self.mask_backward_supported(pool) and not fuse_below:
+            if self.mask_backward_supported(pool) and not (need_gin and below_info(below)[0] is not None):
                 # small maps: weight and input gradients as matrix-core products over an
                 # LDS-resident dz, one kernel
                 if need_gin and self.gin is None:
@@ -285,8 +266,7 @@ class ConvLayer(Layer):
         if self.ctx.lib.tn_convblock_supported(self.num_prev_maps, self.num_maps, self.filter_sz,
                                                self.stride, pool.pool_sz, self.out_sz, self.out_sz):
             # LDS-resident variant: dW/db AND the gradient w.r.t. the input in one kernel
-            b_out, b_act, b_prm, b_mask = below.act_info() if below is not None else (None, 0, 0., None)
-            if not (need_gin and b_out is not None and b_act != _lib.TN_ACT_LINEAR):
+            if not (need_gin and below_info(below)[0] is not None):
                 if need_gin and self.gin is None:
                     self.gin = self.ctx.empty(self.inpt.shape)
                 self.ctx.call("tn_convblock_bwd", self.inpt.ptr, self.W.ptr, self.b.ptr, gpool.ptr,
@@ -319,11 +299,9 @@ class ConvLayer(Layer):
             return None
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
-        b_out, b_act, b_prm, b_mask = below.act_info()
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
-        self.ctx.call("tn_conv2d_dgrad", gout.ptr, self.W.ptr, self.gin.ptr, *self._geom(),
-                      b_out.ptr if b_out is not None and b_act != _lib.TN_ACT_LINEAR else None,
-                      b_act, b_prm)
+        self.ctx.call("tn_conv2d_dgrad", gout.ptr, self.W.ptr, self.gin.ptr, *self._geom(), b_ptr, b_act, b_prm)
         return self.gin
 
 
@@ -345,7 +323,7 @@ class PoolLayer(Layer):
         self.args = (num_maps, in_sz, pool_sz, ignore_border)
         self.n_out = num_maps * self.out_sz ** 2
         self.batch_sz = inpt.shape[0]
-        self.f16 = getattr(inpt, "c8", None) is not None      # DTYPE float16: pooled c8 tensor (only as a fused block)
+        self.f16 = is_c8(inpt)      # 16-bit stack: pooled c8 tensor (only as a fused block)
         if self.f16:
             self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem,
                                   pitch=inpt.pitch // 2 if inpt.padded else None)
@@ -365,7 +343,7 @@ class PoolLayer(Layer):
         return PoolLayer(inpt, *self.args)
 
     def act_info(self):
-        """DTYPE float16: the gradient a pooled block receives carries act'(pooled output) (applied by whichever kernel
+        """16-bit stack: the gradient a pooled block receives carries act'(pooled output) (applied by whichever kernel
         produces it, from the block's stored output); fp32 blocks take the derivative from the pooling mask's sign
         bits inside their own backward kernels instead."""
         if self.f16:
@@ -376,7 +354,6 @@ class PoolLayer(Layer):
     def forward(self, train=True):
         conv = self.fused_conv
         if self.f16:
-            assert conv is not None, "DTYPE {}: a PoolLayer must directly follow a ConvLayer".format(self.output.elem)
             if train and self.mask is None:
                 self.mask = self.ctx.empty(self.output.shape, np.uint8)
             return conv._c8_forward(self.output, self.mask if train else None)
@@ -410,7 +387,7 @@ class PoolLayer(Layer):
             return gout               # the conv layer's fused backward consumes d cost / d y
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
-        b_out, b_act, b_prm, b_mask = below.act_info()
+        _, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
         # below.output IS self.inpt, so the activation gradient rides along for free
         self.ctx.call("tn_pool_bwd", self.inpt.ptr, self.output.ptr, gout.ptr, self.gin.ptr,
@@ -429,12 +406,11 @@ class MeanLayer(Layer):
         self.out_sz = 1
         self.n_out = num_maps
         self.batch_sz = inpt.shape[0]
-        # DTYPE float16 / bfloat16: the input is the 16-bit-resident c8 tensor of the conv stack (tn_c8_mean_*); the
-        # output stays the fp32 (N, C) matrix the dense layers above take
-        self.f16 = getattr(inpt, "c8", None) is not None
-        # ... a padded one (S < pitch) is cropped to a dense tensor first (tn_c8_crop), the gradient embedded back
-        self.dense = C8Array(self.ctx, self.batch_sz, num_maps, in_sz, in_sz, inpt.elem) \
-            if self.f16 and inpt.padded else None
+        # 16-bit stack: the input is the 16-bit-resident c8 tensor of the conv stack (tn_c8_mean_*); the output stays
+        # the fp32 (N, C) matrix the dense layers above take
+        self.f16 = is_c8(inpt)
+        # ... a padded one (S < pitch) goes through a dense copy, the gradient back into the padded layout
+        self.detour = DenseDetour(inpt) if self.f16 else None
         self.output = self.ctx.empty((self.batch_sz, num_maps))
         self.gin = None
         self.representation = (
@@ -446,49 +422,25 @@ class MeanLayer(Layer):
 
     def forward(self, train=True):
         if self.f16:
-            x = self.inpt
-            if self.dense is not None:
-                x = self.dense
-                self.ctx.call("tn_c8_crop", self.inpt.ptr, x.ptr, self.batch_sz, self.num_maps, self.in_sz,
-                              self.inpt.pitch)
-            self.ctx.call("tn_c8_mean_fwd", x.ptr, self.output.ptr, self.batch_sz, self.num_maps,
+            self.ctx.call("tn_c8_mean_fwd", self.detour.crop().ptr, self.output.ptr, self.batch_sz, self.num_maps,
                           self.in_sz, self.in_sz)
             return
         self.ctx.call("tn_mean_fwd", self.inpt.ptr, self.output.ptr,
                       self.batch_sz * self.num_maps, self.in_sz * self.in_sz)
 
-    def _c8_backward(self, gout, below):
-        """The c8 gradient of the block below (an unpooled ConvLayer, or a fused 2x2 PoolLayer standing for its block):
-        grad_scale * gout / (H W) * act'(its stored output), rounded when stored."""
-        if self.gin is None:
-            self.gin = C8Array(self.ctx, self.batch_sz, self.num_maps, self.in_sz, self.in_sz, self.inpt.elem,
-                               pitch=self.inpt.pitch)
-            self._gin_dense = self.gin if self.dense is None else \
-                C8Array(self.ctx, self.batch_sz, self.num_maps, self.in_sz, self.in_sz, self.inpt.elem)
-        b_out, b_act, b_prm, b_mask = below.act_info()
-        assert b_mask is None
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-        if fuse and self.dense is not None:
-            assert b_out is self.inpt
-            b_out = self.dense                  # act' from the cropped copy of the block's output (same values)
-        self.ctx.call("tn_c8_mean_bwd", gout.ptr, self._gin_dense.ptr, self.batch_sz, self.num_maps, self.in_sz,
-                      self.in_sz, b_out.ptr if fuse else None, b_act, b_prm)
-        if self.dense is not None:
-            self.ctx.call("tn_c8_embed", self._gin_dense.ptr, self.gin.ptr, self.batch_sz, self.num_maps, self.in_sz,
-                          self.gin.pitch)
-        return self.gin
-
     def backward(self, gout, need_gin, below):
         if not need_gin:
             return None
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
+        assert b_mask is None
         if self.f16:
-            return self._c8_backward(gout, below)
+            # the c8 gradient of the block below (an unpooled ConvLayer, or a fused 2x2 PoolLayer standing for its
+            # block): grad_scale * gout / (H W) * act'(its stored output), rounded when stored
+            self.ctx.call("tn_c8_mean_bwd", gout.ptr, self.detour.dense_gin().ptr, self.batch_sz, self.num_maps,
+                          self.in_sz, self.in_sz, self.detour.act_ptr(b_ptr), b_act, b_prm)
+            return self.detour.embed()
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
-        b_out, b_act, b_prm, b_mask = below.act_info()
-        assert b_mask is None
         self.ctx.call("tn_mean_bwd", gout.ptr, self.gin.ptr, self.batch_sz * self.num_maps,
-                      self.in_sz * self.in_sz,
-                      b_out.ptr if b_out is not None and b_act != _lib.TN_ACT_LINEAR else None,
-                      b_act, b_prm)
+                      self.in_sz * self.in_sz, b_ptr, b_act, b_prm)
         return self.gin

@@ -18,8 +18,8 @@ the block's only where the mask is zero) and rounded once.
 import numpy as np
 
 from .. import _lib
-from ..device import C8Array
-from .layer import Layer
+from ..device import C8Array, is_c8
+from .layer import Layer, below_info
 
 
 class DropStream:
@@ -29,11 +29,14 @@ class DropStream:
         self.ctx, self.shape, self.pdrop = ctx, tuple(shape), float(pdrop)
         self.seed = int(rand_gen.randint(1e6)) if rand_gen is not None \
             else int(np.random.randint(0, 1e6))
-        self.mask = ctx.empty(shape, np.uint8)
+        self.mask = self._new_mask()
         self.injected = False
         self.ready = False          # mask of the current step already generated (side stream)
         self.d_step = None          # device step counter (set by the net)
         self.elem0 = 0              # global index of this shard's first element
+
+    def _new_mask(self):
+        return self.ctx.empty(self.shape, np.uint8)
 
     def inject(self, mask):
         """Parity hook: use this host mask (0/1) instead of the device RNG.
@@ -60,16 +63,12 @@ class C8DropStream(DropStream):
     draw happens inside tn_c8_dropout_fwd: nothing is generated ahead of the forward."""
 
     def __init__(self, ctx, shape, pitch, pdrop, rand_gen=None):
-        self.ctx, self.shape, self.pdrop = ctx, tuple(shape), float(pdrop)
-        self.seed = int(rand_gen.randint(1e6)) if rand_gen is not None \
-            else int(np.random.randint(0, 1e6))
-        n, c, s, _ = self.shape
         self.pitch = int(pitch)
-        self.mask = ctx.zeros((n, (c + 7) // 8, self.pitch, self.pitch), np.uint8)
-        self.injected = False
-        self.ready = False
-        self.d_step = None
-        self.elem0 = 0
+        DropStream.__init__(self, ctx, shape, pdrop, rand_gen)
+
+    def _new_mask(self):
+        n, c, s, _ = self.shape
+        return self.ctx.zeros((n, (c + 7) // 8, self.pitch, self.pitch), np.uint8)
 
     def inject(self, mask):
         """Parity hook: the same NCHW 0/1 host array the fp32 layer takes, packed to cell bytes.  None: back to the
@@ -110,13 +109,13 @@ class DropOutLayer(Layer):
         self.pdrop = pdrop
         self.test_scale = 1.0
         self.drop = None
-        # DTYPE float16 / bfloat16: a 16-bit-resident tensor of the conv stack in, one of the same geometry out
-        self.c8 = getattr(inpt, "c8", None)
+        # 16-bit stack: a 16-bit-resident tensor of the conv stack in, one of the same geometry out
+        self.c8 = inpt.c8 if is_c8(inpt) else None
         self.below = None           # (c8) the layer below, set by the net: act_info() looks through to it
         if pdrop and self.c8 is not None:
             c, s, _ = self.c8
             self.drop = C8DropStream(self.ctx, (inpt.shape[0], c, s, s), inpt.pitch, pdrop, rand_gen)
-            self.output = self._c8_like(inpt)
+            self.output = C8Array.like(inpt)
         elif pdrop:
             drop_output(self, inpt, pdrop, rand_gen)
             self.output = self.ctx.empty(inpt.shape)
@@ -129,12 +128,8 @@ class DropOutLayer(Layer):
         test_version = DropOutLayer(inpt, n_in=self.n_in, pdrop=0)
         if self.pdrop:
             test_version.test_scale = 1 - self.pdrop
-            test_version.output = self._c8_like(inpt) if test_version.c8 is not None else self.ctx.empty(inpt.shape)
+            test_version.output = C8Array.like(inpt) if is_c8(inpt) else self.ctx.empty(inpt.shape)
         return test_version
-
-    def _c8_like(self, t):
-        c, s, _ = t.c8
-        return C8Array(self.ctx, t.shape[0], c, s, s, t.elem, pitch=t.pitch)
 
     def _c8_geom(self):
         c, s, _ = self.c8
@@ -175,9 +170,8 @@ class DropOutLayer(Layer):
             if self.drop is not None:
                 self.ctx.call("tn_c8_dropout_bwd", gout.ptr, self.drop.mask.ptr, gout.ptr, *self._c8_geom())
             return gout
-        b_out, b_act, b_prm, b_mask = below.act_info()
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-        if self.drop is None and not fuse and b_mask is None:
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
+        if self.drop is None and b_ptr is None and b_mask is None:
             return gout
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
@@ -187,5 +181,5 @@ class DropOutLayer(Layer):
                           None, _lib.TN_ACT_LINEAR, 0.0)
             src = self.gin
         self.ctx.call("tn_scale_mask", src.ptr, self.drop.mask.ptr if self.drop else None, 1.0,
-                      self.gin.ptr, self.inpt.size, b_out.ptr if fuse else None, b_act, b_prm)
+                      self.gin.ptr, self.inpt.size, b_ptr, b_act, b_prm)
         return self.gin

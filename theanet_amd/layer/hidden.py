@@ -5,9 +5,10 @@ output (:31-32); the test version drops the mask and scales by (1 - pdrop)
 (:50-55).  Note the reference's init quirk: fan_in = fan_out = n_in + n_out (:21-27).
 """
 from .. import _lib
-from ..device import C8Array
+from ..device import is_c8
+from .c8 import DenseDetour
 from .dropout import drop_output
-from .layer import Layer, activation_by_name
+from .layer import Layer, activation_by_name, below_info
 from .weights import init_wb
 
 
@@ -33,9 +34,9 @@ class HiddenLayer(Layer):
         self.ctx = self.w.ctx
 
         self.act = activation_by_name(actvn)
-        # DTYPE float16: the layer above the conv stack consumes the c8 tensor as it is stored (tn_c8_fc_* / tn_c8_fcg_*: fp16
-        # operands through the NCHW row map, fp32 output); further dense layers are fp32 like the reference
-        self.c8 = getattr(inpt, "c8", None)
+        # 16-bit stack: the layer above the conv stack consumes the c8 tensor as it is stored (tn_c8_fc_* / tn_c8_fcg_*:
+        # 16-bit operands through the NCHW row map, fp32 output); further dense layers are fp32 like the reference
+        self.c8 = inpt.c8 if is_c8(inpt) else None
         if self.c8 is not None:
             c, h, wd = self.c8
             assert c * h * wd == n_in, (self.c8, n_in)
@@ -48,16 +49,18 @@ class HiddenLayer(Layer):
                 "DTYPE {}: a dense layer of {} samples on {} maps of {}x{} with {} outputs is beyond what the 16-bit dense "
                 "products index (tn_c8_fcg_supported: fewer than 2^31 input, output and weight elements)".format(
                     inpt.elem, inpt.shape[0], c, h, wd, n_out))
-            self.inpt = inpt
             # a padded stack tensor (maps stored at a pitch > their side): the products read a dense copy, cropped in
-            # front of them (tn_c8_crop); the input gradient is embedded back into the padded layout (tn_c8_embed)
+            # front of them; the input gradient is embedded back into the padded layout
+            self.detour = DenseDetour(inpt)
+            self.inpt = self.detour.dense
             self.c8_src = inpt if inpt.padded else None
-            if self.c8_src is not None:
-                self.inpt = C8Array(self.ctx, inpt.shape[0], c, h, wd, inpt.elem)
         else:
             self.inpt = inpt.flatten(2)
             assert self.inpt.shape[1] == n_in, (self.inpt.shape, n_in)
         self.batch_sz = self.inpt.shape[0]
+        # the forward ops and the shape they take
+        self._fc = (self.c8_fc, (self.batch_sz, c, h * wd, n_out)) if self.c8 is not None else \
+            ("tn_fc", (self.batch_sz, n_in, n_out))
         self.output = self.ctx.empty((self.batch_sz, n_out))
         self.drop = None
         self.test_scale = 1.0
@@ -93,33 +96,19 @@ class HiddenLayer(Layer):
                 self.drop.mask if self.drop is not None else None)
 
     def forward(self, train=True):
-        drop = self.drop
+        drop, (op, shape) = self.drop, self._fc
         if self.c8 is not None:
-            c, h, wd = self.c8
-            if self.c8_src is not None:
-                self.ctx.call("tn_c8_crop", self.c8_src.ptr, self.inpt.ptr, self.batch_sz, c, h, self.c8_src.pitch)
-            if drop is not None and not drop.injected and not drop.ready:
-                # the mask is drawn by the product's finishing kernel (and kept for the backward pass)
-                self.ctx.call(self.c8_fc + "_fwd_dropout", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz,
-                              c, h * wd, self.n_out, self.act.kind, self.act.prm, drop.mask.ptr, drop.pdrop, drop.seed, 0,
-                              drop.d_step.ptr if drop.d_step is not None else None, drop.elem0)
-            else:
-                if drop is not None:
-                    drop.generate()
-                self.ctx.call(self.c8_fc + "_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, self.batch_sz, c, h * wd,
-                              self.n_out, self.act.kind, self.act.prm, drop.mask.ptr if drop is not None else None)
-        elif drop is not None and not drop.injected and not drop.ready:
+            self.detour.crop()
+        if drop is not None and not drop.injected and not drop.ready:
             # the mask is drawn inside the layer's own launch (and kept for the backward pass)
-            self.ctx.call("tn_fc_fwd_dropout", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr,
-                          self.batch_sz, self.n_in, self.n_out, self.act.kind, self.act.prm,
-                          drop.mask.ptr, drop.pdrop, drop.seed, 0,
+            self.ctx.call(op + "_fwd_dropout", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, *shape,
+                          self.act.kind, self.act.prm, drop.mask.ptr, drop.pdrop, drop.seed, 0,
                           drop.d_step.ptr if drop.d_step is not None else None, drop.elem0)
         else:
             if drop is not None:
                 drop.generate()
-            self.ctx.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr,
-                          self.batch_sz, self.n_in, self.n_out, self.act.kind, self.act.prm,
-                          drop.mask.ptr if drop is not None else None)
+            self.ctx.call(op + "_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, *shape,
+                          self.act.kind, self.act.prm, drop.mask.ptr if drop is not None else None)
         if self.test_scale != 1.0:
             self.ctx.call("tn_scale_mask", self.output.ptr, None, float(self.test_scale),
                           self.output.ptr, self.output.size, None, _lib.TN_ACT_LINEAR, 0.0)
@@ -127,57 +116,35 @@ class HiddenLayer(Layer):
     def backward(self, gout, need_gin, below):
         """gout = d cost / d z (activation gradient and dropout mask already applied)."""
         if self.c8 is not None:
-            c, h, wd = self.c8
+            shape = self._fc[1]
             if self.has_updates():
-                self.ctx.call(self.c8_fc + "_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr,
-                              self.batch_sz, c, h * wd, self.n_out)
+                self.ctx.call(self.c8_fc + "_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *shape)
             if not need_gin:
                 return None
-            src = self.c8_src
-            if self.gin is None:
-                self.gin = C8Array(self.ctx, self.batch_sz, c, h, wd, self.inpt.elem)
-                self._gin_padded = None if src is None else \
-                    C8Array(self.ctx, self.batch_sz, c, h, wd, self.inpt.elem, pitch=src.pitch)
-            b_out, b_act, b_prm, b_mask = below.act_info()
+            b_ptr, b_act, b_prm, b_mask = below_info(below)
             assert b_mask is None
-            fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-            if fuse and src is not None:
-                assert b_out is src
-                b_out = self.inpt                   # act' from the cropped copy of the block's output (same values)
-            self.ctx.call(self.c8_fc + "_dgrad", gout.ptr, self.w.ptr, self.gin.ptr, self.batch_sz, c, h * wd, self.n_out,
-                          b_out.ptr if fuse else None, b_act, b_prm)
-            if src is None:
-                return self.gin
-            self.ctx.call("tn_c8_embed", self.gin.ptr, self._gin_padded.ptr, self.batch_sz, c, h, src.pitch)
-            return self._gin_padded
-        if self.has_updates() and need_gin:
-            # weight gradient and input gradient only share dz: one op, one launch
-            if self.wgrad_ws is None:
-                nbytes = self.ctx.lib.tn_fc_wgrad_ws_bytes(self.batch_sz, self.n_in, self.n_out)
-                self.wgrad_ws = self.ctx.empty((nbytes + 3) // 4)
-            if self.gin is None:
-                self.gin = self.ctx.empty(self.inpt.shape)
-            b_out, b_act, b_prm, b_mask = below.act_info()
-            fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-            self.ctx.call("tn_fc_bwd", self.inpt.ptr, gout.ptr, self.w.ptr, self.grads[0].ptr,
-                          self.grads[1].ptr, self.gin.ptr, self.batch_sz, self.n_in, self.n_out,
-                          self.wgrad_ws.ptr, b_out.ptr if fuse else None, b_act, b_prm,
-                          b_mask.ptr if b_mask is not None else None)
-            return self.gin
-        if self.has_updates():
-            if self.wgrad_ws is None:
-                nbytes = self.ctx.lib.tn_fc_wgrad_ws_bytes(self.batch_sz, self.n_in, self.n_out)
-                self.wgrad_ws = self.ctx.empty((nbytes + 3) // 4)
-            self.ctx.call("tn_fc_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr,
-                          self.grads[1].ptr, self.batch_sz, self.n_in, self.n_out,
-                          self.wgrad_ws.ptr)
+            self.ctx.call(self.c8_fc + "_dgrad", gout.ptr, self.w.ptr, self.detour.dense_gin().ptr, *shape,
+                          self.detour.act_ptr(b_ptr), b_act, b_prm)
+            return self.detour.embed()
+        upd = self.has_updates()
+        if upd and self.wgrad_ws is None:
+            nbytes = self.ctx.lib.tn_fc_wgrad_ws_bytes(self.batch_sz, self.n_in, self.n_out)
+            self.wgrad_ws = self.ctx.empty((nbytes + 3) // 4)
         if not need_gin:
+            if upd:
+                self.ctx.call("tn_fc_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr,
+                              self.grads[1].ptr, self.batch_sz, self.n_in, self.n_out, self.wgrad_ws.ptr)
             return None
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
-        b_out, b_act, b_prm, b_mask = below.act_info()
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
-        self.ctx.call("tn_fc_dgrad", gout.ptr, self.w.ptr, self.gin.ptr, self.batch_sz, self.n_in,
-                      self.n_out, b_out.ptr if fuse else None, b_act, b_prm,
-                      b_mask.ptr if b_mask is not None else None)
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
+        b_mask = b_mask.ptr if b_mask is not None else None
+        if upd:
+            # weight gradient and input gradient only share dz: one op, one launch
+            self.ctx.call("tn_fc_bwd", self.inpt.ptr, gout.ptr, self.w.ptr, self.grads[0].ptr,
+                          self.grads[1].ptr, self.gin.ptr, self.batch_sz, self.n_in, self.n_out,
+                          self.wgrad_ws.ptr, b_ptr, b_act, b_prm, b_mask)
+        else:
+            self.ctx.call("tn_fc_dgrad", gout.ptr, self.w.ptr, self.gin.ptr, self.batch_sz, self.n_in,
+                          self.n_out, b_ptr, b_act, b_prm, b_mask)
         return self.gin

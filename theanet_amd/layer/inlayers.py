@@ -11,7 +11,7 @@ injected by a parity test (``inject``).  The test version is identity + invert
 """
 import numpy as np
 
-from .layer import Layer
+from .layer import Layer, below_info
 
 
 class InputSlot:
@@ -48,7 +48,7 @@ class InputLayer(Layer):
     def TestVersion(self, inpt):
         return InputLayer(inpt, self.out_sz, self.num_maps)
 
-    _packed_by_conv = False     # DTYPE float16: the first conv layer reads the dataset window itself (tn_c8_pack)
+    _packed_by_conv = False     # 16-bit stack: the first conv layer reads the dataset window itself (tn_c8_pack)
 
     def forward(self, train=True):
         s = self.inpt
@@ -163,7 +163,7 @@ class ElasticLayer(Layer):
             self._inj_flip = self.ctx.array(
                 np.asarray(flipmask).reshape(self.output.shape).astype(np.uint8))
 
-    _c8_consumer = None     # DTYPE float16: the first conv layer, whose c8 input this stage writes (NeuralNet._fuse)
+    _c8_consumer = None     # 16-bit stack: the first conv layer, whose c8 input this stage writes (NeuralNet._fuse)
 
     def forward(self, train=True):
         s = self.inpt
@@ -204,7 +204,7 @@ class ElasticLayer(Layer):
         if self.fused_conv is not None and train:
             return                      # the conv block's forward resamples while it loads (PoolLayer)
         if self._c8_consumer is not None:
-            # DTYPE float16: straight into the c8 tensor of the first conv layer (same values, rounded when stored)
+            # 16-bit stack: straight into the c8 tensor of the first conv layer (same values, rounded when stored)
             a = self._apply_args
             self.ctx.call("tn_c8_elastic_apply", *(a[:3] + (self._c8_consumer.x16.ptr,) + a[4:]))
             return
@@ -216,20 +216,17 @@ class ElasticLayer(Layer):
         if not need_gin or isinstance(self.inpt, InputSlot):
             return None
         from .. import _lib
-        b_out, b_act, b_prm, b_mask = below.act_info()
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
         if getattr(self, "gin", None) is None:
             self.gin = self.ctx.empty(self.inpt.shape)
         h = w = self.img_sz
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
         if self.active:
             a = self._apply_args
             self.ctx.call("tn_elastic_apply_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps, h, w,
-                          a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[16], a[17], a[18],
-                          b_out.ptr if fuse else None, b_act, b_prm)
+                          a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[16], a[17], a[18], b_ptr, b_act, b_prm)
         else:
             self.ctx.call("tn_elastic_apply_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps, h, w,
-                          int(self.invert), 1, None, None, None, 0.0, None, 0, 0, None, 0,
-                          b_out.ptr if fuse else None, b_act, b_prm)
+                          int(self.invert), 1, None, None, None, 0.0, None, 0, 0, None, 0, b_ptr, b_act, b_prm)
         if b_mask is not None:        # a Hidden layer with dropout right below: its mask, after the copy
             self.ctx.call("tn_scale_mask", self.gin.ptr, b_mask.ptr, 1.0, self.gin.ptr, self.gin.size,
                           None, _lib.TN_ACT_LINEAR, 0.0)
@@ -326,17 +323,14 @@ class ColorLayer(Layer):
         if not need_gin or isinstance(self.inpt, InputSlot):
             return None
         from .. import _lib
-        b_out, b_act, b_prm, b_mask = below.act_info()
-        fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
+        b_ptr, b_act, b_prm, b_mask = below_info(below)
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
         if not self.active:
-            self.ctx.call("tn_scale_mask", gout.ptr, None, 1.0, self.gin.ptr, self.gin.size,
-                          b_out.ptr if fuse else None, b_act, b_prm)
+            self.ctx.call("tn_scale_mask", gout.ptr, None, 1.0, self.gin.ptr, self.gin.size, b_ptr, b_act, b_prm)
         else:
             self.ctx.call("tn_color_apply_bwd", self.inpt.ptr, 0, self.fac.ptr, gout.ptr, self.gin.ptr,
-                          self.batch_sz, self.num_maps, self.out_sz * self.out_sz, float(self.maxval),
-                          b_out.ptr if fuse else None, b_act, b_prm)
+                          self.batch_sz, self.num_maps, self.out_sz * self.out_sz, float(self.maxval), b_ptr, b_act, b_prm)
         if b_mask is not None:        # a Hidden layer with dropout right below: its mask, after the copy
             self.ctx.call("tn_scale_mask", self.gin.ptr, b_mask.ptr, 1.0, self.gin.ptr, self.gin.size,
                           None, _lib.TN_ACT_LINEAR, 0.0)

@@ -46,6 +46,16 @@ def activation_by_name(name):
     raise NotImplementedError("Unknown Activation Specified: " + name)
 
 
+def below_info(below):
+    """What a backward kernel fuses in for the layer ``below`` (None: nothing): (pointer of the output act' is taken
+    from, or None when there is none to apply; activation kind; its parameter; dropout mask or None)."""
+    if below is None:
+        return None, _lib.TN_ACT_LINEAR, 0., None
+    b_out, b_act, b_prm, b_mask = below.act_info()
+    fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
+    return b_out.ptr if fuse else None, b_act, b_prm, b_mask
+
+
 class Layer:
     """Base class.  Sub-classes set: params (list of DeviceArray), output
     (DeviceArray), representation, and optionally reg / actvn / mask."""

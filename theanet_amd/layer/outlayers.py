@@ -12,6 +12,7 @@ import numpy as np
 
 from .. import _lib
 from .hidden import HiddenLayer
+from .layer import below_info
 
 
 HEAD_SOFTMAX, HEAD_EXPLOSS, HEAD_HINGE, HEAD_LOGIT, HEAD_RBF = range(5)
@@ -147,14 +148,13 @@ class SoftmaxLayer(HiddenLayer, OutputLayer):
                 self.wgrad_ws = self.ctx.empty((nbytes + 3) // 4)
             if self.gin is None:
                 self.gin = self.ctx.empty(self.inpt.shape)
-            b_out, b_act, b_prm, b_mask = below.act_info()
-            fuse = b_out is not None and b_act != _lib.TN_ACT_LINEAR
+            b_ptr, b_act, b_prm, b_mask = below_info(below)
             self.ctx.call("tn_fc_softmax_train", self.inpt.ptr, self.w.ptr, self.b.ptr, self.logits.ptr,
                           self.batch_sz, self.n_in, self.n_out, y.ptr, int(y_row0),
                           d_row0.ptr if d_row0 is not None else None, self.logprob.ptr,
                           self.rowloss.ptr, self.y_preds.ptr, self.rowp.ptr, self.dlogits.ptr,
                           float(self.inv_batch), self.grads[0].ptr, self.grads[1].ptr, self.gin.ptr,
-                          self.wgrad_ws.ptr, b_out.ptr if fuse else None, b_act, b_prm,
+                          self.wgrad_ws.ptr, b_ptr, b_act, b_prm,
                           b_mask.ptr if b_mask is not None else None)
             self._bwd_done = True
             return

@@ -21,7 +21,8 @@ import numpy as np
 
 from . import _lib, comm, layer
 from .plan import StepPlan
-from .device import C8_DTYPES, DeviceArray, get_context, share
+from .device import DeviceArray, get_context, is_c8, share
+from .layer.c8 import OperandTiles, check_follows
 from .layer import (AuxConcatLayer, SoftAuxLayer, CenteredOutLayer, ColorLayer, ConvLayer, DropOutLayer, ElasticLayer, ExpLossLayer, HiddenLayer,
                     HingeLayer, InputLayer, InputSlot, MeanLayer, OutputLayer, PoolLayer, SoftmaxLayer)
 
@@ -151,6 +152,7 @@ class NeuralNet():
             self.test_x.bind(share(test_x))
 
         # device-side step state (read by the kernels, so a captured graph can be replayed)
+        self._c8_tiles = OperandTiles(self.ctx)            # the 16-bit stack's 3x3 conv weights as operand tiles
         self.d_step = self.ctx.zeros((1,), np.uint32)       # RNG step counter
         self.d_row0 = self.ctx.zeros((1,), np.int64)        # first dataset row of the minibatch
         self.cur_learn_rate = self.ctx.zeros((1,), np.float32)
@@ -212,6 +214,9 @@ class NeuralNet():
         tr_inpt = prev_tr_layer.output
         te_inpt = prev_te_layer.output
         curr_layer_type = getattr(layer, layer_type)
+        if is_c8(tr_inpt):
+            # 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to layer as they are
+            check_follows(self.dtype, prev_tr_layer, layer_type, layer_args.get("pool_sz"), self.fuse_conv_pool)
 
         if curr_layer_type in (ElasticLayer, ColorLayer, ConvLayer, PoolLayer, MeanLayer):
             use_tr_layer, k = prev_tr_layer, self.num_layers - 1
@@ -220,17 +225,7 @@ class NeuralNet():
                 use_tr_layer = self.tr_layers[k]
             num_prev_maps = use_tr_layer.num_maps
             prev_out_sz = use_tr_layer.out_sz
-            if getattr(tr_inpt, "c8", None) is not None:
-                # DTYPE float16 / bfloat16: 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to
-                # layer as they are (a DropOutLayer too: the branch below); a MeanLayer closes the stack with an fp32
-                # (N, C) output
-                assert curr_layer_type in (ConvLayer, PoolLayer, MeanLayer), \
-                    "DTYPE {}: only Conv / Pool / Mean / DropOut layers take the conv stack's 16-bit-resident tensors " \
-                    "(got {})".format(self.dtype, layer_type)
-                assert not (curr_layer_type is PoolLayer and type(prev_tr_layer) is DropOutLayer), \
-                    "DTYPE {}: a DropOutLayer between a ConvLayer and its PoolLayer breaks the fused conv + pool block " \
-                    "of the 16-bit stack; put the DropOutLayer after the PoolLayer".format(self.dtype)
-            elif tr_inpt.ndim != 4:
+            if not is_c8(tr_inpt) and tr_inpt.ndim != 4:
                 tr_inpt = tr_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
                 te_inpt = te_inpt.reshape(self.local_bsz, num_prev_maps, prev_out_sz, prev_out_sz)
 
@@ -251,6 +246,7 @@ class NeuralNet():
                                    self.local_bsz,
                                    num_prev_maps,
                                    prev_out_sz,
+                                   dtype=self.dtype,
                                    **layer_args)
 
         elif curr_layer_type in (PoolLayer, MeanLayer):
@@ -280,14 +276,12 @@ class NeuralNet():
                                           prev_tr_layer.n_out,
                                           **layer_args)
 
-        elif curr_layer_type is HiddenLayer and getattr(tr_inpt, "c8", None) is not None:
-            # DTYPE float16: the dense layer above the conv stack reads the fp16-resident tensor in ITS order (the
+        elif curr_layer_type is HiddenLayer and is_c8(tr_inpt):
+            # 16-bit stack: the dense layer above the conv stack reads the 16-bit-resident tensor in ITS order (the
             # kernels walk W through the NCHW row map of flatten(2), neuralnet.py:168-173)
             curr_layer = HiddenLayer(tr_inpt, wts, self.rand_gen, prev_tr_layer.n_out, **layer_args)
 
         elif curr_layer_type in (AuxConcatLayer, HiddenLayer, SoftmaxLayer, SoftAuxLayer, HingeLayer, ExpLossLayer):
-            assert getattr(tr_inpt, "c8", None) is None, \
-                "DTYPE {}: a HiddenLayer must follow the conv stack (got {})".format(self.dtype, layer_type)
             te_inpt = te_inpt.flatten(2)
             curr_layer = curr_layer_type(tr_inpt.flatten(2),
                                          wts,
@@ -311,10 +305,7 @@ class NeuralNet():
             if isinstance(conv, ConvLayer) and isinstance(pool, PoolLayer) \
                     and conv.can_fuse_with(pool):
                 conv.fused_pool, pool.fused_conv = pool, conv
-        for lyr in lyrs:
-            assert not (isinstance(lyr, PoolLayer) and lyr.f16 and lyr.fused_conv is None), \
-                "DTYPE {}: a PoolLayer must directly follow a ConvLayer".format(lyr.output.elem)
-        # DTYPE float16: the first conv layer packs its c8 input straight from the dataset window
+        # 16-bit stack: the first conv layer packs its c8 input straight from the dataset window
         if len(lyrs) >= 2 and isinstance(lyrs[0], InputLayer) and isinstance(lyrs[1], ConvLayer) and lyrs[1].f16:
             lyrs[1]._pack_from, lyrs[0]._packed_by_conv = lyrs[0].inpt, True
         # ... or has it written by the distortion stage below it (tn_c8_elastic_apply): no fp32 image, no packing pass
@@ -593,8 +584,7 @@ class NeuralNet():
             self._dp_tune_tick()
         if self._dp_can_delay:
             self._dp_bind(self._dp_cur if self._dp_delayed else 0)
-        if self.dtype in C8_DTYPES:
-            self._c8_arrange(self.tr_layers, True)
+        self._c8_tiles.arrange(self.tr_layers, self._need_gin)
         for lyr in self.tr_layers[:-1]:
             lyr.forward(True)
         # the weight-gradient ops only record their finishing slab sums; one launch does them all
@@ -725,8 +715,7 @@ class NeuralNet():
                 self._group().allreduce_sum_async(self.flat_grads, n, getattr(self, "_ar_done_ev", None))
             if ahead:
                 first._cur, first._pre_valid = nxt, True
-            if self.dtype in C8_DTYPES:
-                self._c8_stale()
+            self._c8_tiles.stale()
             return
         delayed = self._dp_delayed
         if delayed and tail:
@@ -787,8 +776,7 @@ class NeuralNet():
             first._cur, first._pre_valid = nxt, True
         if not mn_done:
             self._apply_maxnorm_all()
-        if self.dtype in C8_DTYPES:
-            self._c8_stale()
+        self._c8_tiles.stale()
 
     def _update_and_maxnorm(self, *args):
         """Layer.get_updates of every tensor (layer.py:70-107) as ONE call: tn_sgd_update_net + the max-norm projection,
@@ -816,41 +804,6 @@ class NeuralNet():
                     getattr(lyr, "_inj", None) is not None or getattr(lyr, "_inj_flip", None) is not None:
                 return True
         return False
-
-    def _c8_arrange(self, lyrs, train):
-        """DTYPE float16: the conv layers' weights as fp16 MFMA operand tiles, all products of the pass in ONE launch
-        (tn_c8_arrange_multi); valid until the next update (_c8_stale)."""
-        key = "_c8_tab_tr" if train else "_c8_tab_te"
-        tab = getattr(self, key, None)
-        if tab is None:
-            dt = np.dtype([('W', 'u8'), ('wt', 'u8'), ('K', 'i4'), ('C', 'i4'), ('dgrad', 'i4'), ('pad', 'i4')])
-            assert dt.itemsize == 32          # tn_c8_wt_seg
-            rows, convs = [], []
-            for idx, lyr in enumerate(lyrs):
-                if isinstance(lyr, ConvLayer) and lyr.f16 and not lyr.c8_1x1:      # (K, C, 3, 3) weights only
-                    convs.append(lyr)
-                    rows.append((lyr.W.ptr, lyr.wt_fwd.ptr, lyr.num_maps, lyr.num_prev_maps, 0, 0))
-                    if train and self._need_gin[idx]:
-                        if lyr.wt_bwd is None:
-                            n = self.ctx.lib.tn_c8_wt_elems(lyr.num_maps, lyr.num_prev_maps, 1)
-                            lyr.wt_bwd = self.ctx.empty((n,), np.uint16)
-                        rows.append((lyr.W.ptr, lyr.wt_bwd.ptr, lyr.num_maps, lyr.num_prev_maps, 1, 0))
-            tab = (np.array(rows, dtype=dt) if rows else np.zeros((0,), dt), convs)
-            setattr(self, key, tab)
-        segs, convs = tab
-        for i in range(0, len(segs), 32):
-            chunk = segs[i:i + 32]
-            self.ctx.call("tn_c8_arrange_multi", chunk.ctypes.data, len(chunk))
-        for lyr in convs:
-            lyr.wt_valid = True
-
-    def _c8_stale(self):
-        """The weights are about to change: the arranged operand tiles of both graphs are no longer theirs."""
-        for key in ("_c8_tab_tr", "_c8_tab_te"):
-            tab = getattr(self, key, None)
-            if tab is not None:
-                for lyr in tab[1]:
-                    lyr.wt_valid = False
 
     def _apply_maxnorm_all(self):
         """layer.py:88-103 for every parameter of the net in ONE call (tn_maxnorm_multi: the biases and conv kernels
@@ -978,8 +931,7 @@ class NeuralNet():
         def fn(x, aux=None):
             self._sync_weights()
             self._apply_dtype()
-            if self.dtype in C8_DTYPES:
-                self._c8_arrange(self.te_layers, False)
+            self._c8_tiles.arrange(self.te_layers)
             x = np.ascontiguousarray(x, np.float32).reshape(stage.shape)
             stage.set_value(x)
             if self.takes_aux():                           # neuralnet.py:289-290

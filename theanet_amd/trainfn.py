@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .device import C8_DTYPES, share  # noqa: F401
+from .device import share  # noqa: F401
 from .layer import ElasticLayer
 from .plan import StepPlan
 
@@ -663,8 +663,7 @@ class _TestFn:
         _batch_in_range(i, self.x_data.shape[0], net.batch_sz)
         net._sync_weights()
         net._apply_dtype()
-        if net.dtype in C8_DTYPES:
-            net._c8_arrange(net.te_layers, False)
+        net._c8_tiles.arrange(net.te_layers)
         slot = net.test_x
         slot.bind(self.x_data)
         slot.row0 = int(i) * net.batch_sz + net.shard_lo
