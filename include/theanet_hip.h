@@ -173,6 +173,21 @@ int tn_get_matmul_dtype(tn_ctx* ctx);
  * to the generic products), tn_softmax_nll*, tn_head_rows.  theanet_amd/csrc/gemm_bf16.hip.
  * Modes other than 0 / 1 / 2 are refused; the CPU backend accepts 0 only.                                          */
 int tn_set_fc_matmul(tn_ctx* ctx, int mode);
+/* CONV 'bfloat16' (opt-in, this build's extension; the reference's conv products are float32, convpool.py:54-72): mode 2
+ * runs tn_conv2d_fwd / tn_conv2d_wgrad / tn_conv2d_dgrad -- the call sites convpool.py:54-72 and their gradients -- of
+ * EVERY geometry those entry points take (any N, C, K, any square filter, 'valid' / 'same', any stride, any map size;
+ * nothing falls back to the fp32 kernels) with both operands rounded to bf16 (nearest even) as they are staged, exact
+ * products, fp32 accumulation on v_mfma_f32_32x32x16_bf16 and the fp32 epilogues of mode 0 (bias + activation; act' of
+ * prev_a, NULL: none).  Tensors in memory stay fp32 NCHW; db is the fp32 sum of the unrounded dz; the weight gradient's
+ * pixel slabs meet in context scratch and are summed in slab order (no atomics: the same call gives the same bits).  A
+ * reduced-precision mode (~2^-9 relative per operand).  theanet_amd/csrc/conv_bf16.hip.  In mode 2 the three entry points
+ * answer TN_E_ARG by name, nothing launched, for a NULL tensor, a dimension < 1 and shapes whose index arithmetic would
+ * overflow 32 bits (N*C*H*W, N*K*Ho*Wo or K*C*f*f >= 2^31).  Mode 0 issues exactly the calls issued without this entry
+ * point.  The fused block entry points (tn_convpool_*, tn_convblock_*, tn_elastic_convpool_*) are NOT part of the mode:
+ * they compute in fp32 whatever it is, and a net under CONV 'bfloat16' does not use them.  Mode 2 is refused (TN_E_ARG)
+ * while a 16-bit DTYPE is set (tn_set_matmul_dtype 1 / 2: that stack already runs 16-bit products); modes other than
+ * 0 / 2 are refused (they are numbered as tn_set_fc_matmul numbers them); the CPU backend accepts 0 only.           */
+int tn_set_conv_matmul(tn_ctx* ctx, int mode);
 
 /* ---- DTYPE 'float16' on fp16-RESIDENT tensors (theanet_amd/csrc/conv_c8.hip, fc_c8.hip) --------------------
  * (DTYPE 'bfloat16', tn_set_matmul_dtype mode 2: everything below with bf16 in place of half; the shape predicates and

@@ -84,6 +84,7 @@ SIGNATURES = {
     "tn_set_matmul_dtype": (c_int, [CTX, c_int, c_float]),
     "tn_get_matmul_dtype": (c_int, [CTX]),
     "tn_set_fc_matmul": (c_int, [CTX, c_int]),
+    "tn_set_conv_matmul": (c_int, [CTX, c_int]),
     "tn_c8_conv_supported": (c_int, [c_int] * 8),
     "tn_c8_conv_wgrad_supported": (c_int, [c_int] * 5),
     "tn_c8_wt_elems": (c_size_t, [c_int] * 3),

@@ -55,6 +55,7 @@ struct tn_ctx {
     int mm_f16 = 0;
     int fc_b3 = 0;                         // tn_set_fc_matmul: 1 = FC products as bf16 triplets (gemm_b3.hip)
     int fc_bf16 = 0;                       // tn_set_fc_matmul: 2 = FC products on bf16-rounded operands (gemm_bf16.hip)
+    int conv_bf16 = 0;                     // tn_set_conv_matmul: 2 = tn_conv2d_* on bf16-rounded operands (conv_bf16.hip)
     float grad_scale = 1.f;
     char err[512] = {0};
     // RCCL (loaded lazily, comm.hip)
@@ -110,6 +111,14 @@ int tn_bf_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int 
                    int act, float prm, const uint8_t* mask);
 int tn_bf_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in, int n_out, float* ws,
                    int S);
+// CONV 'bfloat16' products of a conv layer (conv_bf16.hip): operands rounded to bf16 as they are staged, fp32
+// accumulation; tn_conv2d_fwd / _wgrad / _dgrad dispatch here for EVERY geometry while tn_set_conv_matmul(ctx, 2) is in force
+int tn_cb_conv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K,
+                   int f, int stride, int pad, int Ho, int Wo, int act, float prm);
+int tn_cb_conv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int f,
+                     int stride, int pad, int Ho, int Wo, const float* prev_a, int act, float prm);
+int tn_cb_conv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K,
+                     int f, int stride, int pad, int Ho, int Wo);
 int tn_red_flush(tn_ctx* ctx);
 int tn_red_flush_inc(tn_ctx* ctx, uint32_t* inc);
 

@@ -393,6 +393,8 @@ extern "C" {
 int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N,
                   int C, int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo,
                   int act, float act_param) {
+    if (ctx->conv_bf16)     // CONV 'bfloat16': every geometry (conv_bf16.hip)
+        return tn_cb_conv_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, act, act_param);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0 && Ho > 0 && Wo > 0,
                "tn_conv2d_fwd: bad shape");
     TN_REQUIRE(!ctx->mm_f16, "tn_conv2d_fwd: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
@@ -421,6 +423,7 @@ int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, f
 
 int tn_conv2d_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C,
                     int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo) {
+    if (ctx->conv_bf16) return tn_cb_conv_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0, "tn_conv2d_wgrad: bad shape");
     TN_REQUIRE(!ctx->mm_f16, "tn_conv2d_wgrad: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
     if (tn_conv_mfma_supported(C, K, f, stride))
@@ -469,6 +472,8 @@ int tn_conv2d_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, flo
 int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H,
                     int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo, const float* prev_a,
                     int prev_act, float prev_act_param) {
+    if (ctx->conv_bf16)
+        return tn_cb_conv_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0, "tn_conv2d_dgrad: bad shape");
     TN_REQUIRE(!ctx->mm_f16, "tn_conv2d_dgrad: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
     if (tn_conv_mfma_supported(K, C, f, stride))     // reduction K*f*f, rows = C input maps

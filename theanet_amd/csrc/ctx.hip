@@ -102,6 +102,16 @@ int tn_set_fc_matmul(tn_ctx* ctx, int mode) {
     return TN_OK;
 }
 
+int tn_set_conv_matmul(tn_ctx* ctx, int mode) {
+    TN_REQUIRE(mode == 0 || mode == 2,
+               "tn_set_conv_matmul: mode %d (0 the fp32 conv kernels, 2 bf16-rounded operands 'bfloat16')", mode);
+    TN_REQUIRE(mode == 0 || !ctx->mm_f16,
+               "tn_set_conv_matmul: mode 2 (CONV 'bfloat16') while a 16-bit DTYPE is set: its conv stack already runs 16-bit "
+               "products (tn_c8_*)");
+    ctx->conv_bf16 = mode == 2;
+    return TN_OK;
+}
+
 const char* tn_last_error(tn_ctx* ctx) { return ctx ? ctx->err : g_tn_err; }
 
 int tn_sync(tn_ctx* ctx) {

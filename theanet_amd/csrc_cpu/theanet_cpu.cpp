@@ -179,6 +179,11 @@ int tn_set_fc_matmul(tn_ctx* ctx, int mode) {
             mode, mode == 1 ? "MATMUL 'bf16x3'" : mode == 2 ? "MATMUL 'bfloat16'" : "unknown");
     return TN_OK;
 }
+int tn_set_conv_matmul(tn_ctx* ctx, int mode) {
+    REQUIRE(mode == 0, "tn_set_conv_matmul: mode %d (%s): the CPU backend computes the conv products in float32 only (CONV 'float32')",
+            mode, mode == 2 ? "CONV 'bfloat16'" : "unknown");
+    return TN_OK;
+}
 // DTYPE 'float16' on fp16-resident tensors (conv_c8.hip): MI355X only; the capability queries answer 0 and
 // tn_set_matmul_dtype refuses the mode, so the host never gets here
 int tn_c8_conv_supported(int, int, int, int, int, int, int, int) { return 0; }

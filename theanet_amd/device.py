@@ -18,6 +18,8 @@ C8_DTYPES = ("float16", "bfloat16")
 _MM_MODES = {"float32": 0, "float16": 1, "bfloat16": 2}
 # MATMUL values (the dense layers' products) and their tn_set_fc_matmul modes
 _FC_MODES = {"float32": 0, "bf16x3": 1, "bfloat16": 2}
+# CONV values (the conv layers' products) and their tn_set_conv_matmul modes, numbered as MATMUL's
+_CONV_MODES = {"float32": 0, "bfloat16": 2}
 
 _context = None
 
@@ -63,6 +65,7 @@ class Context:
         rc = fn(self.h, *args)
         if rc != 0:
             self._fc_mm = None          # (a step may have stopped inside a head's fc_head bracket: set the mode afresh)
+            self._conv_mm = None        # ... and CONV's with it
             _lib.check(self.h, rc, name)
 
     # -- per-kernel timing with HIP events on the compute stream (bench.py roofline leg) --
@@ -117,6 +120,13 @@ class Context:
         if mode != getattr(self, "_fc_mm", "float32"):
             self.call("tn_set_fc_matmul", _FC_MODES[mode])
             self._fc_mm = mode
+
+    def set_conv_matmul(self, mode):
+        """'float32' (the fp32 conv kernels) or 'bfloat16' (tn_conv2d_* of every geometry on bf16-rounded operands with fp32
+        accumulation, conv_bf16.hip) -- tn_set_conv_matmul 0 / 2."""
+        if mode != getattr(self, "_conv_mm", "float32"):
+            self.call("tn_set_conv_matmul", _CONV_MODES[mode])
+            self._conv_mm = mode
 
     def fc_head(self, inside):
         """The output heads stay fp32 under MATMUL 'bfloat16': the net brackets a head's forward / backward with

@@ -128,6 +128,15 @@ class NeuralNet():
         # of DTYPE: the dense layer directly on a 16-bit conv stack keeps tn_c8_fc_*.
         self.matmul = training_params.get('MATMUL', 'float32')
         assert self.matmul in ('float32', 'bf16x3', 'bfloat16'), "MATMUL must be 'float32', 'bf16x3' or 'bfloat16'"
+        # CONV: 'float32' (default: the fp32 conv kernels, fused conv+pool blocks included) or 'bfloat16': every ConvLayer's
+        # three products on bf16-rounded operands with fp32 accumulation, for every shape a ConvLayer can be built with
+        # (conv_bf16.hip; reduced precision; tensors and weights stay fp32; conv layers are not fused with their pool or
+        # elastic layer).  Independent of MATMUL; not a mode of the 16-bit conv stack, which has its own kernels.
+        self.conv_mm = training_params.get('CONV', 'float32')
+        assert self.conv_mm in ('float32', 'bfloat16'), "CONV must be 'float32' or 'bfloat16'"
+        assert not (self.conv_mm == 'bfloat16' and self.dtype in ('float16', 'bfloat16')), (
+            "CONV 'bfloat16' with DTYPE '{}': the 16-bit conv stack already runs 16-bit products on every conv layer it "
+            "takes; CONV is for float32 nets".format(self.dtype))
         self._apply_dtype()
         self.world = comm.get_world()
         self._dev_group = None
@@ -170,7 +179,9 @@ class NeuralNet():
         while self.num_layers < len(layers):
             self.append_next_layer()
 
-        if self.fuse_conv_pool:
+        # (CONV 'bfloat16': the fused conv+pool / elastic+conv+pool blocks compute in fp32 and are not used -- every conv
+        # layer runs tn_conv2d_*, its pool tn_pool_*)
+        if self.fuse_conv_pool and self.conv_mm != 'bfloat16':
             self._fuse(self.tr_layers)
             self._fuse(self.te_layers)
 
@@ -336,6 +347,7 @@ class NeuralNet():
         (it has been collected: the recorded outputs are dangling)."""
         self.ctx.set_matmul_dtype(self.dtype, self.grad_scale)
         self.ctx.set_fc_matmul(self.matmul)
+        self.ctx.set_conv_matmul(self.conv_mm)
         me = getattr(self, "_main", self)
         ref = NeuralNet._ctx_owner
         prev = ref() if ref is not None else None

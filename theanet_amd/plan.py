@@ -196,6 +196,7 @@ class StepPlan:
         rc = self.ctx.lib.tn_net_step(self.ctx.h, handle, int(i))
         if rc:
             self.ctx._fc_mm = None      # the plan may have stopped inside a head's fc_head bracket (device.py)
+            self.ctx._conv_mm = None
             _lib.check(self.ctx.h, rc, "tn_net_step")
         self.n = j + 1
         return state
