@@ -661,7 +661,7 @@ def test_dp_overlap_schedule_equals_plain(monkeypatch):
         net = NeuralNet(copy.deepcopy(prms["layers"]), dict(prms["training_params"]))
         fn = net.get_trin_model(x, y)
         outs = [fn(s % 4) for s in range(5)]
-        assert (net._dp_split is not None) == (force == "1" and overlap == "1")
+        assert (net.dp.split is not None) == (force == "1" and overlap == "1")
         nets.append((net, outs))
         if force == "1":
             net.ctx.call("tn_comm_destroy")
@@ -688,7 +688,8 @@ def test_dp_schedule_autotune(monkeypatch):
     y = rng.randint(0, 10, 4 * 64).astype(np.int32)
     nets = []
     monkeypatch.setenv("TN_PIPELINE", "0")        # the tuner chooses among the one-step-at-a-time schedules
-    leg, pre = NeuralNet._DP_TUNE_WARM + NeuralNet._DP_TUNE_STEPS, NeuralNet._DP_TUNE_PRE
+    from theanet_amd.dpsched import DpSchedule
+    leg, pre = DpSchedule.TUNE_WARM + DpSchedule.TUNE_STEPS, DpSchedule.TUNE_PRE
     nsteps = pre + 3 * leg + 5
     for overlap in ("auto", "0"):
         monkeypatch.setenv("TN_DP_FORCE", "1")
@@ -700,14 +701,14 @@ def test_dp_schedule_autotune(monkeypatch):
         for s in range(nsteps):
             fn.enqueue(s % 4)
             if overlap == "auto" and s == pre + leg + 1:
-                assert net._dp_split is not None and not net._dp_delayed     # second leg: overlapped
+                assert net.dp.split is not None and not net.dp.delayed       # second leg: overlapped
             if overlap == "auto" and s == pre + 2 * leg + 1:
-                assert net._dp_delayed and net._dp_pending                   # third leg: delayed
+                assert net.dp.delayed and net.dp.pending                     # third leg: delayed
         outs = fn.fetch()
         if overlap == "auto":
             assert net._dp_tune is None and net.dp_schedule in ("plain", "overlap", "delayed")
-            assert (net._dp_split is not None) == (net.dp_schedule == "overlap")
-            assert net._dp_delayed == (net.dp_schedule == "delayed")
+            assert (net.dp.split is not None) == (net.dp_schedule == "overlap")
+            assert net.dp.delayed == (net.dp_schedule == "delayed")
             assert set(net.dp_tuned_ms) == {"plain", "overlap", "delayed"}
             assert all(0 < v < 5 for v in net.dp_tuned_ms.values())
         nets.append((net, outs))
@@ -739,7 +740,7 @@ def test_dp_delayed_allreduce_equals_plain(monkeypatch, name, img, ch, B):
         monkeypatch.setenv("TN_DP_OVERLAP", mode)
         net = NeuralNet(copy.deepcopy(prms["layers"]), dict(prms["training_params"]))
         fn = net.get_trin_model(x, y)
-        assert net._dp_delayed == (mode == "2")
+        assert net.dp.delayed == (mode == "2")
         outs = []
         for s in range(7):
             if s == 4:
@@ -857,7 +858,7 @@ def test_two_gpu_product_path(tmp_path, name, img, ch, B, pipe):
 def test_two_gpu_bucketed_and_rsag_equal_one_allreduce(tmp_path, knob, arms):
     """The cross-stream orderings of the default data-parallel schedule, on two real GPUs (round-4 advisor: they had only
     run where streams are no-ops): the dense bucket on the communication stream while the conv backward continues, the
-    conv bucket at the end, the update waiting on _ar_done_ev -- against ONE all-reduce per step; and every collective
+    conv bucket at the end, the update waiting on dp.ar_done_ev -- against ONE all-reduce per step; and every collective
     as reduce-scatter + all-gather against ncclAllReduce.  With two ranks a + b has one order: costs, statistics and
     weights must be BIT-identical.  Needs two visible GPUs; skipped on a one-GPU box."""
     import ctypes

@@ -20,6 +20,7 @@ from operator import mul
 import numpy as np
 
 from . import _lib, comm, layer
+from .dpsched import DpSchedule
 from .plan import StepPlan
 from .device import DeviceArray, get_context, is_c8, share
 from .layer.c8 import OperandTiles, check_follows
@@ -102,6 +103,22 @@ class NeuralNet():
                     "tn_convblock_bwd_mask", "tn_convblock_bwd", "tn_convpool_bwd", "tn_c8_conv_wgrad", "tn_c8_conv_dgrad",
                     "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad")
 
+    # step state (class-level: the twin of the pipelined schedule is given _is_twin / _main before its __init__ runs)
+    _is_twin, _main = False, None     # the second net of a _PipeTrainFn (odd steps) and the net it is the twin of
+    _pipe_fn = None           # the _PipeTrainFn that has two steps of this net in flight
+    _want_outputs = False     # the caller of this step reads [cost, features, logprob]: they are sent ahead
+    _early = None             # page-locked landing buffers of _send_outputs
+    _cost_pending = None      # pipelined: the last step's cost waits for the update that opens the stream's next step
+    _cost_guard_ev = None     # a step_cost() loop's copy of d_cost that the next launch writing d_cost must wait for
+    _mn_tab = None            # _maxnorm_table's table
+    # what bench.py and the data-parallel workers read of the schedules (dpsched.py)
+    dp_schedule = property(lambda self: self.dp.schedule)
+    dp_tuned_ms = property(lambda self: self.dp.tuned_ms)
+    _dp_bucket = property(lambda self: self.dp.bucket)
+    _dp_cand = property(lambda self: self.dp.cand)
+    _dp_can_delay = property(lambda self: self.dp.can_delay)
+    _dp_tune = property(lambda self: self.dp.tune)
+
     def __init__(self, layers, training_params, allwts=None,
                  test_x=None):
         # Either a random seed or the weights of a previously trained net (neuralnet.py:63-68)
@@ -140,6 +157,7 @@ class NeuralNet():
         self._apply_dtype()
         self.world = comm.get_world()
         self._dev_group = None
+        self.dp = DpSchedule(self)           # when the gradients are all-reduced (inert on a single GPU)
 
         self.tr_prms = training_params
         self.layers = layers
@@ -304,7 +322,7 @@ class NeuralNet():
 
         self.tr_layers.append(curr_layer)
         self.te_layers.append(curr_layer.TestVersion(te_inpt))
-        if not getattr(self, "_is_twin", False):
+        if not self._is_twin:
             curr_layer._wts_hook = self.te_layers[-1]._wts_hook = self._sync_weights
         self.num_layers += 1
 
@@ -348,12 +366,12 @@ class NeuralNet():
         self.ctx.set_matmul_dtype(self.dtype, self.grad_scale)
         self.ctx.set_fc_matmul(self.matmul)
         self.ctx.set_conv_matmul(self.conv_mm)
-        me = getattr(self, "_main", self)
+        me = self._main or self
         ref = NeuralNet._ctx_owner
         prev = ref() if ref is not None else None
         if prev is me:
             return
-        if prev is not None and getattr(prev, "_pipe_fn", None) is not None:
+        if prev is not None and prev._pipe_fn is not None:
             prev._pipe_fn._flush_parked()
         elif ref is not None:
             self.ctx.call("tn_defer_discard")
@@ -383,15 +401,14 @@ class NeuralNet():
             lyr.grads.append(self.flat_grads.view(off, p.shape))
             lyr.accumulated_updates.append(self.ctx.zeros(p.shape))
         self.tr_layers[-1].d_cost = self.d_cost
-        segs = host = self._build_seg_table()
+        host = self._build_seg_table()
         # the minibatch cost can ride in the update launch unless something must be added to it
         # first (weight costs) or it has to travel through the all-reduce (data-parallel ranks)
-        has_wtcost = any(getattr(l, 'reg', None) and l.params and (l.reg['L1'] or l.reg['L2'])
-                         for l in self.tr_layers)
+        self._has_wtcost = has_wtcost = any(getattr(l, 'reg', None) and l.params and (l.reg['L1'] or l.reg['L2'])
+                                            for l in self.tr_layers)
         # data-parallel step (TN_DP_FORCE=1: exercise it with a 1-rank communicator)
         self._dp = self.world.size > 1 or os.environ.get("TN_DP_FORCE") == "1"
         self._cost_rider = self.fused_step and (not has_wtcost) and not self._dp
-        self._cost_rider_ok = self._cost_rider
         # which layers must propagate a gradient to their input
         self._need_gin = []
         seen = False
@@ -400,7 +417,7 @@ class NeuralNet():
             seen = seen or lyr.has_updates()
         if self._dp and not self.world.dry:
             self._group()
-            if self.world.size > 1 and not getattr(self, "_is_twin", False):
+            if self.world.size > 1 and not self._is_twin:
                 # replicas must start from identical weights (same SEED or same checkpoint on every rank)
                 chk = float(sum(np.float64(w.astype(np.float64).sum()) for l in self.tr_layers for w in l.get_wts()))
                 comm.agree(chk, "the initial weights (checksum)")
@@ -413,59 +430,7 @@ class NeuralNet():
                 sig += "".join("|%s=%s" % (k, os.environ.get(k, "")) for k in ("TN_POOL_MASK", "TN_MN_FUSED"))
                 sig += "|cus=%s" % self.ctx.info()[1]
                 comm.agree(float(zlib.crc32(sig.encode())), "the kernel tunables / CU count (%s)" % sig)
-        # Optional overlap of the gradient all-reduce with the backward pass (TN_DP_OVERLAP=1): the
-        # fully-connected layers sit on top of the net and hold almost all parameters; their gradients
-        # (the tail of the flat buffer, cost included) are reduced on the second stream while the conv
-        # blocks below are still in their backward kernels.  _dp_split = first layer of that top group.
-        # Off by default: on one GPU the second flush, the stream joins and the second collective cost
-        # 18 us per step, about what a 1.5 MB all-reduce costs in the first place; the remaining
-        # small all-reduce is latency-bound either way.
-        self._dp_split, self._dp_off = None, 0
-        self._dp_cand, self._dp_tune, self.dp_schedule = None, None, "plain"
-        self._dp_delayed, self._dp_pending, self._dp_cur, self._dp_can_delay = False, False, 0, False
-        self._dp_bound = 0
-        self._dp_bucket = None
-        if self._dp:
-            j = len(self.tr_layers)
-            while j > 0 and isinstance(self.tr_layers[j - 1], HiddenLayer):
-                j -= 1
-            top = [l for l in self.tr_layers[j:] if l.params]
-            if 0 < j < len(self.tr_layers) and top and any(l.has_updates() for l in self.tr_layers[:j]):
-                self._dp_cand = (j, (top[0].grads[0].ptr - self.flat_grads.ptr) // 4)
-                # pipelined schedule: a bucket of its own for the dense group when what is left for the second
-                # collective (the conv layers' gradients) is worth one -- mnist.prms: 780 floats, one all-reduce;
-                # cifar_like: 93 k + 1.05 M, wide6: 1.15 M + 16.8 M floats, two.  TN_DP_BUCKETS=0/1 overrides.
-                want = os.environ.get("TN_DP_BUCKETS", "auto")
-                if want == "1" or (want == "auto" and self._dp_cand[1] * 4 >= (64 << 10)):
-                    self._dp_bucket = self._dp_cand
-            # "delayed" schedule: the all-reduce of step t runs under the whole of step t+1 (exact, see
-            # _train_step).  It needs a second flat gradient buffer (g_{t+1} is produced while G_t is
-            # in flight) and gradients that do not depend on the weights they are applied to (no L1/L2).
-            self._dp_can_delay = len(segs) > 0 and not has_wtcost
-            if self._dp_can_delay:
-                self._flat_ab = [self.flat_grads, self.ctx.zeros((total + _GRAD_ALIGN,))]
-                self._grads_ab, self._segs_ab = [], [self._d_segs]
-                for buf in self._flat_ab:
-                    self._grads_ab.append({id(lyr): [buf.view(off, p.shape) for l2, p, off in slots if l2 is lyr]
-                                           for lyr in self.tr_layers if lyr.params})
-                host_b = host.copy()
-                host_b['g'] = host['g'] - self.flat_grads.ptr + self._flat_ab[1].ptr
-                self._segs_ab.append(self.ctx.array(host_b.view(np.uint8)))
-            # Which schedule is fastest depends on what the all-reduce costs on this node (RCCL latency
-            # over xGMI vs. the extra launches and stream joins): with more than one rank it is
-            # MEASURED -- TN_DP_OVERLAP=auto times a few steps of each schedule on the first calls,
-            # the ranks agree on the result through an all-reduce(max) and keep the fastest one.
-            mode = os.environ.get("TN_DP_OVERLAP", "auto" if self.world.size > 1 else "0")
-            if self._dp_cand and mode == "1":
-                self._dp_split, self._dp_off = self._dp_cand
-                self.dp_schedule = "overlap"
-            elif self._dp_can_delay and mode == "2":
-                self._dp_delayed, self.dp_schedule = True, "delayed"
-            elif mode == "auto":
-                cands = ["plain"] + (["overlap"] if self._dp_cand else []) + \
-                    (["delayed"] if self._dp_can_delay else [])
-                if len(cands) > 1:
-                    self._dp_tune = {"k": 0, "ev": {}, "cands": cands, "ms": []}
+        self.dp.prepare(slots, host)
         self._grads_ready = True
 
     def _build_seg_table(self):
@@ -488,90 +453,12 @@ class NeuralNet():
             self._h_segs = host                       # kept alive: tn_sgd_update_net (TN_UPD_LAZY) reads it
         return host
 
-    _DP_TUNE_PRE, _DP_TUNE_WARM, _DP_TUNE_STEPS = 32, 8, 24      # settle-in steps, per-leg warm-up, timed
-
-    def _dp_bind(self, cur):
-        """Point every layer's gradient views, the cost slot and the update's segment table at flat
-        gradient buffer ``cur`` (the delayed schedule alternates between two)."""
-        if not self._dp_can_delay or self._dp_bound == cur:
-            return
-        self._dp_bound = cur
-        self.flat_grads = self._flat_ab[cur]
-        for lyr in self.tr_layers:
-            if lyr.params:
-                lyr.grads = self._grads_ab[cur][id(lyr)]
-        self.d_cost = self.flat_grads.view(self.n_flat - 1, (1,))
-        self.tr_layers[-1].d_cost = self.d_cost
-        self._d_segs = self._segs_ab[cur]
-
-    def _dp_set_schedule(self, name):
-        """Switch the data-parallel schedule between steps (all ranks at the same step index)."""
-        if self._dp_delayed and name != "delayed" and self._dp_pending:
-            # leaving the delayed schedule: the velocity is one gradient behind -- catch it up
-            prev = 1 - self._dp_cur
-            self.ctx.call("tn_stream_wait", 0, 1)
-            self.ctx.call("tn_sgd_update_net", _lib.TN_UPD_DELAYED, self._segs_ab[prev].ptr, None, self._n_segs, self._max_seg,
-                          self.cur_learn_rate.ptr, 1.0, None, 0, 3, None, 0, 0.0, None)
-            self._dp_pending = False
-        if name != "delayed":
-            self._dp_cur = 0
-        self._dp_delayed = name == "delayed"
-        self._dp_split, self._dp_off = self._dp_cand if name == "overlap" else (None, 0)
-        self.dp_schedule = name
-
-    def _dp_tune_tick(self):
-        """TN_DP_OVERLAP=auto: every candidate schedule (plain / overlapped all-reduce / delayed
-        all-reduce) runs W warm-up + M timed steps under a pair of HIP events; then every rank takes
-        the max over ranks of the times and keeps the fastest schedule.  All ranks switch at the same
-        step index (the schedules issue different collectives).  The steps are ordinary training
-        steps: nothing is thrown away, the weight trajectory is the same under every schedule."""
-        import ctypes
-        ctx, T = self.ctx, self._dp_tune
-        W, M = self._DP_TUNE_WARM, self._DP_TUNE_STEPS
-        k, cands = T["k"] - self._DP_TUNE_PRE, T["cands"]
-        T["k"] += 1
-        if k < 0:                                 # the first steps of a run are not representative
-            return
-        leg, pos = divmod(k, W + M)
-
-        def mark(name):
-            e = ctypes.c_void_p()
-            ctx.call("tn_event_create", ctypes.byref(e))
-            ctx.call("tn_event_record", e)
-            T["ev"][name] = e
-
-        if pos == 0:
-            if leg > 0:
-                mark("e%d" % (leg - 1))
-            if leg < len(cands):
-                self._dp_set_schedule(cands[leg])
-        if pos == W and leg < len(cands):
-            mark("s%d" % leg)
-        if leg == len(cands) and pos == 0:
-            ctx.sync()
-            ms = []
-            for q in range(len(cands)):
-                v = ctypes.c_float()
-                ctx.call("tn_event_elapsed_ms", T["ev"]["s%d" % q], T["ev"]["e%d" % q], ctypes.byref(v))
-                ms.append(v.value)
-            for e in T["ev"].values():
-                ctx.lib.tn_event_destroy(ctx.h, e)
-            t = ctx.array(np.asarray(ms, np.float32))
-            self._group().allreduce_max(t)
-            ms = [float(v) / M for v in t.get_value()]
-            self.dp_tuned_ms = dict(zip(cands, ms))
-            self._dp_tune = None
-            self._dp_set_schedule(cands[int(np.argmin(ms))])
-            if self.world.rank == 0:
-                sys.stderr.write("theanet_amd: data-parallel schedule '%s' (%s)\n" % (
-                    self.dp_schedule, ", ".join("%s %.1f us/step" % (c, 1e3 * m) for c, m in zip(cands, ms))))
-
     def _send_outputs(self, out, with_cost=False):
         """The step's features / logprob start travelling to page-locked host memory now (ordered behind the
         output layer's forward, on the context's copy stream): the copies run under the backward pass instead
         of after the step (the drop-in call fn(i) reads them every step, neuralnet.py:236-241)."""
         from .device import HostBuffer
-        early = getattr(self, "_early", None)
+        early = self._early
         if early is None:
             early = self._early = {"live": False, "logprob": HostBuffer(self.ctx, out.logprob.shape),
                                    "cost": HostBuffer(self.ctx, (1,))}
@@ -592,10 +479,7 @@ class NeuralNet():
         self._apply_dtype()
         out = self.tr_layers[-1]
         first = self.tr_layers[0]
-        if self._dp_tune is not None and not pipe_stride:
-            self._dp_tune_tick()
-        if self._dp_can_delay:
-            self._dp_bind(self._dp_cur if self._dp_delayed else 0)
+        self.dp.begin_step(pipe_stride)
         self._c8_tiles.arrange(self.tr_layers, self._need_gin)
         for lyr in self.tr_layers[:-1]:
             lyr.forward(True)
@@ -613,43 +497,29 @@ class NeuralNet():
             raise
         finally:
             ctx.fc_head(False)
-        want = getattr(self, "_want_outputs", False)
-        cost_sent = False
-        if want:
-            if self._cost_rider_ok and not self._dp:
-                # the caller reads [cost, features, logprob] of this step: the cost is summed now (the cost block
-                # of the update launch on its own: same summation order, same bits) and leaves with the outputs
-                self._guard_cost()
-                ctx.call("tn_sgd_update_net", _lib.TN_UPD_PLAIN, None, None, 0, 0, self.cur_learn_rate.ptr, 1.0, None, 0, 0,
-                         out.rowloss.ptr, self.local_bsz, 1.0 / self.batch_sz, self.d_cost.ptr)
-                cost_sent = True
-            self._send_outputs(out, cost_sent)
-        # cost = -mean logprob[n, y_n] (this rank's share of the global mean).  Without weight
-        # costs it rides in the update launch at the end of the step (tn_sgd_update_net);
-        # with them it must exist before tn_wtcost accumulates onto it: a leaf reduction here.
-        rider = self._cost_rider and not pipe_stride
-        lazy_pipe = bool(pipe_stride) and getattr(self, "_pipe_lazy", False) and self._cost_rider_ok
-        if cost_sent:
-            self._cost_pending = False
-        if lazy_pipe and not cost_sent:
-            self._cost_pending = True             # summed by the launch that opens this stream's next step
-        elif not rider and not cost_sent:
+        # Where the step's cost (-mean logprob[n, y_n], this rank's share of the global mean) is summed -- one of:
+        leaf = not self._cost_rider     # here: weight costs are added onto it, or it travels through the all-reduce
+        rides = self._cost_rider and not pipe_stride    # in the update launch at the end of the step
+        # two steps in flight: it, and the finishing slab sums, wait for the update launch that opens this stream's next step
+        parks = self._cost_rider and bool(pipe_stride)
+        # ... and when the caller reads it, ALSO now: the update's cost block on its own (same order, same bits)
+        sent = self._cost_rider and self._want_outputs
+        if sent:
+            self._sum_cost()
+        if self._want_outputs:
+            self._send_outputs(out, sent)
+        if sent or parks:
+            self._cost_pending = not sent
+        if leaf:
             self._guard_cost()
-            if pipe_stride and self._cost_rider_ok:
-                # the cost block of the update launch on its own: the same summation order as the
-                # one-step-at-a-time schedule, so the reported cost is bit-identical too
-                ctx.call("tn_sgd_update_net", _lib.TN_UPD_PLAIN, None, None, 0, 0, self.cur_learn_rate.ptr, 1.0, None, 0, 0,
-                         out.rowloss.ptr, self.local_bsz, 1.0 / self.batch_sz, self.d_cost.ptr)
-            else:
-                ctx.call("tn_reduce_sum", out.rowloss.ptr, self.local_bsz, 1.0 / self.batch_sz,
-                         self.d_cost.ptr, 0)
+            ctx.call("tn_reduce_sum", out.rowloss.ptr, self.local_bsz, 1.0 / self.batch_sz, self.d_cost.ptr, 0)
         g = out.dlogits
         # The elastic field of the NEXT minibatch only depends on the step counter.  It is left with
-        # the context as a rider (offset +1: the counter advances at the end of the step) and
+        # the context as a rides (offset +1: the counter advances at the end of the step) and
         # travels as extra blocks of the backward pass's paired GEMM launch; nets without such a
         # launch build it beside the update instead (tn_step_tail).
         ahead = (isinstance(first, ElasticLayer) and first.active and first.has_field and
-                 not first._inj_draws and first.d_step is not None and (self._n_segs or rider) and
+                 not first._inj_draws and first.d_step is not None and (self._n_segs or rides) and
                  self.fused_step)
         if ahead:
             nxt = 1 - first._cur
@@ -661,8 +531,6 @@ class NeuralNet():
             ctx.call("tn_rider_elastic_field", first.draws.ptr, first.seed, pipe_stride or 1,
                      self.d_step.ptr, *field_args)
         tail = False
-        dp_async = False
-        bucket_sent = False
         # single-GPU steps leave the finishing slab sums to the update launch (tn_sgd_update_net, TN_UPD_LAZY)
         lazy = False
         try:
@@ -677,27 +545,8 @@ class NeuralNet():
                         ctx.fc_head(False)
                 else:
                     g = lyr.backward(g, self._need_gin[idx], below)
-                if idx == self._dp_split and g is not None:
-                    # the top (fully-connected) group is done: finish its slab sums and send its
-                    # gradients through the all-reduce on the second stream, under the conv backward
-                    ctx.call("tn_defer_reductions", 0)
-                    ctx.call("tn_defer_reductions", 1)
-                    ctx.call("tn_stream_wait", 1, 0)
-                    ctx.call("tn_stream_select", 1)
-                    self._group().allreduce_sum(self.flat_grads.view(self._dp_off, (self.n_flat - self._dp_off,)))
-                    ctx.call("tn_stream_select", 0)
-                    dp_async = True
-                elif pipe_stride and self._dp and self._dp_bucket is not None and idx == self._dp_bucket[0] \
-                        and g is not None:
-                    # two steps in flight, bucketed (SURVEY 8e "bucket by layer"): the dense group on top of the net
-                    # holds almost all parameters and its gradients exist NOW -- their slab sums are finished and the
-                    # bucket [dense gradients | cost] leaves on the communication stream while this stream carries on
-                    # with the conv blocks' backward kernels; the conv bucket follows at the end of the step
-                    ctx.call("tn_defer_reductions", 0)
-                    ctx.call("tn_defer_reductions", 1)
-                    off = self._dp_bucket[1]
-                    self._group().allreduce_sum_async(self.flat_grads.view(off, (self.n_flat - off,)), None, None)
-                    bucket_sent = True
+                if self._dp and g is not None:
+                    self.dp.after_backward(idx, pipe_stride)
                 if g is None:
                     break
             lazy = self.fused_step and not self._dp and 0 < self._n_segs <= 32
@@ -712,76 +561,34 @@ class NeuralNet():
             lazy = lazy and not tail
             if tail:
                 ctx.call("tn_defer_flush_step", self.d_step.ptr)      # the counter advances here
-            elif not lazy and not lazy_pipe:
+            elif not lazy and not parks:
                 ctx.call("tn_defer_reductions", 0)
         if pipe_stride:
-            # two steps in flight (_PipeTrainFn): this stream's next step starts with the update.
-            # Data-parallel: the all-reduce simply follows on this stream -- its latency is covered by
-            # the other stream's step, and the update that needs it is a whole step away.
-            if self._dp:
-                # every collective of the pipelined schedule goes through the context's ONE communication stream
-                # (tn_allreduce_sum_async): one order of collectives on the communicator whatever stream the step
-                # ran on, and neither compute stream ever waits inside a collective.  The consumer -- the update
-                # that opens this stream's next step -- waits for _ar_done_ev (_PipeTrainFn._update_for).
-                n = self._dp_bucket[1] if bucket_sent else self.n_flat
-                self._group().allreduce_sum_async(self.flat_grads, n, getattr(self, "_ar_done_ev", None))
+            self.dp.end_pipelined()               # two steps in flight: this stream's next step starts with the update
             if ahead:
                 first._cur, first._pre_valid = nxt, True
             self._c8_tiles.stale()
             return
-        delayed = self._dp_delayed
-        if delayed and tail:
-            self._dp_set_schedule("plain")        # (configuration-determined: the same on every rank)
-            delayed = False
-        if delayed:
-            # Delayed schedule.  layer.py:82-86 applies the OLD velocity, so p_{t+1} = p_t - s*v_t needs
-            # the gradient of step t-1, not of this step: update with the REDUCED gradient of the
-            # previous step (its all-reduce had this whole step to finish), then start this step's
-            # all-reduce on the second stream, where it runs under the next step.  Bit-identical weights.
-            cur = self._dp_cur
-            if self._dp_pending:
-                ctx.call("tn_stream_wait", 0, 1)
-                ctx.call("tn_sgd_update_net", _lib.TN_UPD_DELAYED, self._segs_ab[1 - cur].ptr, None, self._n_segs,
-                         self._max_seg, self.cur_learn_rate.ptr, 1.0, self.d_step.ptr, 1, 1, None, 0, 0.0, None)
-            else:
-                ctx.call("tn_sgd_update_net", _lib.TN_UPD_DELAYED, self._segs_ab[cur].ptr, None, self._n_segs,
-                         self._max_seg, self.cur_learn_rate.ptr, 1.0, self.d_step.ptr, 1, 2, None, 0, 0.0, None)
-            ctx.call("tn_stream_wait", 1, 0)
-            ctx.call("tn_stream_select", 1)
-            self._group().allreduce_sum(self._flat_ab[cur], self.n_flat)
-            ctx.call("tn_stream_select", 0)
-            self._dp_pending, self._dp_cur = True, 1 - cur
-        elif self._dp:
-            if dp_async:
-                if self._dp_off:
-                    self._group().allreduce_sum(self.flat_grads, self._dp_off)     # the conv head
-                ctx.call("tn_stream_wait", 0, 1)                                  # join the tail
-            else:
-                self._group().allreduce_sum(self.flat_grads, self.n_flat)
+        delayed = self.dp.end_sequential(tail)    # the all-reduce (the delayed schedule: with its update)
         for lyr in self.tr_layers:
             lyr.get_wtcost(self.d_cost)
-        if rider:
+        if rides:
             self._guard_cost()
+        cost_args = (out.rowloss.ptr if rides else None, self.local_bsz, 1.0 / self.batch_sz, self.d_cost.ptr if rides else None)
         mn_done = False
         if delayed:
             pass
         elif tail:
             ctx.call("tn_step_tail", self._d_segs.ptr if self._n_segs else None, self._n_segs,
-                     self._max_seg, self.cur_learn_rate.ptr, 1.0,
-                     out.rowloss.ptr if rider else None, self.local_bsz, 1.0 / self.batch_sz,
-                     self.d_cost.ptr if rider else None, first.draws.ptr, first.seed, self.d_step.ptr,
+                     self._max_seg, self.cur_learn_rate.ptr, 1.0, *cost_args, first.draws.ptr, first.seed, self.d_step.ptr,
                      *field_args)
         elif lazy:
             self._update_and_maxnorm(_lib.TN_UPD_LAZY, self._d_segs.ptr, self._h_segs.ctypes.data, self._n_segs,
-                                     self._max_seg, self.cur_learn_rate.ptr, 1.0, self.d_step.ptr, 1, 0,
-                                     out.rowloss.ptr if rider else None, self.local_bsz, 1.0 / self.batch_sz,
-                                     self.d_cost.ptr if rider else None)
+                                     self._max_seg, self.cur_learn_rate.ptr, 1.0, self.d_step.ptr, 1, 0, *cost_args)
             mn_done = True
-        elif self._n_segs or rider:               # also advances the RNG step counter
+        elif self._n_segs or rides:               # also advances the RNG step counter
             ctx.call("tn_sgd_update_net", _lib.TN_UPD_PLAIN, self._d_segs.ptr if self._n_segs else None, None,
-                     self._n_segs, self._max_seg, self.cur_learn_rate.ptr, 1.0, self.d_step.ptr, 1, 0,
-                     out.rowloss.ptr if rider else None, self.local_bsz, 1.0 / self.batch_sz,
-                     self.d_cost.ptr if rider else None)
+                     self._n_segs, self._max_seg, self.cur_learn_rate.ptr, 1.0, self.d_step.ptr, 1, 0, *cost_args)
         else:
             ctx.call("tn_add_u32", self.d_step.ptr, 1)
         if ahead:
@@ -803,10 +610,15 @@ class NeuralNet():
     def _guard_cost(self):
         """In front of a launch that writes ``d_cost``: a step_cost() loop may still owe the host the previous value (a
         4-byte copy on the copy stream, _CostLedger.issue) -- the stream waits for that copy's event."""
-        ev = getattr(self, "_cost_guard_ev", None)
-        if ev is not None:
-            self.ctx.call("tn_event_wait", ev)
+        if self._cost_guard_ev is not None:
+            self.ctx.call("tn_event_wait", self._cost_guard_ev)
             self._cost_guard_ev = None
+
+    def _sum_cost(self):
+        """The last step's cost into ``d_cost``, on the stream currently selected: the update launch's cost block on its own."""
+        self._guard_cost()
+        self.ctx.call("tn_sgd_update_net", _lib.TN_UPD_PLAIN, None, None, 0, 0, self.cur_learn_rate.ptr, 1.0, None, 0, 0,
+                      self.tr_layers[-1].rowloss.ptr, self.local_bsz, 1.0 / self.batch_sz, self.d_cost.ptr)
 
     def _injecting(self):
         """A parity test has injected random draws somewhere (dropout masks, elastic / color draws)."""
@@ -826,7 +638,7 @@ class NeuralNet():
             self.ctx.call("tn_maxnorm_multi", chunk.ctypes.data, len(chunk))
 
     def _maxnorm_table(self):
-        tab = getattr(self, "_mn_tab", None)
+        tab = self._mn_tab
         if tab is None:
             rows = []
             for lyr in self.tr_layers:
@@ -874,7 +686,7 @@ class NeuralNet():
         else:
             aux_data = None
         self._prepare_training()
-        if getattr(self, "_pipe_fn", None) is not None:
+        if self._pipe_fn is not None:
             self._pipe_fn._fall_back()           # an earlier training function: bring the net up to date
         if aux_data is None and self._pipe_ok(take_index_list):
             return _PipeTrainFn(self, share(x_data), share(y_data, np.int32))
@@ -882,32 +694,23 @@ class NeuralNet():
 
     def _sync_weights(self):
         """With two steps in flight (_PipeTrainFn) the net's own weight buffers lag behind: catch up."""
-        fn = getattr(self, "_pipe_fn", None)
-        if fn is not None:
-            fn.sync_weights()
+        if self._pipe_fn is not None:
+            self._pipe_fn.sync_weights()
 
     def _pipe_ok(self, take_index_list):
         """Two-steps-in-flight schedule (_PipeTrainFn): single GPU, plain momentum-SGD nets."""
-        if getattr(self, "_is_twin", False) or not self.fused_step or os.environ.get("TN_PIPELINE", "1") == "0":
+        if self._is_twin or not self.fused_step or os.environ.get("TN_PIPELINE", "1") == "0":
             return False
-        has_wtcost = any(getattr(l, 'reg', None) and l.params and (l.reg['L1'] or l.reg['L2'])
-                         for l in self.tr_layers)
-        inject = any((getattr(l, "drop", None) is not None and l.drop.injected) or getattr(l, "_inj_draws", False)
-                     or getattr(l, "_inj", None) is not None
-                     or getattr(l, "_inj_flip", None) is not None for l in self.tr_layers)
         if self._dp and os.environ.get("TN_DP_PIPELINE", "1") == "0":
             return False
-        return not take_index_list and self._n_segs > 0 and not has_wtcost and not inject
+        return not take_index_list and self._n_segs > 0 and not self._has_wtcost and not self._injecting()
 
     def reset_accumulated_gradients(self):
         self._prepare_training()
-        if getattr(self, "_pipe_fn", None) is not None:
+        if self._pipe_fn is not None:
             self._pipe_fn._fall_back()           # steps in flight: apply their gradients first
-        if self._dp_delayed and self._dp_pending:
-            # delayed all-reduce schedule: the reduced gradient of the last step is still to be folded
-            # into the velocity -- the reference zeroes that contribution too: drop it
-            self.ctx.call("tn_stream_wait", 0, 1)
-            self._dp_pending = False
+        # (a reduced gradient the delayed schedule has still to fold into the velocity: the reference zeroes it too)
+        self.dp.drop_pending()
         for lyr in self.tr_layers:
             for au in (lyr.accumulated_updates or ()):
                 au.fill_bytes(0)
@@ -985,7 +788,7 @@ class NeuralNet():
 
     def _opt_state(self):
         self._prepare_training()
-        fn = getattr(self, "_pipe_fn", None)
+        fn = self._pipe_fn
         pend, step = None, int(self.d_step.get_value()[0])
         if fn is not None and fn._seq is None and fn._twin is not None and fn.t > 0:
             # two steps in flight: the velocity on the device is one gradient behind (that of step t-1, still with the
@@ -995,12 +798,10 @@ class NeuralNet():
             self.ctx.sync()
             X = fn.nets[(fn.t - 1) & 1]
             pend, step = (lambda i, j: X.tr_layers[i].grads[j].get_value()), fn._base + fn.t
-        elif self._dp_delayed and self._dp_pending:
-            # delayed all-reduce (TN_DP_OVERLAP=2): the same situation -- the reduced gradient of the last step is still
-            # travelling (second stream) and the update that folds it in belongs to the next step.  Read-only here: the
-            # schedule is left alone (a checkpoint is written by one rank; a schedule change must happen on all)
+        elif self.dp.pending_grads() is not None:
+            # delayed all-reduce (TN_DP_OVERLAP=2): the same situation, the last reduced gradient travels on the second stream
             self.ctx.sync()
-            prev = self._grads_ab[1 - self._dp_cur]
+            prev = self.dp.pending_grads()
             pend = lambda i, j: prev[id(self.tr_layers[i])][j].get_value()
         vel = []
         for i, lyr in enumerate(self.tr_layers):
@@ -1018,7 +819,7 @@ class NeuralNet():
     def load_opt_state(self, state):
         """Velocities and RNG step counter saved by get_init_params(with_opt_state=True); call before training."""
         self._prepare_training()
-        if getattr(self, "_pipe_fn", None) is not None:
+        if self._pipe_fn is not None:
             self._pipe_fn._fall_back()
         for lyr, row in zip(self.tr_layers, state["velocities"]):
             for v, a in zip(lyr.accumulated_updates or (), row):

@@ -26,7 +26,7 @@ def _step_outputs(net, out):
     holds the launch summing the cost).  When the step sent features / logprob ahead (``NeuralNet._send_outputs``:
     copies into page-locked memory that ran under the backward pass) the cost follows them through the copy
     stream and one wait covers all three; otherwise three blocking copies."""
-    early = getattr(net, "_early", None)
+    early = net._early
     if early is not None and early["live"]:
         early["live"] = False
         if not early["cost_sent"]:
@@ -145,6 +145,30 @@ def _batch_in_range(i, n_rows, batch_sz):
         raise IndexError("minibatch %d of %d rows each in a dataset of %d rows" % (i, batch_sz, n_rows))
 
 
+def _enqueue_planned(fn, i, keep=lambda: True):
+    """``fn._enqueue(i)`` inside the step plan's bracket (plan.py): a recorded phase is replayed as one C call; otherwise the
+    step is interpreted, and recorded when it is an ordinary one (plannable before it, no exception, ``keep()`` after it)."""
+    pl = fn._plan
+    if pl is None or pl.off:
+        return fn._enqueue(i)
+    ok = fn._plannable()
+    if ok and pl.ready:                      # (the learning rate is a device scalar here: no argument changes with it)
+        fn.net._apply_dtype()
+        st = pl.step(i, fn._plan_state())
+        if st is not None:
+            return fn._plan_set_state(st)
+    if ok:
+        pl.begin(i, fn._plan_state())
+    try:
+        fn._enqueue(i)
+    except Exception:
+        ok = False
+        raise
+    finally:
+        ok = ok and keep()
+        pl.end(fn._plan_state() if ok else None, ok)
+
+
 class _TrainFn:
     """What ``get_trin_model`` returns: ``fn(i) -> [cost, features, logprob]``
     (neuralnet.py:236-241).  ``enqueue(i)`` issues the step without reading anything
@@ -171,8 +195,8 @@ class _TrainFn:
     def _plan_state(self):
         net = self.net
         first = net.tr_layers[0]
-        return (getattr(first, "_cur", None), getattr(first, "_pre_valid", None), getattr(net, "_cost_pending", None),
-                net._dp_cur, net._dp_pending, (self._n & 3) if self._led.live else -1)
+        return (getattr(first, "_cur", None), getattr(first, "_pre_valid", None), net._cost_pending,
+                net.dp.cur, net.dp.pending, (self._n & 3) if self._led.live else -1)
 
     def _plan_set_state(self, st):
         net = self.net
@@ -181,15 +205,14 @@ class _TrainFn:
             first._cur, first._pre_valid = st[0], st[1]
         if st[2] is not None:
             net._cost_pending = st[2]
-        net._dp_cur, net._dp_pending = st[3], st[4]
+        net.dp.cur, net.dp.pending = st[3], st[4]
         if self._led.live:                        # (the replayed step has sent its cost like an interpreted one)
             self._led.issue(self._n, self._n, None, net)
         self._n += 1
 
     def _plannable(self):
         net = self.net
-        return not getattr(net, "_want_outputs", False) and net._dp_tune is None and net.ctx.ev_hook is None and \
-            not net._injecting()
+        return not net._want_outputs and net.dp.tune is None and net.ctx.ev_hook is None and not net._injecting()
 
     def enqueue(self, i):
         if self.take_index_list:
@@ -199,26 +222,7 @@ class _TrainFn:
                                  % (self.net.batch_sz, self.x_data.shape[0]))
         else:
             _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
-        pl = self._plan
-        if pl is not None and not pl.off:
-            ok = self._plannable()
-            if pl.ready:
-                if ok:                       # (the learning rate is a device scalar here: no argument changes with it)
-                    self.net._apply_dtype()
-                    st = pl.step(i, self._plan_state())
-                    if st is not None:
-                        return self._plan_set_state(st)
-            if ok:
-                pl.begin(i, self._plan_state())
-            try:
-                self._enqueue(i)
-            except Exception:
-                ok = False
-                raise
-            finally:
-                pl.end(self._plan_state() if ok else None, ok)
-            return
-        self._enqueue(i)
+        _enqueue_planned(self, i)
 
     def _enqueue(self, i):
         net, ctx = self.net, self.net.ctx
@@ -259,7 +263,7 @@ class _TrainFn:
         """Enqueue step i; return [(step number, cost), ...] of the steps whose cost has become due (step numbers count
         the step_cost calls since the last drain_costs()).  Do not mix with enqueue() / fn(i) before drain_costs()."""
         net, led = self.net, self._led
-        if net._dp_delayed or net._dp_tune is not None or self.take_index_list or net._injecting():
+        if net.dp.delayed or net.dp.tune is not None or self.take_index_list or net._injecting():
             out = self._ring_rest()               # (the cost travels on the second stream / per-step host work)
             out.append((led.k, np.float32(self(i)[0])))
             led.k += 1
@@ -290,7 +294,7 @@ class _TrainFn:
     def fetch(self):
         net = self.net
         out = net.tr_layers[-1]
-        if getattr(net, "_dp_pending", False):
+        if net.dp.pending:
             net.ctx.sync()                        # the cost travels with the all-reduce on the second stream
         return _step_outputs(net, out)
 
@@ -324,6 +328,7 @@ class _PipeTrainFn:
         self.take_index_list = False
         self.t = 0                   # steps enqueued so far
         self._updated = False        # the update for step self.t has already been applied (weights were read)
+        self._want = False           # the caller of this step reads its outputs (__call__)
         self._seq = None             # sequential fallback (_TrainFn) once something rules pipelining out
         self._twin = None
         self._last = net
@@ -343,13 +348,7 @@ class _PipeTrainFn:
         tp = dict(net.tr_prms)
         tp.setdefault('SEED', 0)      # (a net loaded from a checkpoint has none; weights and stream seeds are copied below)
         twin.__init__(copy.deepcopy(net.layers), tp)
-        if net._dp:
-            twin._dev_group = net._group()                 # ONE communicator; the streams alternate on it
-        twin._prepare_training()
-        if net._dp:
-            net._dp_set_schedule("plain")
-            net._dp_tune = twin._dp_tune = None              # nothing to tune: the all-reduce rides in-stream
-            net.dp_schedule = twin.dp_schedule = "pipelined"
+        net.dp.go_pipelined(twin)
         for a, b in zip(net.tr_layers, twin.tr_layers):
             if hasattr(a, "seed"):
                 b.seed = a.seed
@@ -364,8 +363,7 @@ class _PipeTrainFn:
         # the twin's own velocity buffers are gone with that: its update table must name the shared ones
         # (it is what _fall_back folds the last gradient through when the twin ran the last step)
         twin._build_seg_table()
-        if getattr(twin, "_dp_can_delay", False):
-            twin._segs_ab[0] = twin._d_segs
+        twin.dp.segs_rebuilt()
         self._twin = twin
         self.nets = (net, twin)
         seg_dt = np.dtype([('p', 'u8'), ('psrc', 'u8'), ('v', 'u8'), ('g', 'u8'), ('n', 'u8'),
@@ -381,11 +379,7 @@ class _PipeTrainFn:
             self._hsegs.append(host)             # kept alive: the update matches pending slab sums against it
             self._segs.append(ctx.array(host.view(np.uint8)))
             X._cost_pending = False
-            # single-GPU runs leave a step's slab sums and cost to the update that opens the stream's next
-            # step (one launch instead of three); data-parallel steps need both before their all-reduce
-            X._pipe_lazy = not net._dp
             self._lr.append(ctx.zeros((1,)))
-            X._cost_rider = False
         self._nseg, self._max_seg = net._n_segs, net._max_seg
         self._ev, arev = [], []
         for _ in range(2):
@@ -394,7 +388,7 @@ class _PipeTrainFn:
                 ctx.call("tn_event_create", self._ctypes.byref(e))
                 lst.append(e)
         for k, X in enumerate(self.nets):                  # recorded behind step's last collective (communication stream)
-            X._ar_done_ev = arev[k]
+            X.dp.ar_done_ev = arev[k]
         base = int(net.d_step.get_value()[0])            # steps already taken (an earlier training function)
         self._base = base
         ctx.call("tn_set_u32", twin.d_step.ptr, base + 1)    # the twin takes every second step
@@ -430,7 +424,7 @@ class _PipeTrainFn:
 
     def _plannable(self):
         lr = self._lr_now()
-        return self._seq is None and self._twin is not None and not self._updated and not getattr(self, "_want", False) \
+        return self._seq is None and self._twin is not None and not self._updated and not self._want \
             and self.t >= 4 and lr == self._lr_prev and self._lr_set[0] == lr and self._lr_set[1] == lr \
             and not self._blocked()
 
@@ -443,7 +437,7 @@ class _PipeTrainFn:
         ctx.call("tn_stream_select", k)
         ctx.call("tn_event_wait", self._ev[1 - k])
         if X._dp and t >= 2:
-            ctx.call("tn_event_wait", X._ar_done_ev)      # this stream's gradient of step t-2, back from the all-reduce
+            ctx.call("tn_event_wait", X.dp.ar_done_ev)    # this stream's gradient of step t-2, back from the all-reduce
         if self._lr_set[k] != self._lr_prev:              # the rate step t-1 was enqueued under
             ctx.call("tn_set_f32", self._lr[k].ptr, self._lr_prev)
             self._lr_set[k] = self._lr_prev
@@ -498,13 +492,9 @@ class _PipeTrainFn:
             # the velocity is one gradient behind (that of step t-1, held by the stream that ran it)
             Y = self.nets[(self.t - 1) & 1]
             ctx.call("tn_stream_select", 0)
-            ctx.call("tn_sgd_update_net", _lib.TN_UPD_DELAYED, Y._d_segs.ptr, None, Y._n_segs, Y._max_seg,
-                     net.cur_learn_rate.ptr, 1.0, None, 0, 3, None, 0, 0.0, None)
+            net.dp.catch_up(Y._d_segs)
             ctx.call("tn_set_u32", net.d_step.ptr, self._base + self.t)
             ctx.sync()
-        has_wtcost = any(getattr(l, 'reg', None) and l.params and (l.reg['L1'] or l.reg['L2'])
-                         for l in net.tr_layers)
-        net._cost_rider = net.fused_step and (not has_wtcost) and not net._dp
         net._pipe_fn = None
         first = net.tr_layers[0]
         if isinstance(first, ElasticLayer):
@@ -514,31 +504,13 @@ class _PipeTrainFn:
     # -- the step ---------------------------------------------------------------------------------
     def enqueue(self, i):
         _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
-        pl = self._plan
-        if pl is None or pl.off:
-            return self._enqueue(i)
-        ok = self._plannable()
-        if pl.ready and ok:
-            self.net._apply_dtype()
-            st = pl.step(i, self._plan_state())
-            if st is not None:
-                self._plan_set_state(st)
-                return
-        if ok:
-            pl.begin(i, self._plan_state())
-        try:
-            self._enqueue(i)
-        except Exception:
-            ok = False
-            raise
-        finally:
-            pl.end(self._plan_state() if ok and self._seq is None else None, ok and self._seq is None)
+        _enqueue_planned(self, i, keep=lambda: self._seq is None)     # (a step that fell back is not one to record)
 
     def _enqueue(self, i):
         if self._seq is None and self._blocked():
             self._fall_back()
         if self._seq is not None:
-            self.net._want_outputs = getattr(self, "_want", False)
+            self.net._want_outputs = self._want
             try:
                 return self._seq.enqueue(i)
             finally:
@@ -566,7 +538,7 @@ class _PipeTrainFn:
         slot.bind(self.x_data)
         slot.row0 = int(i) * net.batch_sz + net.shard_lo
         slot.row_global0 = net.shard_lo
-        X._want_outputs = getattr(self, "_want", False)
+        X._want_outputs = self._want
         try:
             X._train_step(self.y_data, slot.row0, pipe_stride=2)
         finally:
@@ -620,9 +592,9 @@ class _PipeTrainFn:
         X = self._last
         X.ctx.call("tn_stream_select", self.nets.index(X))
         if X._dp:
-            X.ctx.call("tn_event_wait", X._ar_done_ev)    # the cost travels with the all-reduce (communication stream)
+            X.ctx.call("tn_event_wait", X.dp.ar_done_ev)  # the cost travels with the all-reduce (communication stream)
         try:
-            early = getattr(X, "_early", None)
+            early = X._early
             sent = early is not None and early["live"]
             if not (sent and early["cost_sent"]):
                 self._finish_cost(X)
@@ -635,11 +607,8 @@ class _PipeTrainFn:
     @staticmethod
     def _finish_cost(X):
         """The cost of X's last step, if nothing has summed it yet (on the stream currently selected)."""
-        if getattr(X, "_cost_pending", False):
-            out = X.tr_layers[-1]
-            X._guard_cost()
-            X.ctx.call("tn_sgd_update_net", _lib.TN_UPD_PLAIN, None, None, 0, 0, X.cur_learn_rate.ptr, 1.0, None, 0, 0,
-                       out.rowloss.ptr, X.local_bsz, 1.0 / X.batch_sz, X.d_cost.ptr)
+        if X._cost_pending:
+            X._sum_cost()
             X._cost_pending = False
 
     def __call__(self, i):

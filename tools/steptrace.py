@@ -15,6 +15,12 @@ interpreter's heap, and whether two of them share an address says nothing about 
 (tn_net_plan_add) are decoded the same way.  The last line is a SHA-256 of every weight tensor after the steps (not part
 of the recording).
 
+``--drive`` chooses how the steps are issued: ``enqueue`` (nothing read back), ``call`` (the drop-in ``fn(i)``: outputs sent
+ahead, the cost summed for them) or ``step_cost`` (``fn.step_cost(i)``, with ``drain_costs()`` after every tenth step and at
+the end: the cost ring).  The costs that come back are part of the trace, as ``cost <step number> f:<bits>`` lines where
+they were returned.  The data-parallel and pipelining switches (TN_DP_FORCE, TN_DP_OVERLAP, TN_PIPELINE, TN_DP_BUCKETS)
+need no option: the net reads them from the environment, so set them for the run to be traced.
+
 ``trace(layers, training_params, ...)`` does the same for a net given as Python objects."""
 import argparse
 import ast
@@ -32,6 +38,8 @@ if ROOT not in sys.path:
 
 STEPS = 6 + 12 + 6          # StepPlan.WARM, the steps it records, replayed steps
 NBATCH = 5                  # minibatches in the dataset: odd, so that every phase of a plan sees more than one
+DRIVES = ("enqueue", "call", "step_cost")
+DRAIN_EVERY = 10            # --drive step_cost: drain_costs() after this many steps (train.py does at the end of an epoch)
 
 
 class _Recorder:
@@ -102,9 +110,14 @@ class _Recorder:
         return logged
 
 
-def trace(layers, training_params, channels, img, out=None, steps=STEPS):
-    """Builds the net, runs ``steps`` training steps and one test call with recording on; returns the trace's lines, the
-    weight hash last (and writes them to ``out``)."""
+def _cost_line(k, cost):
+    return "cost %d f:%08x" % (k, int(np.float32(cost).view(np.uint32)))
+
+
+def trace(layers, training_params, channels, img, out=None, steps=STEPS, drive="enqueue"):
+    """Builds the net, runs ``steps`` training steps (issued as ``drive`` says) and one test call with recording on; returns
+    the trace's lines, the weight hash last (and writes them to ``out``)."""
+    assert drive in DRIVES, drive
     from theanet_amd import NeuralNet, _lib
     from theanet_amd.device import get_context
     ctx = get_context()
@@ -120,7 +133,14 @@ def trace(layers, training_params, channels, img, out=None, steps=STEPS):
         net = NeuralNet(layers, dict(training_params))
         fn = net.get_trin_model(x, y)
         for s in range(steps):
-            fn.enqueue(s % NBATCH)
+            if drive == "enqueue":
+                fn.enqueue(s % NBATCH)
+            elif drive == "call":
+                lines.append(_cost_line(s, fn(s % NBATCH)[0]))
+            else:
+                lines.extend(_cost_line(k, c) for k, c in fn.step_cost(s % NBATCH))
+                if (s + 1) % DRAIN_EVERY == 0 or s + 1 == steps:
+                    lines.extend(_cost_line(k, c) for k, c in fn.drain_costs())
         ctx.sync()
         net.get_test_model(x, y)(0)
     finally:
@@ -145,6 +165,7 @@ def main():
     ap.add_argument("--dtype", default="float32", choices=("float32", "float16", "bfloat16"))
     ap.add_argument("--matmul", default=None, help="MATMUL training param (default: the file's)")
     ap.add_argument("--steps", type=int, default=STEPS)
+    ap.add_argument("--drive", default="enqueue", choices=DRIVES, help="how the steps are issued")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     with open(os.path.join(ROOT, "params", args.prms)) as fh:
@@ -155,8 +176,8 @@ def main():
     tp = dict(prms["training_params"], SEED=555555, BATCH_SZ=args.batch, DTYPE=args.dtype)
     if args.matmul:
         tp["MATMUL"] = args.matmul
-    lines = trace(prms["layers"], tp, channels, first["img_sz"], args.out, args.steps)
-    print("%s %s: %d calls, %s" % (args.prms, args.dtype, len(lines) - 1, lines[-1]))
+    lines = trace(prms["layers"], tp, channels, first["img_sz"], args.out, args.steps, args.drive)
+    print("%s %s %s: %d lines, %s" % (args.prms, args.dtype, args.drive, len(lines) - 1, lines[-1]))
 
 
 if __name__ == "__main__":

@@ -34,9 +34,9 @@ for i in range(n):
     fn._want = True
     fn.enqueue(i % 16)
     fn._want = False
-    X = fn._last if getattr(fn, "_seq", None) is None else fn._seq.net
+    X = fn._last if fn._seq is None else fn._seq.net
     t0 = time.perf_counter()
-    if getattr(fn, "_seq", None) is None and X._cost_pending:
+    if fn._seq is None and X._cost_pending:
         X.ctx.call("tn_stream_select", fn.nets.index(X)); fn._finish_cost(X); X.ctx.call("tn_stream_select", 0)
     t1 = time.perf_counter(); X.ctx.sync()
     t2 = time.perf_counter(); c = X.d_cost.get_value()[0]
