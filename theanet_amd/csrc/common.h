@@ -94,6 +94,37 @@ int tn_tmp_get(tn_ctx* ctx, size_t bytes, float** out);
 int tn_red_push(tn_ctx* ctx, const float* src, float* out, uint32_t n, uint32_t S, uint32_t stride,
                 uint32_t flip);
 int tn_red_commit(tn_ctx* ctx);
+// the end of every split weight gradient: record the sums of S_w slabs into dW and of S_b slabs into db (the two
+// tn_red_push calls, dW first; flip_w as tn_red_push's flip for dW), then tn_red_commit
+int tn_red_wgrad(tn_ctx* ctx, const float* w_slabs, float* dW, uint32_t n_w, uint32_t S_w, uint32_t stride_w,
+                 const float* b_slabs, float* db, uint32_t n_b, uint32_t S_b, uint32_t stride_b, uint32_t flip_w = 0);
+// Fully-connected layers with n_out <= SK_MAX outputs: the 16-byte-access kernels of fc_skinny.hip where tn_fc_skinny_ok
+// holds (TN_FC_SKINNY, n_in % 4 == 0, aligned pointers), else the scalar kernels of gemm.hip; the tn_fc_* entry points
+// (gemm.hip) dispatch to both
+#define SK_MAX 16
+#define SK_WROWS 64      // rows per slab of the scalar weight gradient (fc_skinny_wgrad_kernel)
+// rows per block (= per slab) of the one-launch SoftmaxLayer training step (fc_skinny_softmax_train; tn_fc_wgrad_ws_bytes
+// sizes the workspace from it)
+__host__ __device__ inline int sk_train_rb(int B) { return B < 2048 ? 4 : 16; }
+bool tn_fc_skinny_ok(int n_in, int n_out, const void* p0, const void* p1, const void* p2);
+int tn_fc_skinny_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B,
+                     int n_in, int n_out, int act, float prm, const uint8_t* mask);
+int tn_fc_skinny_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B,
+                       int n_in, int n_out, float* ws);
+int tn_fc_skinny_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in,
+                       int n_out, const float* prev_a, int act, float prm, const uint8_t* mask);
+int tn_fc_skinny_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, float* dW, float* db,
+                     float* dx, int B, int n_in, int n_out, float* ws, const float* prev_a, int act,
+                     float prm, const uint8_t* mask);
+int tn_fc_skinny_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float* b, float* logits,
+                               int B, int n_in, int n_out, const int32_t* y, int64_t y_row0,
+                               const int64_t* d_row0, float* logprob, float* rowloss, int32_t* pred,
+                               float* rowp, float* dz, float inv_batch, float* dW, float* db, float* dx,
+                               float* ws, int fuse_act, int act, float prm, const uint8_t* mask);
+int tn_fc_skinny_softmax(tn_ctx* ctx, const float* x, const float* W, const float* b, float* logits,
+                         int B, int n_in, int n_out, const int32_t* y, int64_t y_row0,
+                         const int64_t* d_row0, float* logprob, float* rowloss, int32_t* pred,
+                         float* rowp, float* dz, float inv_batch);
 // MATMUL 'bf16x3' products of a fully-connected layer (gemm_b3.hip); the tn_fc_* entry points dispatch here when
 // tn_set_fc_matmul(ctx, 1) is in force and tn_b3_fc_ok says the shape qualifies
 int tn_b3_fc_ok(const float* x, const float* W, int B, int n_in, int n_out);

@@ -380,12 +380,8 @@ int tn_conv_tile_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b
 int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
                          float* db, int nblk, int K, int C, int f) {
     // slabs are in correlation layout: the sum flips every f x f block back (reduce.hip)
-    int rc = tn_red_push(ctx, partial, dW, (uint32_t)(K * C * f * f), (uint32_t)nblk,
-                         (uint32_t)(K * C * f * f), (uint32_t)(f * f));
-    if (rc) return rc;
-    rc = tn_red_push(ctx, dbpartial, db, (uint32_t)K, (uint32_t)nblk, (uint32_t)K, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, partial, dW, (uint32_t)(K * C * f * f), (uint32_t)nblk, (uint32_t)(K * C * f * f), dbpartial,
+                        db, (uint32_t)K, (uint32_t)nblk, (uint32_t)K, (uint32_t)(f * f));
 }
 
 extern "C" {

@@ -503,11 +503,7 @@ int C8_API(tn_c8_conv1_wgrad)(tn_ctx* ctx, const void* x, const void* dz, float*
     if (pooled) c8_conv1_wgrad_kernel<C8E, true><<<grid, 256, 0, ctx->stream>>>(g);
     else c8_conv1_wgrad_kernel<C8E, false><<<grid, 256, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
-    rc = tn_red_push(ctx, g.ws, dW, (uint32_t)n, g.nslab, (uint32_t)n, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.dbws, db, (uint32_t)K, g.nslab, (uint32_t)K, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, g.ws, dW, (uint32_t)n, g.nslab, (uint32_t)n, g.dbws, db, (uint32_t)K, g.nslab, (uint32_t)K);
 }
 
 }  // extern "C"

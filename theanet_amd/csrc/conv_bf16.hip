@@ -14,7 +14,7 @@
 //   dgrad   : the same kernel: rows = the C input maps, kk = (k, u', v'), weight element W[k][c][u'][v'], gathered element
 //             dz[n, k, (y + pad - (f-1) + u') / s, (x + pad - (f-1) + v') / s] where the stride divides (otherwise zero)
 //   wgrad   : dW[k][kk] = sum_m dz[k][m] . G[kk][m] over the N*Ho*Wo pixels, split over pixel slabs that meet in context
-//             scratch and are summed in slab order by the context's reduction (tn_red_push / tn_red_commit): no atomics.
+//             scratch and are summed in slab order by the context's reduction (tn_red_wgrad): no atomics.
 // Both operands sit in LDS reduction-contiguous, rows of 32 bf16 + 16 bytes (80 bytes: the 16-byte slots of 16 consecutive
 // rows fall into distinct banks), read with ds_read_b128 straight into MFMA operands; lanes <-> pixels in the forward /
 // dgrad epilogue (coalesced NCHW stores), lanes <-> kk in the weight gradient.  Two LDS stages: tile t+1 is fetched into
@@ -366,9 +366,6 @@ int tn_cb_conv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, fl
     g.out = ws; g.dbout = ws + (size_t)Sx * n;
     conv_bf16_wgrad_kernel<<<grid, 256, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
-    rc = tn_red_push(ctx, g.out, dW, (uint32_t)n, (uint32_t)Sx, (uint32_t)n, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.dbout, db, (uint32_t)K, (uint32_t)Sx, (uint32_t)K, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, g.out, dW, (uint32_t)n, (uint32_t)Sx, (uint32_t)n, g.dbout, db, (uint32_t)K, (uint32_t)Sx,
+                        (uint32_t)K);
 }

@@ -1944,11 +1944,8 @@ static int c8w_run(tn_ctx* ctx, C8WG& g, float* dW, float* db, bool pool) {
     else C8W_GO(1, 1);
 #undef C8W_GO
     if (rc) return rc;
-    rc = tn_red_push(ctx, g.ws, dW, (uint32_t)n, (uint32_t)g.S, (uint32_t)n, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.dbws, db, (uint32_t)g.K, (uint32_t)g.S, (uint32_t)g.K, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, g.ws, dW, (uint32_t)n, (uint32_t)g.S, (uint32_t)n, g.dbws, db, (uint32_t)g.K, (uint32_t)g.S,
+                        (uint32_t)g.K);
 }
 
 // ---- NCHW fp32 <-> c8 fp16 -------------------------------------------------------------------------------

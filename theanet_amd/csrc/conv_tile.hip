@@ -588,9 +588,6 @@ static int cw_launch(tn_ctx* ctx, ConvWG& g) {
     return TN_OK;
 }
 
-int tn_red_push(tn_ctx* ctx, const float* src, float* out, uint32_t n, uint32_t S, uint32_t stride, uint32_t flip);
-int tn_red_commit(tn_ctx* ctx);
-
 static int cw_run(tn_ctx* ctx, ConvWG& g, float* dW, float* db, bool pool) {
     TN_REQUIRE(cw_geometry(g, ctx->num_cus), "conv_tile_wgrad: unsupported shape");
     TN_REQUIRE((long long)g.N * g.C * g.H * g.Wd < (1ll << 31) && (long long)g.N * g.K * g.H * g.Wd < (1ll << 31),
@@ -603,11 +600,8 @@ static int cw_run(tn_ctx* ctx, ConvWG& g, float* dW, float* db, bool pool) {
     if (pool) rc = NFT == 2 ? cw_launch<2, true>(ctx, g) : cw_launch<1, true>(ctx, g);
     else rc = NFT == 2 ? cw_launch<2, false>(ctx, g) : cw_launch<1, false>(ctx, g);
     if (rc) return rc;
-    rc = tn_red_push(ctx, g.ws, dW, (uint32_t)n, (uint32_t)(g.S * PS), (uint32_t)n, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.dbws, db, (uint32_t)g.K, (uint32_t)g.S, (uint32_t)g.K, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, g.ws, dW, (uint32_t)n, (uint32_t)(g.S * PS), (uint32_t)n, g.dbws, db, (uint32_t)g.K,
+                        (uint32_t)g.S, (uint32_t)g.K);
 }
 
 int tn_conv_tile_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C,
@@ -862,11 +856,8 @@ static int cs_run(tn_ctx* ctx, ConvSG& g, float* dW, float* db, bool pool) {
     if (pool) conv_tile_wgrad_smallc_kernel<true><<<grid, 256, lds, ctx->stream>>>(g);
     else conv_tile_wgrad_smallc_kernel<false><<<grid, 256, lds, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
-    rc = tn_red_push(ctx, g.ws, dW, (uint32_t)n, (uint32_t)(g.S * 4), (uint32_t)n, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.dbws, db, (uint32_t)g.K, (uint32_t)g.S, (uint32_t)g.K, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, g.ws, dW, (uint32_t)n, (uint32_t)(g.S * 4), (uint32_t)n, g.dbws, db, (uint32_t)g.K,
+                        (uint32_t)g.S, (uint32_t)g.K);
 }
 
 int tn_conv_tile_smallc_bwd(tn_ctx* ctx, const float* x, const float* g_, const float* y, const uint8_t* mask,

@@ -7,11 +7,10 @@
 //                                        N = outputs, reduction over rows; slabs summed by reduce.hip
 //   dgrad  dx = (dz W^T) act'(a) mask    VALU: thread = 4 input features, dz rows as scalar loads
 // Requires n_in % 4 == 0 and 16-byte aligned rows (tn_fc_skinny_ok); anything else keeps the
-// scalar kernels in gemm.hip.
+// scalar kernels in gemm.hip (fc_route there chooses).  SK_MAX and the prototypes of the host side: common.h.
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define SK_MAX 16
 
 __device__ __forceinline__ f32x4 sk_mfma(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -288,7 +287,6 @@ __global__ __launch_bounds__(256) void fc_skinny_bwd_pair(
 // RB = rows per block: 16, or 4 for short batches (a 512-image shard of the 8-GPU run, wide6's 128 images): the block's
 // time is a chain of latencies that does not shrink with its rows, so short batches are spread over 4x the blocks
 // (rows 4.. of the 16-row logits tile are duplicates and go nowhere).
-__host__ __device__ inline int sk_train_rb(int B) { return B < 2048 ? 4 : 16; }
 template <int NOUT, int RB>
 __global__ __launch_bounds__(256) void fc_skinny_softmax_train(
     const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ b,
@@ -482,17 +480,19 @@ int tn_fc_skinny_softmax(tn_ctx* ctx, const float* x, const float* W, const floa
     return TN_OK;
 }
 
+// S slabs of (n_in + 1) * n_out floats: a slab's dW rows, then its db row
+static int sk_red(tn_ctx* ctx, const float* ws, float* dW, float* db, int S, int n_in, int n_out) {
+    const int per = (n_in + 1) * n_out, MN = n_in * n_out;
+    return tn_red_wgrad(ctx, ws, dW, (uint32_t)MN, (uint32_t)S, (uint32_t)per, ws + MN, db, (uint32_t)n_out, (uint32_t)S,
+                        (uint32_t)per);
+}
+
 int tn_fc_skinny_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B,
                        int n_in, int n_out, float* ws) {
     const int S = cdiv(B, 128);
     fc_skinny_wgrad_mfma<<<dim3(cdiv(n_in + 1, 64), S), 256, 0, ctx->stream>>>(x, dz, ws, B, n_in, n_out);
     TN_LAUNCH_CHECK();
-    const int per = (n_in + 1) * n_out, MN = n_in * n_out;
-    int rc = tn_red_push(ctx, ws, dW, (uint32_t)MN, (uint32_t)S, (uint32_t)per, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, ws + MN, db, (uint32_t)n_out, (uint32_t)S, (uint32_t)per, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return sk_red(ctx, ws, dW, db, S, n_in, n_out);
 }
 
 int tn_fc_skinny_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, float* dW, float* db,
@@ -513,12 +513,7 @@ int tn_fc_skinny_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* 
     }
 #undef SKP_GO
     TN_LAUNCH_CHECK();
-    const int per = (n_in + 1) * n_out, MN = n_in * n_out;
-    int rc = tn_red_push(ctx, ws, dW, (uint32_t)MN, (uint32_t)S, (uint32_t)per, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, ws + MN, db, (uint32_t)n_out, (uint32_t)S, (uint32_t)per, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return sk_red(ctx, ws, dW, db, S, n_in, n_out);
 }
 
 // ws must hold cdiv(B, sk_train_rb(B)) slabs of (n_in + 1) * n_out floats (tn_fc_wgrad_ws_bytes provides it)
@@ -547,12 +542,7 @@ int tn_fc_skinny_softmax_train(tn_ctx* ctx, const float* x, const float* W, cons
     }
 #undef SKT_GO
     TN_LAUNCH_CHECK();
-    const int per = (n_in + 1) * n_out, MN = n_in * n_out;
-    int rc = tn_red_push(ctx, ws, dW, (uint32_t)MN, (uint32_t)S, (uint32_t)per, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, ws + MN, db, (uint32_t)n_out, (uint32_t)S, (uint32_t)per, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return sk_red(ctx, ws, dW, db, S, n_in, n_out);
 }
 
 int tn_fc_skinny_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in,

@@ -448,11 +448,8 @@ int C8_API(tn_c8_fcg_wgrad)(tn_ctx* ctx, const void* x, const float* dz, float* 
     g.dbws = g.ws + (size_t)S * n;
     fcg_wgrad_kernel<C8E><<<dim3(kb, nb, S), 256, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
-    rc = tn_red_push(ctx, g.ws, dW, (uint32_t)n, (uint32_t)S, (uint32_t)n, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.dbws, db, (uint32_t)n_out, (uint32_t)S, (uint32_t)n_out, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, g.ws, dW, (uint32_t)n, (uint32_t)S, (uint32_t)n, g.dbws, db, (uint32_t)n_out, (uint32_t)S,
+                        (uint32_t)n_out);
 }
 
 }  // extern "C"

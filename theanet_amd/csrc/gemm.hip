@@ -1052,24 +1052,19 @@ static inline int vec_ok(const void* p, int ld) {
     return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0);
 }
 
-static int tn_tune_tile() { return 0; }       // 0 auto (1 / 2 would force 64x64 / 128x64: sweeps of rounds 1-2)
-
-static int tn_tune_bk() { return 16; }        // K-tile depth (32 measured slower at the layer shapes of the configs)
-
 // FAST needs aligned operands; row-contiguous operands also need an extent % 4 == 0 so that
 // clamped float4 groups stay inside the matrix
 template <bool AKC, bool BKC>
 static bool gemm_fast_ok(const GemmArgs& g) {
     return g.a_vec && g.b_vec && (AKC || (g.M % 4 == 0 && g.M >= 4)) &&
-           (BKC || (g.N % 4 == 0 && g.N >= 4)) && tn_tune_tile() != 9;
+           (BKC || (g.N % 4 == 0 && g.N >= 4));
 }
 
 // the 16-byte epilogue (and with it the inline dropout) needs 4-column groups that never straddle
 // the matrix edge and aligned C / side operands
 static bool gemm_cvec_ok(const GemmArgs& g) {
-    const bool vec_on = true;
     auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) == 0; };
-    return vec_on && g.ldc % 4 == 0 && g.N % 4 == 0 && g.N >= 4 && al(g.C, 15) && al(g.prev_a, 15) &&
+    return g.ldc % 4 == 0 && g.N % 4 == 0 && g.N >= 4 && al(g.C, 15) && al(g.prev_a, 15) &&
            al(g.mask, 3) && al(g.drop_out, 3) && (g.elem0 & 3) == 0;
 }
 
@@ -1114,13 +1109,32 @@ static bool gemm_dma_ok(const GemmArgs& g, int S) {
     return ea * 4 < (1ll << 32) && eb * 4 < (1ll << 32);
 }
 
+// cycle stamps of the DMA kernel (TN_GEMM_DBG): 8 words per wave, 4 waves per block, 65536 records.  The launchers return
+// nothing: a stamp buffer that cannot be had, or a grid beyond its 65536 records, just runs unstamped -- g.dbg stays
+// NULL and the kernel writes no stamps
+static void gemm_dbg_arm(tn_ctx* ctx, GemmArgs& g, int grid) {
+    if (!gemm_dbg_buf && hipMalloc(&gemm_dbg_buf, 8 * sizeof(unsigned long long) * 65536) != hipSuccess) gemm_dbg_buf = nullptr;
+    if (gemm_dbg_buf && grid * 4 <= 65536 &&
+        hipMemsetAsync(gemm_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream) == hipSuccess)
+        g.dbg = gemm_dbg_buf;
+}
+
+template <bool AKC, bool BKC, int NS>
+static void launch_dma(tn_ctx* ctx, GemmArgs& g, int grid, int pad, int nb) {
+    if (tn_knob(TN_K_GEMM_DBG)) {
+        gemm_dbg_arm(ctx, g, grid);
+        gemm_f32_dma<AKC, BKC, NS, true><<<grid, 256, pad, ctx->stream>>>(g, nb);
+    } else
+        gemm_f32_dma<AKC, BKC, NS><<<grid, 256, pad, ctx->stream>>>(g, nb);
+}
+
+// The tile (128 x 64 once that still gives every CU two blocks, else 64 x 64) and the K-tile depth (16) are fixed: forcing
+// 64 x 64 or 128 x 64 everywhere lost to this rule in the sweeps of rounds 1-2, and a K tile of 32 measured slower at the
+// layer shapes of the configs.
 template <bool AKC, bool BKC, bool BSUM>
 static void launch_gemm(tn_ctx* ctx, GemmArgs& g, int S) {
     const bool fast = gemm_fast_ok<AKC, BKC>(g);
-    bool big = (long long)cdiv(g.M, 128) * cdiv(g.N, 64) * S >= 2 * ctx->num_cus;
-    if (tn_tune_tile() == 1) big = false;
-    if (tn_tune_tile() == 2) big = true;
-    if (!fast) big = false;
+    const bool big = fast && (long long)cdiv(g.M, 128) * cdiv(g.N, 64) * S >= 2 * ctx->num_cus;
     g.c_vec = fast && gemm_cvec_ok(g);
     g.S = S;
     g.NT = cdiv(g.N, 64);
@@ -1134,28 +1148,13 @@ static void launch_gemm(tn_ctx* ctx, GemmArgs& g, int S) {
         const int pad = tn_knob(TN_K_GEMM_DMA_PAD), nsf = tn_knob(TN_K_GEMM_DMA_NS);
         const int grid = nb + ((BSUM && !BKC) ? S * g.NT : 0);
         // two blocks per CU or fewer: the deep ring; else four stages
-        const int ns = nsf ? nsf : (nb <= 2 * ctx->num_cus ? 8 : 4);
-        if (tn_knob(TN_K_GEMM_DBG)) {
-            // (cycle stamps: 8 words per wave, 4 waves per block, 65536 records)
-            // (this launcher returns nothing: a stamp buffer that cannot be had, or a grid beyond its 65536 records,
-            // just runs unstamped -- g.dbg stays NULL and the kernel writes no stamps)
-            if (!gemm_dbg_buf && hipMalloc(&gemm_dbg_buf, 8 * sizeof(unsigned long long) * 65536) != hipSuccess) gemm_dbg_buf = nullptr;
-            if (gemm_dbg_buf && grid * 4 <= 65536 &&
-                hipMemsetAsync(gemm_dbg_buf, 0, 8 * sizeof(unsigned long long) * 65536, ctx->stream) == hipSuccess)
-                g.dbg = gemm_dbg_buf;
-            if (ns == 8) gemm_f32_dma<AKC, BKC, 8, true><<<grid, 256, pad, ctx->stream>>>(g, nb);
-            else if (ns == 2) gemm_f32_dma<AKC, BKC, 2, true><<<grid, 256, pad, ctx->stream>>>(g, nb);
-            else gemm_f32_dma<AKC, BKC, 4, true><<<grid, 256, pad, ctx->stream>>>(g, nb);
-        } else if (ns == 8)
-            gemm_f32_dma<AKC, BKC, 8><<<grid, 256, pad, ctx->stream>>>(g, nb);
-        else if (ns == 2)
-            gemm_f32_dma<AKC, BKC, 2><<<grid, 256, pad, ctx->stream>>>(g, nb);
-        else
-            gemm_f32_dma<AKC, BKC, 4><<<grid, 256, pad, ctx->stream>>>(g, nb);
+        switch (nsf ? nsf : (nb <= 2 * ctx->num_cus ? 8 : 4)) {
+            case 8: launch_dma<AKC, BKC, 8>(ctx, g, grid, pad, nb); break;
+            case 2: launch_dma<AKC, BKC, 2>(ctx, g, grid, pad, nb); break;
+            default: launch_dma<AKC, BKC, 4>(ctx, g, grid, pad, nb);
+        }
     } else if (big)
         gemm_f32_fast<AKC, BKC, BSUM, 2, 1, 16><<<grid, 256, 0, ctx->stream>>>(g);
-    else if (tn_tune_bk() == 32)
-        gemm_f32_fast<AKC, BKC, BSUM, 1, 1, 32><<<grid, 256, 0, ctx->stream>>>(g);
     else
         gemm_f32_fast<AKC, BKC, BSUM, 1, 1, 16><<<grid, 256, 0, ctx->stream>>>(g);
 }
@@ -1185,9 +1184,8 @@ static int wgrad_splits(int B, int n_in, int n_out) {
 }
 
 // =====================================================================================
-// skinny layers: n_out <= 16
+// skinny layers: n_out <= SK_MAX (common.h), the scalar kernels
 // =====================================================================================
-#define SK_MAX 16
 
 template <int CTRL>
 __device__ __forceinline__ float gdpp(float v) {
@@ -1293,7 +1291,6 @@ __global__ __launch_bounds__(256) void fc_skinny_dgrad_kernel(
 // wgrad: thread = one input feature k, block.y = a chunk of SK_WROWS rows.  The chunk's dz rows
 // are staged in LDS (read back as wave broadcasts), the x values are loaded 32 at a time (all
 // in flight).  partial[chunk][k][n], dbpartial[chunk][n].
-#define SK_WROWS 64
 __global__ __launch_bounds__(256) void fc_skinny_wgrad_kernel(
     const float* __restrict__ x, const float* __restrict__ dz, float* __restrict__ partial,
     float* __restrict__ dbpartial, int B, int n_in, int n_out) {
@@ -1338,27 +1335,82 @@ __global__ __launch_bounds__(256) void fc_skinny_wgrad_kernel(
 }
 
 
-// fc_skinny.hip: 16-byte-access kernels for n_out <= 16
-bool tn_fc_skinny_ok(int n_in, int n_out, const void* p0, const void* p1, const void* p2);
-int tn_fc_skinny_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B,
-                     int n_in, int n_out, int act, float prm, const uint8_t* mask);
-int tn_fc_skinny_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B,
-                       int n_in, int n_out, float* ws);
-int tn_fc_skinny_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in,
-                       int n_out, const float* prev_a, int act, float prm, const uint8_t* mask);
+// =====================================================================================
+// dense layers: which kernel family runs a product, and the products' GemmArgs
+// =====================================================================================
+// The families, in the order every entry point tries them.  FC_SCALAR / FC_TILED are this file's own kernels.
+enum FcRoute {
+    FC_BF16,      // MATMUL 'bfloat16' (gemm_bf16.hip): any shape while the mode is in force
+    FC_B3,        // MATMUL 'bf16x3' (gemm_b3.hip): where tn_b3_fc_ok(p, q) holds
+    FC_SKINNY,    // n_out <= SK_MAX, 16-byte accesses (fc_skinny.hip): where tn_fc_skinny_ok(s0, s1, s2) holds
+    FC_SCALAR,    // n_out <= SK_MAX otherwise: fc_skinny_*_kernel above
+    FC_TILED      // everything else: the gemm_f32_* kernels
+};
+// p, q: the two operands tn_b3_fc_ok looks at; s0, s1, s2: the pointers tn_fc_skinny_ok looks at.  What an entry point
+// passes for them is part of its contract:
+//   forward          (x, W)    (x, -, -)
+//   weight gradient  (x, dz)   (x, -, -)          [tn_fc_bwd asks with (x, W)]
+//   input gradient   (dz, W)   (dx, prev_a, prev_mask)
+static FcRoute fc_route(tn_ctx* ctx, int B, int n_in, int n_out, const float* p, const float* q, const void* s0,
+                        const void* s1, const void* s2) {
+    if (ctx->fc_bf16) return FC_BF16;
+    if (ctx->fc_b3 && tn_b3_fc_ok(p, q, B, n_in, n_out)) return FC_B3;
+    if (tn_fc_skinny_ok(n_in, n_out, s0, s1, s2)) return FC_SKINNY;
+    return n_out <= SK_MAX ? FC_SCALAR : FC_TILED;
+}
 
-int tn_fc_skinny_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, float* dW, float* db,
-                     float* dx, int B, int n_in, int n_out, float* ws, const float* prev_a, int act,
-                     float prm, const uint8_t* mask);
-int tn_fc_skinny_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float* b, float* logits,
-                               int B, int n_in, int n_out, const int32_t* y, int64_t y_row0,
-                               const int64_t* d_row0, float* logprob, float* rowloss, int32_t* pred,
-                               float* rowp, float* dz, float inv_batch, float* dW, float* db, float* dx,
-                               float* ws, int fuse_act, int act, float prm, const uint8_t* mask);
-int tn_fc_skinny_softmax(tn_ctx* ctx, const float* x, const float* W, const float* b, float* logits,
-                         int B, int n_in, int n_out, const int32_t* y, int64_t y_row0,
-                         const int64_t* d_row0, float* logprob, float* rowloss, int32_t* pred,
-                         float* rowp, float* dz, float inv_batch);
+// a (B, n_out) = act(x W + b) * mask
+static GemmArgs fc_fwd_args(const float* x, const float* W, const float* b, float* a, int B, int n_in, int n_out, int act,
+                            float act_param, const uint8_t* mask) {
+    GemmArgs g{};
+    g.A = x; g.B = W; g.C = a;
+    g.M = B; g.N = n_out; g.K = n_in;
+    g.lda = n_in; g.ldb = n_out; g.ldc = n_out;
+    g.kchunk = cdiv(n_in, BK) * BK;
+    g.epi = EPI_FWD; g.bias = b; g.mask = mask; g.act = act; g.act_prm = act_param;
+    g.a_vec = vec_ok(x, n_in); g.b_vec = vec_ok(W, n_out);
+    return g;
+}
+
+// dW (n_in, n_out) = x^T dz, db = column sums of dz, over *Sx sample slabs (wgrad_splits, fewer where the batch is short).
+// One slab writes dW / db themselves; several write ws ([S][n_in * n_out] then [S][n_out]) and fc_wgrad_sum finishes.
+static GemmArgs fc_wgrad_args(const float* x, const float* dz, float* dW, float* db, int B, int n_in, int n_out, void* ws,
+                              int* Sx) {
+    const int S = wgrad_splits(B, n_in, n_out);
+    GemmArgs g{};
+    g.A = x; g.B = dz;
+    g.M = n_in; g.N = n_out; g.K = B;
+    g.lda = n_in; g.ldb = n_out; g.ldc = n_out;
+    g.kchunk = cdiv(cdiv(B, S), BK) * BK;
+    g.epi = EPI_PLAIN;
+    g.a_vec = vec_ok(x, n_in); g.b_vec = vec_ok(dz, n_out);
+    *Sx = cdiv(B, g.kchunk);
+    if (*Sx == 1) {
+        g.C = dW; g.colsum = db;
+    } else {
+        g.C = (float*)ws; g.colsum = g.C + (size_t)S * n_in * n_out;
+    }
+    return g;
+}
+static int fc_wgrad_sum(tn_ctx* ctx, const GemmArgs& g, int Sx, float* dW, float* db) {
+    if (Sx == 1) return TN_OK;
+    const size_t MN = (size_t)g.M * g.N;
+    return tn_red_wgrad(ctx, g.C, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, g.colsum, db, (uint32_t)g.N, (uint32_t)Sx,
+                        (uint32_t)g.N);
+}
+
+// dx (B, n_in) = (dz W^T) * act'(prev_a) * mask
+static GemmArgs fc_dgrad_args(const float* dz, const float* W, float* dx, int B, int n_in, int n_out, const float* prev_a,
+                              int prev_act, float prev_act_param, const uint8_t* prev_mask) {
+    GemmArgs g{};
+    g.A = dz; g.B = W; g.C = dx;
+    g.M = B; g.N = n_in; g.K = n_out;
+    g.lda = n_out; g.ldb = n_out; g.ldc = n_in;     // B(k,n) = W[n*n_out + k]: k-contiguous
+    g.kchunk = cdiv(n_out, BK) * BK;
+    g.epi = EPI_DGRAD; g.prev_a = prev_a; g.mask = prev_mask; g.act = prev_act; g.act_prm = prev_act_param;
+    g.a_vec = vec_ok(dz, n_out); g.b_vec = vec_ok(W, n_out);
+    return g;
+}
 
 // The output heads stay fp32 under MATMUL 'bfloat16' (gemm_bf16.hip): while a head's entry point runs, the generic
 // products it falls back to for a wide head (tn_fc_fwd / tn_fc_bwd) do not dispatch to the bf16 kernels.
@@ -1476,25 +1528,18 @@ static int fc_dgrad_splits(tn_ctx* ctx, int B, int n_in, int n_out) {
 int tn_fc_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B, int n_in,
               int n_out, int act, float act_param, const uint8_t* mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0, "tn_fc_fwd: bad shape");
-    if (ctx->fc_bf16) return tn_bf_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);      // any shape
-    if (ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out))
-        return tn_b3_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
-    if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr))
-        return tn_fc_skinny_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
+    const FcRoute route = fc_route(ctx, B, n_in, n_out, x, W, x, nullptr, nullptr);
+    if (route == FC_BF16) return tn_bf_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
+    if (route == FC_B3) return tn_b3_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
+    if (route == FC_SKINNY) return tn_fc_skinny_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
     const size_t sk_lds = (size_t)n_in * (n_out + 1) * sizeof(float);
-    if (n_out <= SK_MAX && sk_lds <= 60 * 1024) {
+    if (route == FC_SCALAR && sk_lds <= 60 * 1024) {      // (a W beyond the kernel's LDS runs tiled)
         fc_skinny_fwd_kernel<<<cdiv(B, 8), 256, sk_lds, ctx->stream>>>(
             x, W, b, a, B, n_in, n_out, act, act_param, mask);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
-    GemmArgs g{};
-    g.A = x; g.B = W; g.C = a;
-    g.M = B; g.N = n_out; g.K = n_in;
-    g.lda = n_in; g.ldb = n_out; g.ldc = n_out;
-    g.kchunk = cdiv(n_in, BK) * BK;
-    g.epi = EPI_FWD; g.bias = b; g.mask = mask; g.act = act; g.act_prm = act_param;
-    g.a_vec = vec_ok(x, n_in); g.b_vec = vec_ok(W, n_out);
+    GemmArgs g = fc_fwd_args(x, W, b, a, B, n_in, n_out, act, act_param, mask);
     const int S = fc_fwd_splits(ctx, B, n_in, n_out);
     if (S > 1) return fc_fwd_splitk(ctx, g, S, mask);
     if (gemm_deep_ok<false>(ctx, g))
@@ -1510,18 +1555,14 @@ int tn_fc_fwd_dropout(tn_ctx* ctx, const float* x, const float* W, const float* 
                       uint64_t seed, uint32_t step, const uint32_t* d_step, uint64_t elem0) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && mask_out != nullptr, "tn_fc_fwd_dropout: bad arguments");
     TN_REQUIRE(!ctx->fc_bf16 || (x && W && b && a), "tn_fc_fwd_dropout (MATMUL 'bfloat16'): bad arguments");    // before the mask is drawn
-    GemmArgs g{};
-    g.A = x; g.B = W; g.C = a;
-    g.M = B; g.N = n_out; g.K = n_in;
-    g.lda = n_in; g.ldb = n_out; g.ldc = n_out;
-    g.kchunk = cdiv(n_in, BK) * BK;
-    g.epi = EPI_FWD; g.bias = b; g.act = act; g.act_prm = act_param;
-    g.a_vec = vec_ok(x, n_in); g.b_vec = vec_ok(W, n_out);
+    GemmArgs g = fc_fwd_args(x, W, b, a, B, n_in, n_out, act, act_param, nullptr);
     g.drop_out = mask_out; g.pdrop = pdrop; g.dk0 = (uint32_t)seed; g.dk1 = (uint32_t)(seed >> 32);
     g.dstep = step; g.d_step = d_step; g.elem0 = elem0;
-    // (MATMUL 'bfloat16': the mask from its own launch -- the same bits -- then the product with that mask)
-    if (!ctx->fc_bf16 && !(ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out)) && n_out > SK_MAX && fc_fwd_splits(ctx, B, n_in, n_out) == 1 && gemm_fast_ok<true, false>(g) &&
-        gemm_cvec_ok(g)) {
+    // The mask is drawn in the product's epilogue only on the tiled fp32 route, with one K slab and a 16-byte epilogue;
+    // every other route (MATMUL 'bfloat16' included) takes the mask from its own launch -- the same bits -- and then
+    // runs the product with that mask.
+    if (fc_route(ctx, B, n_in, n_out, x, W, x, nullptr, nullptr) == FC_TILED && fc_fwd_splits(ctx, B, n_in, n_out) == 1 &&
+        gemm_fast_ok<true, false>(g) && gemm_cvec_ok(g)) {
         if (gemm_deep_ok<false>(ctx, g))
             launch_deep<false>(ctx, g);
         else
@@ -1538,7 +1579,7 @@ size_t tn_fc_wgrad_ws_bytes(int B, int n_in, int n_out) {
     if (n_out <= SK_MAX) {
         const int chunks = cdiv(B, SK_WROWS);
         const size_t a = ((size_t)chunks * n_in * n_out + (size_t)chunks * n_out) * sizeof(float) + 64;
-        const size_t t = (size_t)cdiv(B, B < 2048 ? 4 : 16) * (n_in + 1) * n_out * sizeof(float) + 64;   // softmax_train slabs (fc_skinny.hip sk_train_rb)
+        const size_t t = (size_t)cdiv(B, sk_train_rb(B)) * (n_in + 1) * n_out * sizeof(float) + 64;   // softmax_train slabs
         return a > t ? a : t;
     }
     const int S = wgrad_splits(B, n_in, n_out);
@@ -1548,13 +1589,13 @@ size_t tn_fc_wgrad_ws_bytes(int B, int n_in, int n_out) {
 int tn_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in,
                 int n_out, void* ws) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && ws != nullptr, "tn_fc_wgrad: bad arguments");
-    if (ctx->fc_bf16)
+    const FcRoute route = fc_route(ctx, B, n_in, n_out, x, dz, x, nullptr, nullptr);
+    if (route == FC_BF16)
         return tn_bf_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
-    if (ctx->fc_b3 && tn_b3_fc_ok(x, dz, B, n_in, n_out))
+    if (route == FC_B3)
         return tn_b3_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
-    if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr))
-        return tn_fc_skinny_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws);
-    if (n_out <= SK_MAX) {
+    if (route == FC_SKINNY) return tn_fc_skinny_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws);
+    if (route == FC_SCALAR) {
         const int chunks = cdiv(B, SK_WROWS);
         float* wsC = (float*)ws;
         float* wsB = wsC + (size_t)chunks * n_in * n_out;
@@ -1562,88 +1603,44 @@ int tn_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* 
             x, dz, wsC, wsB, B, n_in, n_out);
         TN_LAUNCH_CHECK();
         const int MN = n_in * n_out;
-        int rc = tn_red_push(ctx, wsC, dW, (uint32_t)MN, (uint32_t)chunks, (uint32_t)MN, 0);
-        if (rc) return rc;
-        rc = tn_red_push(ctx, wsB, db, (uint32_t)n_out, (uint32_t)chunks, (uint32_t)n_out, 0);
-        if (rc) return rc;
-        return tn_red_commit(ctx);
+        return tn_red_wgrad(ctx, wsC, dW, (uint32_t)MN, (uint32_t)chunks, (uint32_t)MN, wsB, db, (uint32_t)n_out,
+                            (uint32_t)chunks, (uint32_t)n_out);
     }
-    const int S = wgrad_splits(B, n_in, n_out);
-    float* wsC = (float*)ws;
-    float* wsB = wsC + (size_t)S * n_in * n_out;
-    GemmArgs g{};
-    g.A = x; g.B = dz;
-    g.M = n_in; g.N = n_out; g.K = B;
-    g.lda = n_in; g.ldb = n_out; g.ldc = n_out;
-    g.kchunk = cdiv(cdiv(B, S), BK) * BK;
-    g.epi = EPI_PLAIN;
-    g.a_vec = vec_ok(x, n_in); g.b_vec = vec_ok(dz, n_out);
-    const int Sx = cdiv(B, g.kchunk);
-    if (Sx == 1) {
-        g.C = dW; g.colsum = db;
-    } else {
-        g.C = wsC; g.colsum = wsB;
-    }
+    int Sx;
+    GemmArgs g = fc_wgrad_args(x, dz, dW, db, B, n_in, n_out, ws, &Sx);
     launch_gemm<false, false, true>(ctx, g, Sx);
     TN_LAUNCH_CHECK();
-    if (Sx > 1) {
-        const size_t MN = (size_t)n_in * n_out;
-        int blocks = cdiv(cdiv(MN, 4), 256);
-        if (blocks < cdiv(n_out, 256)) blocks = cdiv(n_out, 256);
-        (void)blocks;
-        int rc = tn_red_push(ctx, wsC, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, 0);
-        if (rc) return rc;
-        rc = tn_red_push(ctx, wsB, db, (uint32_t)n_out, (uint32_t)Sx, (uint32_t)n_out, 0);
-        if (rc) return rc;
-        return tn_red_commit(ctx);
-    }
-    return TN_OK;
+    return fc_wgrad_sum(ctx, g, Sx, dW, db);
 }
 
 int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, float* dW, float* db,
               float* dx, int B, int n_in, int n_out, void* ws, const float* prev_a, int prev_act,
               float prev_act_param, const uint8_t* prev_mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0 && ws != nullptr && dx != nullptr, "tn_fc_bwd: bad arguments");
-    if (ctx->fc_bf16) {
+    // A family runs the pair only where BOTH products qualify for it (the weight gradient is asked about with (x, W)
+    // here, not tn_fc_wgrad's (x, dz)); otherwise each product takes its own route at the bottom.
+    const FcRoute rw = fc_route(ctx, B, n_in, n_out, x, W, x, nullptr, nullptr);
+    const FcRoute rd = fc_route(ctx, B, n_in, n_out, dz, W, dx, prev_a, prev_mask);
+    if (rw == FC_BF16) {       // the mode, not the shape: rd is FC_BF16 too
         TN_REQUIRE(x && dz && W && dW && db, "tn_fc_bwd (MATMUL 'bfloat16'): bad arguments");      // before either product
         int rc = tn_bf_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
         if (rc) return rc;
         return tn_bf_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     }
-    if (ctx->fc_b3 && tn_b3_fc_ok(x, W, B, n_in, n_out) && tn_b3_fc_ok(dz, W, B, n_in, n_out)) {
+    if (rw == FC_B3 && rd == FC_B3) {
         int rc = tn_b3_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
         if (rc) return rc;
         return tn_b3_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     }
-    if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr) &&
-        tn_fc_skinny_ok(n_in, n_out, dx, prev_a, prev_mask))
+    if (rw == FC_SKINNY && rd == FC_SKINNY)
         return tn_fc_skinny_bwd(ctx, x, dz, W, dW, db, dx, B, n_in, n_out, (float*)ws, prev_a, prev_act,
                                 prev_act_param, prev_mask);
     if (n_out > SK_MAX && fc_dgrad_splits(ctx, B, n_in, n_out) == 1) {
-        // weight gradient (split-K slabs) and input gradient as ONE launch of interleaved blocks
-        const int S = wgrad_splits(B, n_in, n_out);
-        float* wsC = (float*)ws;
-        float* wsB = wsC + (size_t)S * n_in * n_out;
-        GemmArgs g1{}, g2{};
-        g1.A = x; g1.B = dz;
-        g1.M = n_in; g1.N = n_out; g1.K = B;
-        g1.lda = n_in; g1.ldb = n_out; g1.ldc = n_out;
-        g1.kchunk = cdiv(cdiv(B, S), BK) * BK;
-        g1.epi = EPI_PLAIN;
-        g1.a_vec = vec_ok(x, n_in); g1.b_vec = vec_ok(dz, n_out);
-        const int Sx = cdiv(B, g1.kchunk);
-        if (Sx == 1) {
-            g1.C = dW; g1.colsum = db;
-        } else {
-            g1.C = wsC; g1.colsum = wsB;
-        }
-        g2.A = dz; g2.B = W; g2.C = dx;
-        g2.M = B; g2.N = n_in; g2.K = n_out;
-        g2.lda = n_out; g2.ldb = n_out; g2.ldc = n_in;
-        g2.kchunk = cdiv(n_out, BK) * BK;
-        g2.epi = EPI_DGRAD; g2.prev_a = prev_a; g2.mask = prev_mask; g2.act = prev_act;
-        g2.act_prm = prev_act_param;
-        g2.a_vec = vec_ok(dz, n_out); g2.b_vec = vec_ok(W, n_out);
+        // weight gradient (split-K slabs) and input gradient as ONE launch of interleaved blocks, where both are
+        // eligible for the 64 x 64 fast kernel (gemm_setup_small)
+        int Sx;
+        GemmArgs g1 = fc_wgrad_args(x, dz, dW, db, B, n_in, n_out, ws, &Sx);
+        GemmArgs g2 = fc_dgrad_args(dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
         const int n1 = gemm_setup_small<false, false>(g1, Sx), n2 = gemm_setup_small<true, true>(g2, 1);
         if (n1 > 0 && n2 > 0) {
             int nrider = 0;
@@ -1695,15 +1692,7 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
                 gemm_f32_pair<false, false, true, true, true, false><<<n1 + n2 + nrider, 256, rlds, ctx->stream>>>(
                     g1, g2, n1, n2, rider);
             TN_LAUNCH_CHECK();
-            if (Sx > 1) {
-                const size_t MN = (size_t)n_in * n_out;
-                int rc = tn_red_push(ctx, wsC, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, 0);
-                if (rc) return rc;
-                rc = tn_red_push(ctx, wsB, db, (uint32_t)n_out, (uint32_t)Sx, (uint32_t)n_out, 0);
-                if (rc) return rc;
-                return tn_red_commit(ctx);
-            }
-            return TN_OK;
+            return fc_wgrad_sum(ctx, g1, Sx, dW, db);
         }
     }
     int rc = tn_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, ws);
@@ -1714,26 +1703,20 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
 int tn_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in, int n_out,
                 const float* prev_a, int prev_act, float prev_act_param, const uint8_t* prev_mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0, "tn_fc_dgrad: bad shape");
-    if (ctx->fc_bf16)
+    const FcRoute route = fc_route(ctx, B, n_in, n_out, dz, W, dx, prev_a, prev_mask);
+    if (route == FC_BF16)
         return tn_bf_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
-    if (ctx->fc_b3 && tn_b3_fc_ok(dz, W, B, n_in, n_out))
+    if (route == FC_B3)
         return tn_b3_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
-    if (tn_fc_skinny_ok(n_in, n_out, dx, prev_a, prev_mask))
-        return tn_fc_skinny_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param,
-                                  prev_mask);
-    if (n_out <= SK_MAX) {
+    if (route == FC_SKINNY)
+        return tn_fc_skinny_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
+    if (route == FC_SCALAR) {
         fc_skinny_dgrad_kernel<<<dim3(cdiv(n_in, 256), cdiv(B, 16)), 256, 0, ctx->stream>>>(
             dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
-    GemmArgs g{};
-    g.A = dz; g.B = W; g.C = dx;
-    g.M = B; g.N = n_in; g.K = n_out;
-    g.lda = n_out; g.ldb = n_out; g.ldc = n_in;     // B(k,n) = W[n*n_out + k]: k-contiguous
-    g.kchunk = cdiv(n_out, BK) * BK;
-    g.epi = EPI_DGRAD; g.prev_a = prev_a; g.mask = prev_mask; g.act = prev_act; g.act_prm = prev_act_param;
-    g.a_vec = vec_ok(dz, n_out); g.b_vec = vec_ok(W, n_out);
+    GemmArgs g = fc_dgrad_args(dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     const int S = fc_dgrad_splits(ctx, B, n_in, n_out);
     if (S > 1) {
         // few rows, a long reduction and a big weight matrix (wide6's 128 x 16384 <- 1024): a block per output

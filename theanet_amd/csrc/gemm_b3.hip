@@ -296,7 +296,7 @@ int tn_b3_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int 
 }
 
 // dW (n_in, n_out) = x^T . dz, db = column sums of dz; S sample slabs into ws ([S][n_in * n_out] then [S][n_out]),
-// recorded for the step's reduction (tn_red_push) unless S == 1
+// recorded for the step's reduction (tn_red_wgrad) unless S == 1
 int tn_b3_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in, int n_out, float* ws,
                    int S) {
     B3Args g{};
@@ -312,9 +312,6 @@ int tn_b3_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, floa
     g.C = ws; g.colsum = ws + (size_t)S * MN;
     int rc = b3_launch<false, false>(ctx, g, Sx);
     if (rc) return rc;
-    rc = tn_red_push(ctx, ws, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.colsum, db, (uint32_t)n_out, (uint32_t)Sx, (uint32_t)n_out, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, ws, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, g.colsum, db, (uint32_t)n_out, (uint32_t)Sx,
+                        (uint32_t)n_out);
 }

@@ -23,7 +23,7 @@
 // ANY shape runs here (no fp32 fall-back for a HiddenLayer): rows / columns / reduction indices beyond the operand are
 // staged as zeros and never stored.  Operands whose rows are 16-byte aligned with extents that are multiples of 4 are
 // fetched as float4; every other operand element by element with clamped addresses.
-// Split-K slabs for the weight gradient, finished in slab order by the step's reduction (tn_red_push / tn_red_commit).
+// Split-K slabs for the weight gradient, finished in slab order by the step's reduction (tn_red_wgrad).
 #include "common.h"
 
 #include <type_traits>
@@ -302,7 +302,7 @@ int tn_bf_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int 
 }
 
 // dW (n_in, n_out) = x^T . dz, db = column sums of dz; S sample slabs into ws ([S][n_in * n_out] then [S][n_out]),
-// recorded for the step's reduction (tn_red_push: slabs are added in slab order) unless one slab covers B
+// recorded for the step's reduction (tn_red_wgrad: slabs are added in slab order) unless one slab covers B
 int tn_bf_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B, int n_in, int n_out, float* ws,
                    int S) {
     TN_REQUIRE(x && dz && dW && db && ws && B > 0 && n_in > 0 && n_out > 0 && S > 0,
@@ -320,9 +320,6 @@ int tn_bf_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, floa
     g.C = ws; g.colsum = ws + (size_t)S * MN;
     int rc = bf_launch<false, false>(ctx, g, Sx);
     if (rc) return rc;
-    rc = tn_red_push(ctx, ws, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, 0);
-    if (rc) return rc;
-    rc = tn_red_push(ctx, g.colsum, db, (uint32_t)n_out, (uint32_t)Sx, (uint32_t)n_out, 0);
-    if (rc) return rc;
-    return tn_red_commit(ctx);
+    return tn_red_wgrad(ctx, ws, dW, (uint32_t)MN, (uint32_t)Sx, (uint32_t)MN, g.colsum, db, (uint32_t)n_out, (uint32_t)Sx,
+                        (uint32_t)n_out);
 }

@@ -124,6 +124,15 @@ int tn_red_push(tn_ctx* ctx, const float* src, float* out, uint32_t n, uint32_t 
 
 int tn_red_commit(tn_ctx* ctx) { return ctx->defer ? TN_OK : tn_red_flush(ctx); }
 
+int tn_red_wgrad(tn_ctx* ctx, const float* w_slabs, float* dW, uint32_t n_w, uint32_t S_w, uint32_t stride_w,
+                 const float* b_slabs, float* db, uint32_t n_b, uint32_t S_b, uint32_t stride_b, uint32_t flip_w) {
+    int rc = tn_red_push(ctx, w_slabs, dW, n_w, S_w, stride_w, flip_w);
+    if (rc) return rc;
+    rc = tn_red_push(ctx, b_slabs, db, n_b, S_b, stride_b, 0);
+    if (rc) return rc;
+    return tn_red_commit(ctx);
+}
+
 // bytes of context scratch: the whole buffer outside a deferral window, a fresh 256-byte aligned
 // piece of it inside one (earlier pieces hold slabs that are still to be reduced)
 int tn_scratch_get(tn_ctx* ctx, size_t bytes, float** out) {
