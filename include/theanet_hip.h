@@ -724,6 +724,17 @@ int tn_deformer_transform(tn_ctx* ctx, const float* imgs, float* out, int N, int
 /* ---- minibatch gather (replaces x_data[indx]; neuralnet.py:228-234) ---- */
 int tn_gather_rows(tn_ctx* ctx, const void* src, const int32_t* d_index, void* dst,
                    int nrows, size_t row_bytes);
+/* The minibatch of a shuffled epoch in ONE launch on the ctx stream (new; the reference's TODO item 18: "a different
+ * permutation vector for each epoch"): the epoch's row order stays on the device and for r < nrows, with
+ * s = order[row0 + r]: row r of x_out = row s of x (x_row_bytes each), y_out[r] = y[s], row r of aux_out = row s of aux
+ * (aux_row_bytes each).  y / y_out and aux / aux_out may be NULL in pairs.  A bit copy (NaN payloads survive): 16 bytes
+ * per lane where a row size is a multiple of 16 and both bases are 16-byte aligned, dwords otherwise.  row0 is an
+ * int64 like every other row0 of this header, so a recorded step (tn_net_plan_add) advances it with the minibatch
+ * index.  Row sizes must be multiples of 4; order entries are NOT range-checked here (the caller checks an order
+ * once, when it uploads it).  nrows == 0: no launch.                                                              */
+int tn_gather_batch(tn_ctx* ctx, const int32_t* order, int64_t row0, int nrows, const void* x, void* x_out,
+                    size_t x_row_bytes, const int32_t* y, int32_t* y_out, const void* aux, void* aux_out,
+                    size_t aux_row_bytes);
 
 /* ---- data-parallel gradient exchange over RCCL/xGMI (new) ---- */
 #define TN_UNIQUE_ID_BYTES 128

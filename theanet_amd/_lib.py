@@ -199,6 +199,7 @@ SIGNATURES = {
     "tn_deformer_transform": (c_int, [CTX, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
                                       P, c_uint64, c_int64]),
     "tn_gather_rows": (c_int, [CTX, P, P, P, c_int, c_size_t]),
+    "tn_gather_batch": (c_int, [CTX, P, c_int64, c_int, P, P, c_size_t, P, P, P, P, c_size_t]),
     "tn_comm_unique_id": (c_int, [CTX, P]),
     "tn_comm_init": (c_int, [CTX, P, c_int, c_int]),
     "tn_comm_destroy": (c_int, [CTX]),

@@ -1231,6 +1231,26 @@ int tn_gather_rows(tn_ctx*, const void* src, const int32_t* idx, void* dst, int 
     return TN_OK;
 }
 
+int tn_gather_batch(tn_ctx* ctx, const int32_t* order, int64_t row0, int nrows, const void* x, void* x_out, size_t x_row_bytes,
+                    const int32_t* y, int32_t* y_out, const void* aux, void* aux_out, size_t aux_row_bytes) {
+    REQUIRE(order && x && x_out, "tn_gather_batch: order, x and x_out must not be NULL");
+    REQUIRE(nrows >= 0 && row0 >= 0, "tn_gather_batch: nrows %d, row0 %lld", nrows, (long long)row0);
+    REQUIRE(x_row_bytes % 4 == 0 && aux_row_bytes % 4 == 0,
+            "tn_gather_batch: row sizes (%zu, %zu bytes) must be multiples of 4", x_row_bytes, aux_row_bytes);
+    REQUIRE((y == nullptr) == (y_out == nullptr) && (aux == nullptr) == (aux_out == nullptr),
+            "tn_gather_batch: y / y_out and aux / aux_out are NULL in pairs");
+#pragma omp parallel for
+    for (int r = 0; r < nrows; ++r) {
+        const size_t s = (size_t)order[row0 + r];
+        std::memcpy(static_cast<char*>(x_out) + (size_t)r * x_row_bytes, static_cast<const char*>(x) + s * x_row_bytes, x_row_bytes);
+        if (y) y_out[r] = y[s];
+        if (aux)
+            std::memcpy(static_cast<char*>(aux_out) + (size_t)r * aux_row_bytes, static_cast<const char*>(aux) + s * aux_row_bytes,
+                        aux_row_bytes);
+    }
+    return TN_OK;
+}
+
 // ---- data-parallel exchange: ranks of a CPU job reduce HOST buffers in the Python layer
 // (theanet_amd/comm.py, socket rendezvous); one rank needs nothing ----
 int tn_comm_unique_id(tn_ctx*, void* id128) { std::memset(id128, 0, TN_UNIQUE_ID_BYTES); return TN_OK; }

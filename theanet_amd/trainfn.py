@@ -2,7 +2,8 @@
 (neuralnet.py:236-241, :270-277): ``fn(i) -> [cost, features, logprob]`` one step at a time (``_TrainFn``) or with two
 steps in flight (``_PipeTrainFn``), ``fn(i) -> [sym_err, P(MLE)]`` (``_TestFn``).  ``enqueue(i)`` issues a step without
 reading anything back; once the calls of a function have been seen to repeat, a step is ONE C call (plan.py,
-tn_net_step)."""
+tn_net_step).  ``set_order(order)`` makes the minibatches of an epoch slices of a device-resident row order (one
+tn_gather_batch launch per step) without giving any of that up."""
 import os
 
 import numpy as np
@@ -145,6 +146,75 @@ def _batch_in_range(i, n_rows, batch_sz):
         raise IndexError("minibatch %d of %d rows each in a dataset of %d rows" % (i, batch_sz, n_rows))
 
 
+class _RowOrder:
+    """The row order of a shuffled epoch (``set_order``), resident on the device, and the per-net buffers its
+    minibatches are staged in.  ONE per training function: the one-step-at-a-time fallback of a pipelined function
+    shares it.  ``buf`` (int32, one entry per dataset row) is allocated when the first order arrives and never moves:
+    recorded steps bake its address (and the stages') into their tn_gather_batch call, so a new order only changes
+    what the buffer holds.  A stage belongs to one net -- the twin of the pipelined schedule has its own: a stream's
+    previous step is two steps back and complete in stream order when the next gather overwrites the stage."""
+
+    def __init__(self, ctx, x_data, y_data, aux_data=None):
+        self.ctx, self.x_data, self.y_data, self.aux_data = ctx, x_data, y_data, aux_data
+        self.buf = None
+        self.len = None                 # entries of the current order (None: dataset order)
+        self.stages = {}                # id(net) -> (net, x_stage, y_stage, aux_stage)
+        self.row_bytes = int(np.prod(x_data.shape[1:])) * 4
+        self.aux_bytes = int(np.prod(aux_data.shape[1:])) * 4 if aux_data is not None else 0
+
+    def check(self, order, batch_sz):
+        """``order`` as a contiguous int32 vector, or the exception set_order documents."""
+        rows = self.x_data.shape[0]
+        order = np.asarray(order)
+        if order.ndim != 1 or order.dtype.kind not in "iu":
+            raise ValueError("an order is a 1-D integer array (got %s, %d-D)" % (order.dtype, order.ndim))
+        if not batch_sz <= order.shape[0] <= rows:
+            raise ValueError("an order holds between %d (one minibatch) and %d (the dataset) row numbers, not %d"
+                             % (batch_sz, rows, order.shape[0]))
+        if order.min() < 0 or order.max() >= rows:
+            raise IndexError("an order holds row numbers of a dataset of %d rows (got [%d, %d])"
+                             % (rows, order.min(), order.max()))
+        return np.ascontiguousarray(order, np.int32)
+
+    def upload(self, order):
+        """(the caller has synchronised: no step in flight reads the buffer)"""
+        if order is None:
+            self.len = None
+            return
+        if self.buf is None:
+            self.buf = self.ctx.empty((self.x_data.shape[0],), np.int32)
+        self.buf.view(0, (order.shape[0],)).set_value(order)
+        self.len = order.shape[0]
+
+    def in_range(self, i, batch_sz):
+        i = int(i)
+        if i < 0 or (i + 1) * batch_sz > self.len:
+            raise IndexError("minibatch %d of %d rows each in an order of %d rows" % (i, batch_sz, self.len))
+
+    def gather(self, net, row0):
+        """Stage rows order[row0, row0 + local_bsz) for ``net`` on the stream currently selected: (x, y, aux) stages."""
+        st = self.stages.get(id(net))
+        if st is None:
+            n = net.local_bsz
+            st = self.stages[id(net)] = (
+                net, self.ctx.empty((n,) + tuple(self.x_data.shape[1:])), self.ctx.empty((n,), np.int32),
+                self.ctx.empty((n,) + tuple(self.aux_data.shape[1:])) if self.aux_data is not None else None)
+        _, xs, ys, auxs = st
+        self.ctx.call("tn_gather_batch", self.buf.ptr, int(row0), net.local_bsz, self.x_data.ptr, xs.ptr, self.row_bytes,
+                      self.y_data.ptr, ys.ptr, self.aux_data.ptr if auxs is not None else None,
+                      auxs.ptr if auxs is not None else None, self.aux_bytes)
+        return xs, ys, auxs
+
+
+def _agree_on_order(net, order):
+    """Data-parallel ranks must train on the same order (each takes its shard of every minibatch of it)."""
+    if net.world.size > 1:
+        import zlib
+        from . import comm
+        crc = -1.0 if order is None else float(zlib.crc32(order.tobytes()))
+        comm.agree(crc, "the row order of set_order (CRC)")
+
+
 def _enqueue_planned(fn, i, keep=lambda: True):
     """``fn._enqueue(i)`` inside the step plan's bracket (plan.py): a recorded phase is replayed as one C call; otherwise the
     step is interpreted, and recorded when it is an ordinary one (plannable before it, no exception, ``keep()`` after it)."""
@@ -174,11 +244,12 @@ class _TrainFn:
     (neuralnet.py:236-241).  ``enqueue(i)`` issues the step without reading anything
     back (the GPU runs ahead of the host); ``fetch()`` copies the last step's outputs."""
 
-    def __init__(self, net, x_data, y_data, take_index_list, aux_data=None, ledger=None):
+    def __init__(self, net, x_data, y_data, take_index_list, aux_data=None, ledger=None, order=None):
         self.net, self.x_data, self.y_data = net, x_data, y_data
         self.aux_data = aux_data
         self.take_index_list = take_index_list
         ctx = net.ctx
+        self._ord = order or _RowOrder(ctx, x_data, y_data, aux_data)      # set_order(): a shuffled epoch
         if take_index_list:
             row = int(np.prod(x_data.shape[1:]))
             self.x_stage = ctx.empty((net.local_bsz,) + tuple(x_data.shape[1:]))
@@ -220,16 +291,46 @@ class _TrainFn:
             if idx.shape != (self.net.batch_sz,) or idx.min() < 0 or idx.max() >= self.x_data.shape[0]:
                 raise IndexError("an index list must hold %d row numbers of a dataset of %d rows"
                                  % (self.net.batch_sz, self.x_data.shape[0]))
+        elif self._ord.len is not None:
+            self._ord.in_range(i, self.net.batch_sz)
         else:
             _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
         _enqueue_planned(self, i)
+
+    def set_order(self, order):
+        """From now on ``fn(i)`` / ``enqueue(i)`` / ``step_cost(i)`` train on dataset rows ``order[i*B:(i+1)*B]`` (a
+        data-parallel rank: on its shard of that slice); ``None``: dataset order again.  ``order``: 1-D integers,
+        B <= len <= dataset rows, entries in [0, rows) -- not necessarily a permutation.  The order is an input, not
+        state: checkpoints and test functions do not know it.  Meant to be called once per epoch: it waits for the
+        steps in flight.  A recorded step plan, the cost ring and its numbering survive a new order; only switching
+        between no order and an order changes the calls a step makes, and the plan watches again."""
+        if self.take_index_list:
+            raise ValueError("set_order: this training function takes an index list per step")
+        net = self.net
+        if order is not None:
+            order = self._ord.check(order, net.batch_sz)
+        _agree_on_order(net, order)
+        if self._led.live:                        # costs still under way: taken now, handed out by the next call
+            self._led.owed = self._ring_rest(keep=True)
+        net.ctx.sync()
+        switched = (order is None) != (self._ord.len is None)
+        self._ord.upload(order)
+        if switched:
+            self._plan.restart("row order on" if order is not None else "row order off")
 
     def _enqueue(self, i):
         net, ctx = self.net, self.net.ctx
         B, lo = net.batch_sz, net.shard_lo
         slot = net.x
         slot.d_row0 = None
-        if self.take_index_list:
+        if self._ord.len is not None:
+            xs, y, auxs = self._ord.gather(net, int(i) * B + lo)
+            slot.bind(xs)
+            slot.row0, y_row0 = 0, 0
+            if auxs is not None:
+                net.aux_inpt_tr.bind(auxs)
+                net.aux_inpt_tr.row0 = 0
+        elif self.take_index_list:
             idx = np.ascontiguousarray(np.asarray(i, np.int32)[lo:lo + net.local_bsz])
             self.idx_dev.set_value(idx)
             ctx.call("tn_gather_rows", self.x_data.ptr, self.idx_dev.ptr, self.x_stage.ptr,
@@ -336,6 +437,7 @@ class _PipeTrainFn:
         self._ctypes = ctypes
         self._plan = StepPlan(net.ctx, net.batch_sz, net.shard_lo)
         self._led = _CostLedger(net.ctx)     # step_cost(): costs read four calls late
+        self._ord = _RowOrder(net.ctx, x_data, y_data)       # set_order(): a shuffled epoch
 
     # -- set-up of the twin on first use ---------------------------------------------------------
     def _build(self):
@@ -499,12 +601,32 @@ class _PipeTrainFn:
         first = net.tr_layers[0]
         if isinstance(first, ElasticLayer):
             first._pre_valid = False              # a field built ahead was for this stream's step t+2
-        self._seq = _TrainFn(net, self.x_data, self.y_data, False, ledger=self._led)
+        self._seq = _TrainFn(net, self.x_data, self.y_data, False, ledger=self._led, order=self._ord)
 
     # -- the step ---------------------------------------------------------------------------------
     def enqueue(self, i):
-        _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
+        if self._ord.len is not None:
+            self._ord.in_range(i, self.net.batch_sz)
+        else:
+            _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
         _enqueue_planned(self, i, keep=lambda: self._seq is None)     # (a step that fell back is not one to record)
+
+    def set_order(self, order):
+        """``_TrainFn.set_order`` with two steps in flight: the schedule stays pipelined (both streams are drained, the
+        next step carries on from the weights they left), a ready plan stays ready."""
+        if self._seq is not None:
+            return self._seq.set_order(order)
+        net = self.net
+        if order is not None:
+            order = self._ord.check(order, net.batch_sz)
+        _agree_on_order(net, order)
+        if self._led.live:                        # costs still under way: taken now, handed out by the next call
+            self._led.owed = self._leave_ring(keep=True)
+        net.ctx.sync()
+        switched = (order is None) != (self._ord.len is None)
+        self._ord.upload(order)
+        if switched:
+            self._plan.restart("row order on" if order is not None else "row order off")
 
     def _enqueue(self, i):
         if self._seq is None and self._blocked():
@@ -535,12 +657,18 @@ class _PipeTrainFn:
         self._lr_prev = self._lr_now()
         slot = X.x
         slot.d_row0 = None
-        slot.bind(self.x_data)
-        slot.row0 = int(i) * net.batch_sz + net.shard_lo
+        row0 = int(i) * net.batch_sz + net.shard_lo
+        if self._ord.len is not None:             # on this step's own stream, into this net's own stage
+            xs, y, _ = self._ord.gather(X, row0)
+            slot.bind(xs)
+            slot.row0 = 0
+        else:
+            slot.bind(self.x_data)
+            slot.row0, y = row0, self.y_data
         slot.row_global0 = net.shard_lo
         X._want_outputs = self._want
         try:
-            X._train_step(self.y_data, slot.row0, pipe_stride=2)
+            X._train_step(y, slot.row0, pipe_stride=2)
         finally:
             X._want_outputs = False
             ctx.call("tn_stream_select", 0)

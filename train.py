@@ -205,6 +205,14 @@ def run(dataset_name, prms_file_name, redirect):
 
         for epoch in range(tr_prms['NUM_EPOCHS']):
             total_cost, t0 = 0, time.perf_counter()
+            perm = None
+            if tr_prms.get('SHUFFLE'):
+                # a new row order every epoch (the reference's TODO item 18), resident on the device (set_order).  The
+                # generator is keyed by the epoch number: a resumed run continues the sequence, every rank draws the
+                # same order, and net.rand_gen is never touched
+                perm = np.random.RandomState([tr_prms.get('SHUFFLE_SEED', tr_prms['SEED']), net.get_epoch()]) \
+                    .permutation(len(tr_x))[:n_tr_batches * batch_sz]
+                training_fn.set_order(perm)
             if not exp_head:
                 # The reference's loop (train.py:211-226) needs ONE number of a step: its cost, for the epoch's total and
                 # the NaN guard.  step_cost(i) enqueues the step and hands back the costs that have ARRIVED (a step's cost
@@ -223,7 +231,8 @@ def run(dataset_name, prms_file_name, redirect):
                 cost, features, _ = training_fn(ibatch)
                 total_cost += cost
                 # ExpLoss nets: report samples whose true-class feature runs away (train.py:216-222)
-                labels = np.asarray(data.training_y[ibatch * batch_sz:(ibatch + 1) * batch_sz])
+                rows = slice(ibatch * batch_sz, (ibatch + 1) * batch_sz)
+                labels = np.asarray(data.training_y)[perm[rows]] if perm is not None else np.asarray(data.training_y[rows])
                 lo = net.shard_lo                         # a data-parallel rank holds its own rows of the batch
                 own = labels[lo:lo + len(features)]
                 true_features = features[np.arange(len(own)), own]
