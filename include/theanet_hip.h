@@ -526,7 +526,12 @@ int tn_head_rows(tn_ctx* ctx, int head, int loss, float loss_param, const float*
 int tn_reduce_sum(tn_ctx* ctx, const float* v, size_t n, float scale, float* out, int accumulate);
 /* out[0] (+)= L1*sum|p| + L2*sum p^2  (layer.py:109-117)                                 */
 int tn_wtcost(tn_ctx* ctx, const float* p, size_t n, float L1, float L2, float* out, int accumulate);
-/* out[0] = mean(pred != y) ; out[1] = mean(rowp)   (outlayers.py:69-80)                  */
+/* out2[0] = mean(pred != y) ; out2[1] = mean(rowp)   (outlayers.py:69-80)
+ * out2 is ANY two floats of device memory, written with plain stores by one block: an evaluation of several
+ * minibatches (the reference calls its compiled test function once per minibatch, train.py:185-190,238-241, and reads two
+ * floats back each time) passes row k of a (len, 2) float array, d_stats + 2*k, for minibatch k and reads the array
+ * back once (_TestFn.sweep, theanet_amd/trainfn.py).  Same kernel, same summation order: a row holds the bits a call
+ * with its own out2 gets.  There is no separate entry point taking a row number.                                */
 int tn_error_stats(tn_ctx* ctx, const int32_t* pred, const int32_t* y, int64_t y_row0,
                    const float* rowp, int B, float* out2);
 

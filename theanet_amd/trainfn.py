@@ -1,7 +1,7 @@
 """What ``get_trin_model`` / ``get_test_model`` return -- the counterparts of the reference's compiled Theano functions
 (neuralnet.py:236-241, :270-277): ``fn(i) -> [cost, features, logprob]`` one step at a time (``_TrainFn``) or with two
-steps in flight (``_PipeTrainFn``), ``fn(i) -> [sym_err, P(MLE)]`` (``_TestFn``).  ``enqueue(i)`` issues a step without
-reading anything back; once the calls of a function have been seen to repeat, a step is ONE C call (plan.py,
+steps in flight (``_PipeTrainFn``), ``fn(i) -> [sym_err, P(MLE)]`` (``_TestFn``; ``sweep(indices)``: a run of minibatches,
+read back once).  ``enqueue(i)`` issues a step without reading anything back; once the calls of a function have been seen to repeat, a step is ONE C call (plan.py,
 tn_net_step).  ``set_order(order)`` makes the minibatches of an epoch slices of a device-resident row order (one
 tn_gather_batch launch per step) without giving any of that up."""
 import os
@@ -749,18 +749,24 @@ class _PipeTrainFn:
 
 
 class _TestFn:
-    """``get_test_model``'s function: ``fn(i) -> [sym_err, P(MLE)](, features, y_preds)``."""
+    """``get_test_model``'s function: ``fn(i) -> [sym_err, P(MLE)](, features, y_preds)``; ``sweep(indices)`` evaluates a
+    run of minibatches with one weight sync, one collective and one copy back."""
 
     def __init__(self, net, x_data, y_data, preds_feats, aux_data=None):
         self.net, self.x_data, self.y_data, self.preds_feats = net, x_data, y_data, preds_feats
         self.aux_data = aux_data
+        self._sweep_stats = None        # (len, 2) device rows of sweep(), grown when a longer sweep arrives
 
-    def __call__(self, i):
-        net, ctx = self.net, self.net.ctx
-        _batch_in_range(i, self.x_data.shape[0], net.batch_sz)
+    def _prepare(self):
+        """What a call does once, however many minibatches follow."""
+        net = self.net
         net._sync_weights()
         net._apply_dtype()
         net._c8_tiles.arrange(net.te_layers)
+
+    def _enqueue(self, i, d_stats):
+        """The test graph on minibatch i and its two statistics into ``d_stats`` (2 floats); nothing is read back."""
+        net, ctx = self.net, self.net.ctx
         slot = net.test_x
         slot.bind(self.x_data)
         slot.row0 = int(i) * net.batch_sz + net.shard_lo
@@ -777,7 +783,14 @@ class _TestFn:
         finally:
             ctx.fc_head(False)
         ctx.call("tn_error_stats", out.y_preds.ptr, self.y_data.ptr, slot.row0, out.rowp.ptr,
-                 net.local_bsz, out.d_stats.ptr)
+                 net.local_bsz, d_stats.ptr)
+
+    def __call__(self, i):
+        net = self.net
+        _batch_in_range(i, self.x_data.shape[0], net.batch_sz)
+        self._prepare()
+        out = net.te_layers[-1]
+        self._enqueue(i, out.d_stats)
         if net.world.size > 1:
             net._group().allreduce_sum(out.d_stats)
         stats = out.d_stats.get_value() / net.world.size
@@ -788,4 +801,31 @@ class _TestFn:
             res += [out.features.get_value(), out.y_preds.get_value().astype(np.int64)]
         return res
 
-
+    def sweep(self, indices):
+        """``[fn(i) for i in indices]`` -- one ``[sym_err, P(MLE)]`` pair of Python floats per index, bit for bit what
+        ``fn(i)`` returns at the same weights -- without a host synchronisation between the minibatches: the weights are
+        brought up to date once, minibatch k leaves its statistics in row k of a device array (tn_error_stats at
+        ``rows + 2 k``), data-parallel ranks sum all rows in ONE collective (element-wise: each row's sum is the one the
+        per-call path forms) and one copy brings them back.  ``indices``: any finite iterable, repeats allowed; all of
+        them are checked before anything is enqueued."""
+        assert not self.preds_feats, "sweep() returns the two error statistics only: this function was built with " \
+            "preds_feats=True (features and predictions come from fn(i), one minibatch at a time)"
+        net = self.net
+        indices = [int(i) for i in indices]
+        for i in indices:
+            _batch_in_range(i, self.x_data.shape[0], net.batch_sz)
+        n = len(indices)
+        if n == 0:
+            return []
+        if self._sweep_stats is None or self._sweep_stats.shape[0] < n:
+            self._sweep_stats = net.ctx.empty((n, 2))
+        rows = self._sweep_stats.view(0, (n, 2))
+        self._prepare()
+        for k, i in enumerate(indices):
+            self._enqueue(i, rows.view(2 * k, (2,)))
+        if net.world.size > 1:
+            net._group().allreduce_sum(rows)
+        stats = rows.get_value() / net.world.size
+        if net.world.size > 1:
+            net._group().verify_order()
+        return [[float(e), float(p)] for e, p in stats]

@@ -106,7 +106,7 @@ class BatchWindows:
 
 def error_rates(test_fn, batches):
     """Mean symbol error and mean second statistic (P(MLE) / bit error) over ``batches``, in percent."""
-    stats = np.array([test_fn(i)[:2] for i in batches], dtype=np.float64)
+    stats = np.array(test_fn.sweep(batches), dtype=np.float64)
     return 100 * stats[:, 0].mean(), 100 * stats[:, 1].mean()
 
 
