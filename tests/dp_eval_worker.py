@@ -38,4 +38,7 @@ def main(out_stem, B, steps):
 
 
 if __name__ == "__main__":
+    from tests import guard_util
+    guard_util.install()            # guard bands and 0xFF poison around every device buffer of this rank
     main(sys.argv[1], int(sys.argv[2]), int(sys.argv[3]))
+    guard_util.check_all()

@@ -39,4 +39,7 @@ def main(out_path, prms_name, img, ch, B, steps):
 
 
 if __name__ == "__main__":
+    from tests import guard_util
+    guard_util.install()            # guard bands and 0xFF poison around every device buffer of this rank
     main(sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6]))
+    guard_util.check_all()

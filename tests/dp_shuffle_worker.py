@@ -38,4 +38,7 @@ def main(out_path, B, steps, order_seed, disagree):
 
 
 if __name__ == "__main__":
+    from tests import guard_util
+    guard_util.install()            # guard bands and 0xFF poison around every device buffer of this rank
     main(sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]))
+    guard_util.check_all()

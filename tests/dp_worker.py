@@ -74,4 +74,7 @@ def main(out_path):
 
 
 if __name__ == "__main__":
+    from tests import guard_util
+    guard_util.install()            # guard bands and 0xFF poison around every device buffer of this rank
     main(sys.argv[1])
+    guard_util.check_all()

@@ -47,12 +47,21 @@ def act_code(name):
 
 
 def assert_close(got, want, rtol=1e-4, atol=1e-5, what=""):
+    """|got - want| <= atol + rtol * |want| element by element.  A NaN compares false with every bound, so the test is
+    "not within", never "beyond": a NaN or an infinity in ``got`` where ``want`` has a finite number is a mismatch
+    and where ``want`` is not finite only the same value matches (equal infinities do; a NaN never does)."""
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = np.abs(got.astype(np.float64) - want.astype(np.float64))
-    tol = atol + rtol * np.abs(want.astype(np.float64))
-    bad = err > tol
+    g, w = got.astype(np.float64), want.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(g - w)
+        tol = atol + rtol * np.abs(w)
+        bad = ~((np.isfinite(w) & (err <= tol)) | (g == w))
+        over = np.where(bad, np.where(np.isnan(err - tol), np.inf, err - tol), -np.inf)
     if bad.any():
-        i = np.unravel_index(np.argmax(err - tol), err.shape)
-        raise AssertionError("%s: %d/%d mismatches, worst at %s: got %r want %r" %
-                             (what, bad.sum(), bad.size, i, got[i], want[i]))
+        i = tuple(int(k) for k in np.unravel_index(np.argmax(over), err.shape))
+        nans = int((np.isnan(g) & bad).sum())
+        raise AssertionError("%s: %d/%d mismatches%s, worst at %s: got %r want %r" %
+                             (what, bad.sum(), bad.size,
+                              ", %d of them NaN (an element never written?)" % nans if nans else "",
+                              i, got[i], want[i]))

@@ -16,6 +16,7 @@ import pytest
 
 from tests import c8_util as U
 from tests.gpu_util import ctx, dev, empty, call
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

@@ -22,6 +22,7 @@ from tests.gpu_util import ctx, dev, empty, call
 from tests.test_gpu_c8 import (ACTS, C8_ACT_NAMES, C8_CASES, C8_FWD_CASES, C8_GENERIC_ACTS, LEAKY, SLOPE,
                                WGRAD_RING_CASES, _act, _act_grad_from_out, _assert_masks_equal_up_to_provable_near_ties,
                                _rel, _rowmap, _wgrad_blas)
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

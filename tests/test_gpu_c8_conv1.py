@@ -22,6 +22,7 @@ from tests.gpu_util import ROOT, act_code, assert_close, call, ctx, dev, empty, 
 from tests.test_gpu_c8_dropout import _oracle_16
 from tests.test_gpu_c8_mean import GS, R16, TOL
 from tests.test_gpu_f16 import _inject_draws
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

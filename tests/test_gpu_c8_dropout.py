@@ -26,6 +26,7 @@ from tests import c8b_util as CB
 from tests.gpu_util import assert_close, call, ctx, dev, load_prms
 from tests.test_gpu_c8_mean import GS, R16, TOL, _bits
 from tests.test_gpu_f16 import _inject_draws
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

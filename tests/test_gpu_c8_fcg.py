@@ -24,6 +24,7 @@ from tests.test_gpu_c8_conv1 import TOL16, _act, _act_grad_from_out, _code, _R, 
 from tests.test_gpu_c8_dropout import _oracle_16
 from tests.test_gpu_c8_mean import GS, R16, TOL
 from tests.test_gpu_f16 import _inject_draws
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

@@ -20,6 +20,7 @@ from tests import c8_util as U
 from tests import c8b_util as CB
 from tests.gpu_util import act_code, assert_close, call, ctx, dev, empty, load_prms
 from tests.test_gpu_f16 import _inject_draws
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

@@ -19,6 +19,7 @@ from tests.test_gpu_c8 import (ACTS, C8_CASES, LEAKY, SLOPE, WGRAD_RING_CASES, _
                                _assert_masks_equal_up_to_provable_near_ties, _rel, _wgrad_blas)
 from tests.test_gpu_f16 import _inject_draws
 from theanet_amd.device import DeviceArray
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

@@ -19,6 +19,7 @@ from oracle import theanet_oracle as O
 from tests import c8b_util as CB
 from tests.gpu_util import act_code, call, ctx, dev, empty
 from tests.test_gpu_fc_bf16 import _tol
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

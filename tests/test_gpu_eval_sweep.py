@@ -7,6 +7,8 @@ import copy
 import numpy as np
 import pytest
 
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
+
 pytestmark = pytest.mark.gpu
 
 NB = 6                          # minibatches in every corpus

@@ -17,6 +17,7 @@ import pytest
 
 from oracle import theanet_oracle as O
 from tests.gpu_util import assert_close, ctx, load_prms
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

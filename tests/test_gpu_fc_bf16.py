@@ -16,6 +16,7 @@ import pytest
 
 from tests import c8b_util as CB
 from tests.gpu_util import act_code, call, ctx, dev, empty
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

@@ -8,6 +8,7 @@ import pytest
 
 from oracle import theanet_oracle as O
 from tests.gpu_util import act_code, assert_close, call, ctx, dev, empty
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

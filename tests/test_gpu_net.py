@@ -11,6 +11,7 @@ import pytest
 from oracle import theanet_oracle as O
 from tests.gpu_util import assert_close, load_prms
 from tests.golden.make_golden import sub_index
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.gpu_util import load_prms
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 

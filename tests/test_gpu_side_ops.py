@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 
 from oracle import theanet_oracle as O
-from tests.gpu_util import act_code, call, ctx, dev, empty
-from tests.gpu_util import assert_close as _assert_close
+from tests.gpu_util import act_code, assert_close, call, ctx, dev, empty
+from tests.guard_util import device_guard  # noqa: F401  (autouse: guard bands and 0xFF poison on every device buffer)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +37,6 @@ def filled(shape, dtype=np.float32):
     a = empty(shape, dtype)
     a.fill_bytes(0xff)
     return a
-
-
-def assert_close(got, want, rtol=1e-4, atol=1e-5, what=""):
-    """gpu_util.assert_close, and no NaN: an element of the 0xff fill that the kernel never wrote (a NaN compares
-    false with every bound)."""
-    assert not np.isnan(np.asarray(got)).any(), what + ": NaN (an element never written?)"
-    _assert_close(got, want, rtol, atol, what)
 
 
 def untouched(a):
