@@ -81,6 +81,27 @@ struct Window {
                     for (int q = 0; q < S; ++q) v[c][r][q] = (rok[r] && cok[q]) ? v[c][r][q] : 0.f;
         }
     }
+    // The same values through S / 2 eight-byte loads per row.  The caller guarantees: no padding, x0 >= 0 and even,
+    // x0 + S <= Wd (no column is ever clamped), Wd even and x 8-byte aligned -- then base, c * H * Wd, every row
+    // offset and x0 are all even, so every pair is aligned.  Rows are clamped exactly as in load().
+    __device__ __forceinline__ void load_pairs(const float* __restrict__ x, unsigned base, int H, int Wd, int y0, int x0) {
+        static_assert(S % 2 == 0 && !PADDED, "load_pairs: even, unpadded windows only");
+        unsigned roff[S];
+#pragma unroll
+        for (int r = 0; r < S; ++r) roff[r] = (unsigned)(min(max(y0 + r, 0), H - 1) * Wd);
+        const unsigned HW = (unsigned)(H * Wd);
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+#pragma unroll
+            for (int r = 0; r < S; ++r)
+#pragma unroll
+                for (int q = 0; q < S; q += 2) {
+                    const float2 w = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(x) +
+                                                                      (base + c * HW + roff[r] + (unsigned)(x0 + q)) * 4u);
+                    v[c][r][q] = w.x;
+                    v[c][r][q + 1] = w.y;
+                }
+    }
 };
 
 // conv outputs of the P x P window for map k (fixed FMA order: c, u, v -- shared by fwd and bwd)
@@ -290,7 +311,17 @@ __global__ __launch_bounds__(256) void convpool_bwd_kernel(
 // window: its 4 x 4 x C input patch is loaded once (16 C loads for 4 conv outputs), dz of the 4
 // window elements is mask bit ? g * act'(y) : 0 -- no conv recompute, no cross-lane max -- and
 // the wgrad FMAs run on the patch registers.  Same partial-slab contract as convpool_bwd_kernel.
-template <int C, int KT, int ACT, bool PADDED>
+//
+// A thread's rounds of the grid-stride walk come in groups of MW, fully unrolled: first the clamped
+// indices and EVERY load of all MW windows (patch, g, mask, y), then the selects and FMAs round by
+// round.  A wave issues in order, so with one round at a time round i + 1's loads waited behind round
+// i's FMAs, which waited for round i's loads: one full memory latency per round, in series, at under
+// three waves per SIMD.  The window -> thread assignment and the order of every accumulator's FMAs
+// (round, kk, c, u, v, window element) are those of the one-round loop, so the sums are bit-identical.
+// PAIRS: patch rows as 8-byte loads (Window::load_pairs; the launcher checks its conditions).
+// DZ: dz_out is written.  A template flag because the store path (window indices again, four guarded stores per
+// filter) costs ~35 registers when it is only branched around: with it the MW = 4 group misses three waves per SIMD.
+template <int C, int KT, int ACT, bool PADDED, int MW, bool PAIRS, bool DZ>
 __global__ __launch_bounds__(256) void convpool_bwd_mask_kernel(
     const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ y,
     const uint8_t* __restrict__ mask, float* __restrict__ dz_out, float* __restrict__ partial,
@@ -315,39 +346,67 @@ __global__ __launch_bounds__(256) void convpool_bwd_mask_kernel(
 #pragma unroll
             for (int s = 0; s < FF; ++s) acc[kk][c][s] = 0.f;
     }
-    const unsigned stride = gridDim.x * 256u;
-    for (unsigned base = blockIdx.x * 256u; base < total; base += stride) {
-        const unsigned t = base + threadIdx.x;
-        const bool live = t < total;
-        const unsigned tt = live ? t : total - 1;
-        const int n = (int)(tt / (unsigned)HpWp);
-        const int q = (int)(tt - (unsigned)n * HpWp);
-        const int pi = q / Wp, pj = q - pi * Wp;
-        Window<4, C, PADDED> pt;
-        pt.load(x, (unsigned)n * C * H * Wd, H, Wd, 2 * pi - pad, 2 * pj - pad);
-        float gy[KT];
-        unsigned mk[KT];
+    const unsigned stride = gridDim.x * 256u;      // total < 2^31 and MW * stride <= 2^21: no wrap-around below
+    // G rounds from base0 on, each of them inside the tensor (base0 + (G - 1) * stride < total)
+    auto group = [&](auto G_, const unsigned base0) {
+        constexpr int G = decltype(G_)::value;
+        Window<4, C, PADDED> pt[G];
+        float gy[G][KT], yv[G][KT];
+        unsigned mk[G][KT];
+        // phase 1: every load of the group in flight before the first use
 #pragma unroll
-        for (int kk = 0; kk < KT; ++kk) {
-            const size_t e = ((size_t)n * K + min(k0 + kk, K - 1)) * HpWp + q;
-            gy[kk] = g[e];
-            mk[kk] = mask[e];
-            if (ACT != TN_ACT_LEAKY) gy[kk] *= tn_act_grad_from_out(y[e], act, prm);
+        for (int w = 0; w < G; ++w) {
+            if (w) __builtin_amdgcn_sched_barrier(0);      // one window's index math and loads at a time
+            const unsigned t = base0 + w * stride + threadIdx.x;
+            const unsigned tt = t < total ? t : total - 1;
+            const int n = (int)(tt / (unsigned)HpWp);
+            const int q = (int)(tt - (unsigned)n * HpWp);
+            const int pi = q / Wp, pj = q - pi * Wp;
+            if constexpr (PAIRS) pt[w].load_pairs(x, (unsigned)n * C * H * Wd, H, Wd, 2 * pi, 2 * pj);
+            else pt[w].load(x, (unsigned)n * C * H * Wd, H, Wd, 2 * pi - pad, 2 * pj - pad);
+            // g / mask / y: wave-uniform 64-bit base (the wave's first image, filter k) + a 32-bit offset per lane (a
+            // wave spans at most 64 images; the launcher checks K * Hp * Wp < 2^23), as for the patch: with a 64-bit
+            // address per load the address registers of a whole group no longer fit beside its operands
+            const int nb = __builtin_amdgcn_readfirstlane(n);
+            const unsigned eo = (unsigned)(n - nb) * (unsigned)(K * HpWp) + (unsigned)q;
+#pragma unroll
+            for (int kk = 0; kk < KT; ++kk) {
+                const size_t eb = ((size_t)nb * K + min(k0 + kk, K - 1)) * HpWp;
+                gy[w][kk] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(g + eb) + eo * 4u);
+                mk[w][kk] = *(mask + eb + eo);
+                if (ACT != TN_ACT_LEAKY)
+                    yv[w][kk] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(y + eb) + eo * 4u);
+            }
         }
+        // phase 2: selects and FMAs, round by round.  The fences keep hipcc's scheduler from pulling a round's mask tests
+        // up between the loads (they wait for that round's bytes) and from forming several rounds' dz ahead of their FMAs.
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int kk = 0; kk < KT; ++kk) {
-            const int k = k0 + kk;
-            if (k < K) {   // wave-uniform
+        for (int w = 0; w < G; ++w) {
+            if (w) __builtin_amdgcn_sched_barrier(0);
+            const unsigned t = base0 + w * stride + threadIdx.x;
+            const bool live = t < total;
+#pragma unroll
+            for (int kk = 0; kk < KT; ++kk)
+                if (ACT != TN_ACT_LEAKY) gy[w][kk] *= tn_act_grad_from_out(yv[w][kk], act, prm);
+#pragma unroll
+            for (int kk = 0; kk < KT; ++kk) {
+                // No branch on k < K here: behind one, hipcc sinks that filter's g / mask loads out of phase 1.  A filter
+                // past K (only when KT does not divide K) repeats filter K - 1 into accumulators that are never written.
+                const int k = k0 + kk;
                 if (ACT == TN_ACT_LEAKY) {
-                    float gp = (mk[kk] & 32u) ? prm : tie;
-                    gp = (mk[kk] & 16u) ? 1.f : gp;
-                    gy[kk] *= gp;
+                    float gp = (mk[w][kk] & 32u) ? prm : tie;
+                    gp = (mk[w][kk] & 16u) ? 1.f : gp;
+                    gy[w][kk] *= gp;
                 }
-                const float gl = live ? gy[kk] : 0.f;
+                const float gl = live ? gy[w][kk] : 0.f;
                 float d[2][2];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) d[r >> 1][r & 1] = (mk[kk] >> r & 1u) ? gl : 0.f;
-                if (dz_out && live) {
+                for (int r = 0; r < 4; ++r) d[r >> 1][r & 1] = (mk[w][kk] >> r & 1u) ? gl : 0.f;
+                if (DZ && live && k < K) {      // (the window's indices again: kept from phase 1 they cost 3 G registers)
+                    const int n = (int)(t / (unsigned)HpWp);
+                    const int q = (int)(t - (unsigned)n * HpWp);
+                    const int pi = q / Wp, pj = q - pi * Wp;
                     float* o = dz_out + ((size_t)n * K + k) * HoWo + (2 * pi) * Wo + 2 * pj;
                     const bool vj = 2 * pj + 1 < Wo, vi = 2 * pi + 1 < Ho;
                     o[0] = d[0][0];
@@ -363,15 +422,19 @@ __global__ __launch_bounds__(256) void convpool_bwd_mask_kernel(
 #pragma unroll
                         for (int v = 0; v < F; ++v) {
                             float a = acc[kk][c][u * F + v];
-                            a = fmaf(d[0][0], pt.v[c][u][v], a);
-                            a = fmaf(d[0][1], pt.v[c][u][v + 1], a);
-                            a = fmaf(d[1][0], pt.v[c][u + 1][v], a);
-                            a = fmaf(d[1][1], pt.v[c][u + 1][v + 1], a);
+                            a = fmaf(d[0][0], pt[w].v[c][u][v], a);
+                            a = fmaf(d[0][1], pt[w].v[c][u][v + 1], a);
+                            a = fmaf(d[1][0], pt[w].v[c][u + 1][v], a);
+                            a = fmaf(d[1][1], pt[w].v[c][u + 1][v + 1], a);
                             acc[kk][c][u * F + v] = a;
                         }
             }
         }
-    }
+    };
+    unsigned base0 = blockIdx.x * 256u;
+    if constexpr (MW > 1)
+        for (; base0 + (MW - 1) * stride < total; base0 += MW * stride) group(std::integral_constant<int, MW>{}, base0);
+    for (; base0 < total; base0 += stride) group(std::integral_constant<int, 1>{}, base0);      // the rounds left over
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int KCFF = K * C * FF;
     if constexpr (NACC <= 48) {
@@ -491,6 +554,14 @@ static int launch_bwd(tn_ctx* ctx, const float* x, const float* W, const float* 
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, K, C, F);
 }
 
+// Largest group (rounds unrolled together, all loads first) at which convpool_bwd_mask_kernel still holds three waves
+// per SIMD (<= 168 VGPRs, no scratch) -- from the compiler's resource report; see the table in docs/EXPERIMENTS.md.
+constexpr int mask_mw_cap(int C, bool leaky, bool padded, bool pairs, bool dz) {
+    if (C > 1) return 1;                                   // C = 2 at MW = 2: 177 .. 218 VGPRs; C = 3, 4: 245 and up
+    if (!dz && !padded && (leaky || pairs)) return 4;      // 160 .. 166 VGPRs; the other C = 1 forms: 173 .. 223
+    return 2;                                              // 112 .. 139 VGPRs
+}
+
 static int tn_tune_mwin() { return 4; }        // windows per thread of the mask-driven backward (full batches)
 
 template <int C, int KT>
@@ -500,6 +571,7 @@ static int launch_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const fl
     const long long total = (long long)N * Hp * Wp;
     TN_REQUIRE(total < (1ll << 31), "tn_convpool_bwd_mask: too many outputs for 32-bit indexing");
     TN_REQUIRE((long long)N * C * H * Wd < (1ll << 30), "tn_convpool_bwd_mask: input too large for 32-bit byte offsets");
+    TN_REQUIRE((long long)K * Hp * Wp < (1ll << 23), "tn_convpool_bwd_mask: image too large for 32-bit byte offsets inside a wave");
     int mwin = tn_tune_mwin();                          // windows per thread ...
     while (mwin > 1 && cdiv(total, 256 * mwin) < 2 * ctx->num_cus) mwin >>= 1;   // ... fewer for short batches (a 512-image shard: 85 blocks otherwise)
     int nblk = cdiv(total, 256 * mwin);
@@ -511,15 +583,33 @@ static int launch_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const fl
     if (rc) return rc;
     float* dbpartial = partial + (size_t)nblk * KCFF;
     const dim3 grid(nblk, cdiv(K, KT));
-#define CP_L(ACT_, PAD_)                                                                          \
-    convpool_bwd_mask_kernel<C, KT, ACT_, PAD_><<<grid, 256, 0, ctx->stream>>>(                     \
+    // patch rows as 8-byte loads: unpadded, even pitch, aligned tensor, and no window column ever clamped
+    const bool pairs = pad == 0 && Wd % 2 == 0 && 2 * Wp + 2 <= Wd && (reinterpret_cast<uintptr_t>(x) & 7) == 0;
+    // rounds per unrolled group: the windows per thread, capped per instantiation (MASK_MW_CAP) -- the launch below tries
+    // MW = 4, 2, 1 in turn; groups of fewer rounds than windows per thread simply repeat
+#define CP_K(ACT_, PAD_, PR_, DZ_)                                                                \
+    do {                                                                                          \
+        constexpr int cap = mask_mw_cap(C, ACT_ == TN_ACT_LEAKY, PAD_, PR_, DZ_);                 \
+        if constexpr (cap >= 4) if (mwin >= 4) { CP_G(ACT_, PAD_, 4, PR_, DZ_); break; }          \
+        if constexpr (cap >= 2) if (mwin >= 2) { CP_G(ACT_, PAD_, 2, PR_, DZ_); break; }          \
+        CP_G(ACT_, PAD_, 1, PR_, DZ_);                                                            \
+    } while (0)
+#define CP_G(ACT_, PAD_, MW_, PR_, DZ_)                                                           \
+    convpool_bwd_mask_kernel<C, KT, ACT_, PAD_, MW_, PR_, DZ_><<<grid, 256, 0, ctx->stream>>>(      \
         x, g, y, mask, dz, partial, dbpartial, N, H, Wd, K, pad, Ho, Wo, Hp, Wp, act, prm)
-    if (act == TN_ACT_LEAKY) {
-        if (pad) CP_L(TN_ACT_LEAKY, true); else CP_L(TN_ACT_LEAKY, false);
-    } else {
-        if (pad) CP_L(-1, true); else CP_L(-1, false);
-    }
+#define CP_D(ACT_, PAD_, PR_)                                                                     \
+    do { if (dz) CP_K(ACT_, PAD_, PR_, true); else CP_K(ACT_, PAD_, PR_, false); } while (0)
+#define CP_L(ACT_)                                                                                \
+    do {                                                                                          \
+        if (pad) CP_D(ACT_, true, false);                                                         \
+        else if (pairs) CP_D(ACT_, false, true);                                                  \
+        else CP_D(ACT_, false, false);                                                            \
+    } while (0)
+    if (act == TN_ACT_LEAKY) CP_L(TN_ACT_LEAKY); else CP_L(-1);
 #undef CP_L
+#undef CP_D
+#undef CP_G
+#undef CP_K
     TN_LAUNCH_CHECK();
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, K, C, 3);
 }
