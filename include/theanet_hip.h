@@ -526,6 +526,26 @@ int tn_head_rows(tn_ctx* ctx, int head, int loss, float loss_param, const float*
 int tn_reduce_sum(tn_ctx* ctx, const float* v, size_t n, float scale, float* out, int accumulate);
 /* out[0] (+)= L1*sum|p| + L2*sum p^2  (layer.py:109-117)                                 */
 int tn_wtcost(tn_ctx* ctx, const float* p, size_t n, float L1, float L2, float* out, int accumulate);
+/* The cost of a step of a net with weight costs as ONE launch (layer.py:109-117 summed over the layers,
+ * neuralnet.py:208-210, plus the minibatch cost of outlayers.py:50-51):
+ *   *d_cost = cost_scale * sum(rowloss[0:nrow]) + sum over rows of (L1 * sum|p| + L2 * sum p^2)
+ * h_tab: HOST array of ntab rows, one per parameter tensor of every layer with a non-zero L1 or L2 (frozen layers
+ * included); rows with n == 0 or L1 == L2 == 0 add nothing.  Up to 32 rows travel by value with one launch; a longer
+ * table takes one launch per 32 rows.  Every (row, TN_WTCOST_CHUNK-element chunk) pair is summed by one block in a
+ * fixed order (strided per-thread sums, wave shuffles, the four wave sums), its partial goes to a scratch array of the
+ * context's current stream, and the block that finishes last adds the partials in index order, the row losses in the
+ * order of tn_sgd_update_net's cost rider, and stores the result: no floating-point atomics, the result depends on
+ * the inputs only.  rowloss == NULL: no minibatch cost term.  accumulate != 0: the sum is added to *d_cost (the
+ * data-parallel step: the row losses have travelled through the all-reduce).  With ntab == 0 and accumulate == 0 the
+ * result has the bits of the rider.                                                                              */
+typedef struct tn_wc_seg {
+    const float* p;
+    uint64_t n;
+    float L1, L2;
+} tn_wc_seg;
+#define TN_WTCOST_CHUNK 16384
+int tn_wtcost_net(tn_ctx* ctx, const tn_wc_seg* h_tab, int ntab, const float* rowloss, int nrow, float cost_scale,
+                  float* d_cost, int accumulate);
 /* out2[0] = mean(pred != y) ; out2[1] = mean(rowp)   (outlayers.py:69-80)
  * out2 is ANY two floats of device memory, written with plain stores by one block: an evaluation of several
  * minibatches (the reference calls its compiled test function once per minibatch, train.py:185-190,238-241, and reads two
@@ -581,16 +601,23 @@ int tn_maxnorm_multi(tn_ctx* ctx, const tn_mn_seg* h_segs, int nseg);
  *                   t+1 do not depend on the gradient of step t and its all-reduce may overlap the whole next step.
  *                   seg.g = the REDUCED gradient of the PREVIOUS step; flags 1: v = m v + (1-m) g, then p -= rate*lr*v
  *                   (steady state); 2: p only (first delayed step); 3: v only (leaving the schedule).  No L1 / L2
- *                   terms (they need the weights the gradient was taken at), no cost rider.
+ *                   terms (they need the weights the gradient was taken at) unless flags bit 2 (+4) is set: then
+ *                   g' = g*gscale + L1*sign(p) + 2*L2*p with the segment's L1 / L2 at seg.p -- for a caller whose
+ *                   seg.p still IS what the gradient was taken at (the pipelined schedule catching its velocity
+ *                   up).  No cost rider.
  *   TN_UPD_PIPE     pipelined single-GPU schedule: two steps in flight on the context's two streams, each with its own
  *                   weights / activations / gradients.  d_segs / h_segs = tn_pipe_seg (device array / host copy or
  *                   NULL): p = the stepping stream's own copy, psrc = the other stream's copy (p_{t-1}, read-only
  *                   there), g = the stepping stream's gradient of two steps ago, v shared; flags bit 0 = update v (0
  *                   for the first two steps: no gradient yet).  Also CLOSES the stream's parked tn_defer_reductions
  *                   window like TN_UPD_LAZY (h_segs != NULL, nseg <= 32).  gscale is not used.
+ *   TN_UPD_PIPE_REG TN_UPD_PIPE for nets with weight costs: d_segs / h_segs = tn_pipe_reg_seg.  The stepping stream's
+ *                   own copy p still holds p_{t-2}, the weights its gradient of two steps ago was taken at, so a
+ *                   segment with a non-zero L1 or L2 reads it before it is overwritten and updates v with
+ *                   g' = g + L1*sign(p_{t-2}) + 2*L2*p_{t-2} (PLAIN's expression, same bits).
  *
  * d_step != NULL: *d_step += step_inc in the same launch (the RNG step counter; step_inc must be 1 outside
- * TN_UPD_PIPE).  rowloss != NULL: one more block computes *d_cost = cost_scale * sum(rowloss[0:nrow]) in a fixed order
+ * TN_UPD_PIPE / TN_UPD_PIPE_REG).  rowloss != NULL: one more block computes *d_cost = cost_scale * sum(rowloss[0:nrow]) in a fixed order
  * -- the minibatch cost tt.mean(nll) of outlayers.py:50-51 (TN_UPD_PIPE: of the stream's PREVIOUS step) -- instead
  * of a reduction kernel of its own; with nseg == 0 the launch is that block alone.                                 */
 typedef struct tn_sgd_seg {
@@ -608,10 +635,19 @@ typedef struct tn_pipe_seg {
     uint64_t n;
     float momentum, rate;
 } tn_pipe_seg;
+typedef struct tn_pipe_reg_seg {
+    float* p;
+    const float* psrc;
+    float* v;
+    const float* g;
+    uint64_t n;
+    float momentum, rate, L1, L2;
+} tn_pipe_reg_seg;
 #define TN_UPD_PLAIN 0
 #define TN_UPD_LAZY 1
 #define TN_UPD_DELAYED 2
 #define TN_UPD_PIPE 3
+#define TN_UPD_PIPE_REG 4
 int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void* h_segs, int nseg, size_t max_n,
                       const float* d_lr, float gscale, uint32_t* d_step, uint32_t step_inc, int flags,
                       const float* rowloss, int nrow, float cost_scale, float* d_cost);
@@ -619,7 +655,7 @@ int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void* h_s
  * call: in the TN_UPD_LAZY / TN_UPD_PIPE forms the update launch walks a 2-D max-norm tensor in tn_maxnorm's tiles and
  * leaves its column sums of squares (same partial sums, same order: same bits), so the matrix is not read a second
  * time; only the rescaling pass (which touches nothing while every column is within the bound) follows.  Tensors the
- * walk cannot take, and the other modes, run the two calls back to back.  nmn <= 32.                               */
+ * walk cannot take, and the other modes (TN_UPD_PIPE_REG among them), run the two calls back to back.  nmn <= 32.      */
 int tn_sgd_update_net_maxnorm(tn_ctx* ctx, int mode, const void* d_segs, const void* h_segs, int nseg, size_t max_n,
                               const float* d_lr, float gscale, uint32_t* d_step, uint32_t step_inc, int flags,
                               const float* rowloss, int nrow, float cost_scale, float* d_cost, const tn_mn_seg* h_mn,

@@ -29,7 +29,8 @@ def backend():
 
 TN_ACT_LINEAR, TN_ACT_LEAKY, TN_ACT_TANH, TN_ACT_SIGMOID, TN_ACT_SOFTPLUS, TN_ACT_SCALED_TANH = range(6)
 TN_UNIQUE_ID_BYTES = 128
-TN_UPD_PLAIN, TN_UPD_LAZY, TN_UPD_DELAYED, TN_UPD_PIPE = range(4)     # modes of tn_sgd_update_net
+TN_UPD_PLAIN, TN_UPD_LAZY, TN_UPD_DELAYED, TN_UPD_PIPE, TN_UPD_PIPE_REG = range(5)     # modes of tn_sgd_update_net
+TN_WTCOST_CHUNK = 16384   # elements one block of tn_wtcost_net sums (include/theanet_hip.h)
 
 P = c_void_p          # device or host pointer passed as integer
 CTX = c_void_p
@@ -141,6 +142,7 @@ SIGNATURES = {
                              c_int, c_int, c_float, c_float, c_int, c_float]),
     "tn_reduce_sum": (c_int, [CTX, P, c_size_t, c_float, P, c_int]),
     "tn_wtcost": (c_int, [CTX, P, c_size_t, c_float, c_float, P, c_int]),
+    "tn_wtcost_net": (c_int, [CTX, P, c_int, P, c_int, c_float, P, c_int]),
     "tn_error_stats": (c_int, [CTX, P, P, c_int64, P, c_int, P]),
     "tn_sgd_update": (c_int, [CTX, P, P, P, c_size_t, c_float, c_float, P, c_float, c_float, c_float]),
     "tn_maxnorm": (c_int, [CTX, P, c_int, c_int, c_int, c_float]),

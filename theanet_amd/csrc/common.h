@@ -81,6 +81,10 @@ struct tn_ctx {
     int npend = 0;
     tn_red_rec pend[TN_RED_MAX];
     unsigned long long scratch_gen = 0;    // bumped by every tn_scratch_get: "nobody has asked for scratch since" checks
+    // tn_wtcost_net (wtcost.hip), per stream (two pipelined steps sum their costs side by side): the blocks' partial
+    // sums and, at wc_part[k][-4 .. -1] (a 16-byte block of its own at the allocation's start), the finishing ticket
+    float* wc_part[2] = {nullptr, nullptr};
+    size_t wc_cap[2] = {0, 0};             // partials the array holds
     // a light independent job waiting for a heavy launch to ride in (tn_rider_elastic_field)
     bool rider_valid = false;
     ElField rider;

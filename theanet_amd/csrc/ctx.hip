@@ -63,6 +63,7 @@ int tn_ctx_destroy(tn_ctx* ctx) {
     for (int i = 0; i < 2; ++i) {
         if (ctx->scratch_slot[i]) hipFree(ctx->scratch_slot[i]);
         if (ctx->tmp[i]) hipFree(ctx->tmp[i]);
+        if (ctx->wc_part[i]) hipFree(ctx->wc_part[i] - 4);
     }
     hipEventDestroy(ctx->sync_ev[0]);
     hipEventDestroy(ctx->sync_ev[1]);

@@ -34,6 +34,17 @@ __global__ __launch_bounds__(256) void sgd_update_multi_kernel(const tn_sgd_seg*
                            blockIdx.x, blockIdx.y, gridDim.x, red);
 }
 
+// g' = g + L1*sign(p) + 2*L2*p (layer.py:74-76) for a gradient already scaled, p = the weights it was taken at.  ONE
+// inline function for every form that adds the term behind a flat or lazy gradient (sgd_apply, the TN_UPD_PIPE_REG
+// kernels, TN_UPD_DELAYED with flags bit 2): same operation order and contraction, so the same bits.
+__device__ __forceinline__ float sgd_reg_grad(float gg, float pv, float L1, float L2) {
+    if (L1 != 0.f) gg += L1 * ((pv > 0.f) - (pv < 0.f));
+    if (L2 != 0.f) gg += 2.f * L2 * pv;
+    return gg;
+}
+// segment type of the pipelined update: REG = with L1 / L2 (TN_UPD_PIPE_REG)
+template <bool REG> struct PipeSeg { typedef tn_pipe_seg type; };
+template <> struct PipeSeg<true> { typedef tn_pipe_reg_seg type; };
 // Data-parallel "delayed" schedule (see NeuralNet._train_step): the reference applies the OLD velocity
 // (layer.py:82-86: v' = m v + (1-m) g ; p' = p - rate*lr*v), so the weights of step t+1 do not depend
 // on the gradient of step t -- the all-reduce of g_t may take the whole of step t+1.  At the end of
@@ -42,6 +53,8 @@ __global__ __launch_bounds__(256) void sgd_update_multi_kernel(const tn_sgd_seg*
 //   mode 2: p = p - step * v                                        -- first delayed step (v is v_t already)
 //   mode 3: v = m v + (1-m) G_{t-1}                                 -- leaving the schedule: catch v up
 // Same expressions as sgd_update_multi_block, so the weight trajectory is bit-identical.
+// REG (flags bit 2): the segment's L1 / L2 terms taken at seg.p, which the caller knows to be the weights of g.
+template <bool REG>
 __global__ __launch_bounds__(256) void sgd_update_delayed_kernel(const tn_sgd_seg* __restrict__ segs, int nseg,
                                                                 const float* __restrict__ d_lr, float gscale,
                                                                 uint32_t* d_step_inc, int mode) {
@@ -57,7 +70,8 @@ __global__ __launch_bounds__(256) void sgd_update_delayed_kernel(const tn_sgd_se
     for (size_t i = (size_t)bx * 256 + threadIdx.x; i < n; i += (size_t)nbx * 256) {
         float vv = v[i];
         if (mode != 2) {
-            const float gg = g[i] * gscale;
+            float gg = g[i] * gscale;
+            if constexpr (REG) gg = sgd_reg_grad(gg, p[i], sg.L1, sg.L2);
             vv = tn_vel(m, vv, gg);
             v[i] = vv;
         }
@@ -68,6 +82,32 @@ __global__ __launch_bounds__(256) void sgd_update_delayed_kernel(const tn_sgd_se
     }
 }
 
+// A TN_UPD_PIPE_REG segment with a non-zero term and a final gradient, update_v set: the flat walk of the pipelined
+// update with the old p_own read in.  (p is not __restrict__ here: it is read and then written.)
+__device__ __forceinline__ void pipe_reg_flat(float* p, const float* __restrict__ ps, float* __restrict__ v,
+                                              const float* __restrict__ g, size_t n, float m, float step, float L1,
+                                              float L2, int bx, int nbx) {
+    if ((n & 3) == 0 && (((uintptr_t)p | (uintptr_t)ps | (uintptr_t)v | (uintptr_t)g) & 15) == 0) {
+        for (size_t i = ((size_t)bx * 256 + threadIdx.x) * 4; i < n; i += (size_t)nbx * 1024) {
+            float4 vv = *reinterpret_cast<const float4*>(v + i);
+            const float4 gg = *reinterpret_cast<const float4*>(g + i);
+            const float4 po = *reinterpret_cast<const float4*>(p + i);
+            const float4 pv = *reinterpret_cast<const float4*>(ps + i);
+            vv.x = tn_vel(m, vv.x, sgd_reg_grad(gg.x, po.x, L1, L2)); vv.y = tn_vel(m, vv.y, sgd_reg_grad(gg.y, po.y, L1, L2));
+            vv.z = tn_vel(m, vv.z, sgd_reg_grad(gg.z, po.z, L1, L2)); vv.w = tn_vel(m, vv.w, sgd_reg_grad(gg.w, po.w, L1, L2));
+            *reinterpret_cast<float4*>(v + i) = vv;
+            *reinterpret_cast<float4*>(p + i) = make_float4(tn_stepped(pv.x, step, vv.x), tn_stepped(pv.y, step, vv.y),
+                                                            tn_stepped(pv.z, step, vv.z), tn_stepped(pv.w, step, vv.w));
+        }
+        return;
+    }
+    for (size_t i = (size_t)bx * 256 + threadIdx.x; i < n; i += (size_t)nbx * 256) {
+        const float vv = tn_vel(m, v[i], sgd_reg_grad(g[i], p[i], L1, L2));
+        v[i] = vv;
+        p[i] = tn_stepped(ps[i], step, vv);
+    }
+}
+
 // Update of the PIPELINED single-GPU schedule (two steps in flight on two streams, each with its own
 // weights, activations and gradients; NeuralNet / _PipeTrainFn).  Because the reference applies the old
 // velocity, p_t = p_{t-1} - s*v_{t-1} with v_{t-1} = m v_{t-2} + (1-m) g_{t-2}: the weights of step t
@@ -75,12 +115,16 @@ __global__ __launch_bounds__(256) void sgd_update_delayed_kernel(const tn_sgd_se
 // p_{t-1} the OTHER stream is using right now (read-only there).  One launch at the start of step t:
 //   v = m v + (1-m) g   (update_v; v is shared by both streams)   ;   p = psrc - rate*lr*v
 // Same expressions as sgd_update_multi_block: the weight trajectory is bit-identical.
-__global__ __launch_bounds__(256) void sgd_update_pipe_kernel(const tn_pipe_seg* __restrict__ segs, int nseg,
+// REG (TN_UPD_PIPE_REG): a segment with a non-zero L1 or L2 reads its own p -- still p_{t-2}, what g was taken at --
+// before overwriting it and updates v with sgd_reg_grad(g, p_{t-2}); the other segments, and REG == false, are the
+// code below as it always was.
+template <bool REG>
+__global__ __launch_bounds__(256) void sgd_update_pipe_kernel(const typename PipeSeg<REG>::type* __restrict__ segs, int nseg,
                                                              const float* __restrict__ d_lr,
                                                              uint32_t* d_step, uint32_t step_inc, int update_v) {
     const int bx = blockIdx.x, by = blockIdx.y, nbx = gridDim.x;
     if (d_step && step_inc && bx == 0 && by == 0 && threadIdx.x == 0) *d_step += step_inc;
-    const tn_pipe_seg sg = segs[by];
+    const typename PipeSeg<REG>::type sg = segs[by];
     const float step = sg.rate * d_lr[0];
     float* __restrict__ p = sg.p;
     const float* __restrict__ ps = sg.psrc;
@@ -88,6 +132,12 @@ __global__ __launch_bounds__(256) void sgd_update_pipe_kernel(const tn_pipe_seg*
     const float* __restrict__ g = sg.g;
     const size_t n = sg.n;
     const float m = sg.momentum;
+    if constexpr (REG) {
+        if ((sg.L1 != 0.f || sg.L2 != 0.f) && update_v) {
+            pipe_reg_flat(sg.p, ps, v, g, n, m, step, sg.L1, sg.L2, bx, nbx);
+            return;
+        }
+    }
     if ((n & 3) == 0 && (((uintptr_t)p | (uintptr_t)ps | (uintptr_t)v | (uintptr_t)g) & 15) == 0) {
         // 16-byte accesses: the big tensors (wide6's 16.8 M-element FC weight) are pure HBM streaming
         for (size_t i = ((size_t)bx * 256 + threadIdx.x) * 4; i < n; i += (size_t)nbx * 1024) {
@@ -239,9 +289,7 @@ struct CnPipeOp {
 
 __device__ __forceinline__ void sgd_apply(float& pv, float& vv, float gg, float gscale, float m, float step,
                                           float L1, float L2) {
-    gg *= gscale;
-    if (L1 != 0.f) gg += L1 * ((pv > 0.f) - (pv < 0.f));
-    if (L2 != 0.f) gg += 2.f * L2 * pv;
+    gg = sgd_reg_grad(gg * gscale, pv, L1, L2);
     const float vo = vv;
     vv = tn_vel(m, vo, gg);
     pv = tn_stepped(pv, step, vo);
@@ -359,7 +407,10 @@ __global__ __launch_bounds__(256) void sgd_update_lazy_kernel(const tn_sgd_seg* 
 // next step adds the slabs up on the fly (order of slab_sum_multi_kernel: bit-identical), stores the
 // gradient, applies v = m v + (1-m) g ; p = psrc - rate*lr*v, and one extra block row (by == nseg) sums
 // the previous step's cost in the fixed order of sgd_update_multi_block's rider.
-__global__ __launch_bounds__(256) void sgd_update_pipe_lazy_kernel(const tn_pipe_seg* __restrict__ segs, int nseg,
+// REG: as in sgd_update_pipe_kernel.  A segment with a non-zero term never has a slab stack here: upd_pipe leaves its
+// sums to the reduction launch in front, so the slab walks below exist once, for the segments without terms.
+template <bool REG>
+__global__ __launch_bounds__(256) void sgd_update_pipe_lazy_kernel(const typename PipeSeg<REG>::type* __restrict__ segs, int nseg,
                                                                   const float* __restrict__ d_lr, uint32_t* d_step,
                                                                   uint32_t step_inc, int update_v,
                                                                   const float* __restrict__ rowloss, int nrow,
@@ -380,7 +431,7 @@ __global__ __launch_bounds__(256) void sgd_update_pipe_lazy_kernel(const tn_pipe
         if (threadIdx.x == 0) d_cost[0] = cost_scale * ((r4[0] + r4[1]) + (r4[2] + r4[3]));
         return;
     }
-    const tn_pipe_seg sg = segs[by];
+    const typename PipeSeg<REG>::type sg = segs[by];
     const float step = sg.rate * d_lr[0], m = sg.momentum;
     float* __restrict__ p = sg.p;
     const float* __restrict__ ps = sg.psrc;
@@ -390,6 +441,12 @@ __global__ __launch_bounds__(256) void sgd_update_pipe_lazy_kernel(const tn_pipe
 #pragma unroll
     for (int k = 0; k < TN_COLNORM_MAX; ++k)
         if (cb.c[k].seg == by) return;  // this tensor is walked by sgd_colnorm_pipe_kernel
+    if constexpr (REG) {
+        if ((sg.L1 != 0.f || sg.L2 != 0.f) && update_v) {
+            pipe_reg_flat(sg.p, ps, v, g, sg.n, m, step, sg.L1, sg.L2, bx, nbx);     // (ri < 0: see upd_pipe)
+            return;
+        }
+    }
     if (ri < 0 || !update_v) {
         const size_t n = sg.n;
         if ((n & 3) == 0 && (((uintptr_t)p | (uintptr_t)ps | (uintptr_t)v | (uintptr_t)g) & 15) == 0) {
@@ -744,17 +801,27 @@ static int upd_cost(tn_ctx* ctx, const tn_sgd_seg* d_segs, int nseg, size_t max_
 
 static int upd_delayed(tn_ctx* ctx, const tn_sgd_seg* d_segs, int nseg, size_t max_n,
                                 const float* d_lr, float gscale, uint32_t* d_step_inc, int mode) {
+    const bool reg = (mode & 4) != 0;       // flags bit 2: L1 / L2 at seg.p
+    mode &= ~4;
     TN_REQUIRE(nseg > 0 && d_segs && d_lr && mode >= 1 && mode <= 3, "tn_sgd_update_net (delayed): bad arguments");
     int bx = cdiv(max_n, 1024);
     if (bx > 2048) bx = 2048;
     if (bx < 1) bx = 1;
-    sgd_update_delayed_kernel<<<dim3(bx, nseg), 256, 0, ctx->stream>>>(d_segs, nseg, d_lr, gscale, d_step_inc, mode);
+    if (reg)
+        sgd_update_delayed_kernel<true><<<dim3(bx, nseg), 256, 0, ctx->stream>>>(d_segs, nseg, d_lr, gscale, d_step_inc, mode);
+    else
+        sgd_update_delayed_kernel<false><<<dim3(bx, nseg), 256, 0, ctx->stream>>>(d_segs, nseg, d_lr, gscale, d_step_inc, mode);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
 
-static int upd_pipe(tn_ctx* ctx, const tn_pipe_seg* d_segs, const tn_pipe_seg* h_segs, int nseg, size_t max_n,
-                             const float* d_lr, uint32_t* d_step, uint32_t step_inc, int update_v,
+}  // extern "C"
+
+// REG: the TN_UPD_PIPE_REG form (SEG = tn_pipe_reg_seg); its max-norm tensors take the back-to-back route (the caller
+// passes no h_mn), so the column-norm walk keeps its one form
+template <bool REG>
+static int upd_pipe(tn_ctx* ctx, const typename PipeSeg<REG>::type* d_segs, const typename PipeSeg<REG>::type* h_segs, int nseg,
+                             size_t max_n, const float* d_lr, uint32_t* d_step, uint32_t step_inc, int update_v,
                              const float* rowloss, int nrow, float cost_scale, float* d_cost,
                              const tn_mn_seg* h_mn = nullptr, int nmn = 0) {
     TN_REQUIRE(nseg > 0 && d_segs && d_lr, "tn_sgd_update_net (pipe): bad arguments");
@@ -774,6 +841,8 @@ static int upd_pipe(tn_ctx* ctx, const tn_pipe_seg* d_segs, const tn_pipe_seg* h
         if (can)
             for (int s = 0; s < nseg; ++s)
                 if (h_segs[s].g == ctx->pend[i].out && h_segs[s].n == ctx->pend[i].n && lb.rec_of_seg[s] < 0) seg = s;
+        if constexpr (REG)                  // a segment with L1 / L2 terms takes the flat walk behind the reduction launch
+            if (seg >= 0 && (h_segs[seg].L1 != 0.f || h_segs[seg].L2 != 0.f)) seg = -1;
         if (seg >= 0) {
             lb.r[nlazy] = ctx->pend[i];
             lb.rec_of_seg[seg] = (int8_t)nlazy++;
@@ -788,7 +857,10 @@ static int upd_pipe(tn_ctx* ctx, const tn_pipe_seg* d_segs, const tn_pipe_seg* h
     ctx->scratch_off = 0;
     ColNormBatch cb;
     int fused_of_mn[32];
-    {
+    if constexpr (REG) {
+        TN_REQUIRE(nmn == 0, "tn_sgd_update_net (pipe, weight costs): the max-norm list follows in a call of its own");
+        for (int k = 0; k < TN_COLNORM_MAX; ++k) cb.c[k] = ColNormRec{-1, 0, 0, 0, 0, nullptr};
+    } else {
         const float* ps[TN_LAZY_SEGS];
         if (h_segs && nseg <= TN_LAZY_SEGS)
             for (int s = 0; s < nseg; ++s) ps[s] = h_segs[s].psrc;
@@ -796,21 +868,26 @@ static int upd_pipe(tn_ctx* ctx, const tn_pipe_seg* d_segs, const tn_pipe_seg* h
         if (rc) return rc;
     }
     if (nlazy == 0 && !rider && cb.c[0].seg < 0) {
-        sgd_update_pipe_kernel<<<dim3(bx, nseg), 256, 0, ctx->stream>>>(d_segs, nseg, d_lr, d_step, step_inc, update_v);
+        sgd_update_pipe_kernel<REG><<<dim3(bx, nseg), 256, 0, ctx->stream>>>(d_segs, nseg, d_lr, d_step, step_inc, update_v);
     } else {
-        sgd_update_pipe_lazy_kernel<<<dim3(bx, nseg + (rider ? 1 : 0)), 256, 0, ctx->stream>>>(
+        sgd_update_pipe_lazy_kernel<REG><<<dim3(bx, nseg + (rider ? 1 : 0)), 256, 0, ctx->stream>>>(
             d_segs, nseg, d_lr, d_step, step_inc, update_v, rowloss, nrow, cost_scale, d_cost, lb, cb);
     }
     TN_LAUNCH_CHECK();
-    if (cb.c[0].seg >= 0) {
-        if (update_v && !colnorm_slabs(cb, lb))
-            sgd_colnorm_pipe_kernel<true><<<colnorm_grid(cb), 256, 0, ctx->stream>>>(d_segs, d_lr, update_v, lb, cb);
-        else
-            sgd_colnorm_pipe_kernel<false><<<colnorm_grid(cb), 256, 0, ctx->stream>>>(d_segs, d_lr, update_v, lb, cb);
-        TN_LAUNCH_CHECK();
+    if constexpr (!REG) {
+        if (cb.c[0].seg >= 0) {
+            if (update_v && !colnorm_slabs(cb, lb))
+                sgd_colnorm_pipe_kernel<true><<<colnorm_grid(cb), 256, 0, ctx->stream>>>(d_segs, d_lr, update_v, lb, cb);
+            else
+                sgd_colnorm_pipe_kernel<false><<<colnorm_grid(cb), 256, 0, ctx->stream>>>(d_segs, d_lr, update_v, lb, cb);
+            TN_LAUNCH_CHECK();
+        }
+        return nmn ? maxnorm_multi_impl(ctx, h_mn, nmn, &cb, fused_of_mn) : TN_OK;
     }
-    return nmn ? maxnorm_multi_impl(ctx, h_mn, nmn, &cb, fused_of_mn) : TN_OK;
+    return TN_OK;
 }
+
+extern "C" {
 
 static int upd_lazy(tn_ctx* ctx, const tn_sgd_seg* d_segs, const tn_sgd_seg* h_segs, int nseg,
                              size_t max_n, const float* d_lr, float gscale, uint32_t* d_step_inc,
@@ -871,14 +948,14 @@ int tn_sgd_update_net_maxnorm(tn_ctx* ctx, int mode, const void* d_segs, const v
                               const float* rowloss, int nrow, float cost_scale, float* d_cost, const tn_mn_seg* h_mn,
                               int nmn) {
     TN_REQUIRE(nmn >= 0 && nmn <= 32 && (nmn == 0 || h_mn), "tn_sgd_update_net_maxnorm: bad max-norm list");
-    TN_REQUIRE(mode == TN_UPD_PIPE || d_step == nullptr || step_inc == 1,
+    TN_REQUIRE(mode == TN_UPD_PIPE || mode == TN_UPD_PIPE_REG || d_step == nullptr || step_inc == 1,
                "tn_sgd_update_net: the step counter advances by one outside the pipelined schedule");
     if (mode == TN_UPD_LAZY)
         return upd_lazy(ctx, static_cast<const tn_sgd_seg*>(d_segs), static_cast<const tn_sgd_seg*>(h_segs), nseg, max_n,
                         d_lr, gscale, d_step, rowloss, nrow, cost_scale, d_cost, h_mn, nmn);
     if (mode == TN_UPD_PIPE)
-        return upd_pipe(ctx, static_cast<const tn_pipe_seg*>(d_segs), static_cast<const tn_pipe_seg*>(h_segs), nseg, max_n,
-                        d_lr, d_step, step_inc, flags & 1, rowloss, nrow, cost_scale, d_cost, h_mn, nmn);
+        return upd_pipe<false>(ctx, static_cast<const tn_pipe_seg*>(d_segs), static_cast<const tn_pipe_seg*>(h_segs), nseg, max_n,
+                               d_lr, d_step, step_inc, flags & 1, rowloss, nrow, cost_scale, d_cost, h_mn, nmn);
     int rc = tn_sgd_update_net(ctx, mode, d_segs, h_segs, nseg, max_n, d_lr, gscale, d_step, step_inc, flags, rowloss, nrow,
                                cost_scale, d_cost);
     if (rc) return rc;
@@ -888,7 +965,7 @@ int tn_sgd_update_net_maxnorm(tn_ctx* ctx, int mode, const void* d_segs, const v
 int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void* h_segs, int nseg, size_t max_n,
                       const float* d_lr, float gscale, uint32_t* d_step, uint32_t step_inc, int flags,
                       const float* rowloss, int nrow, float cost_scale, float* d_cost) {
-    TN_REQUIRE(mode == TN_UPD_PIPE || d_step == nullptr || step_inc == 1,
+    TN_REQUIRE(mode == TN_UPD_PIPE || mode == TN_UPD_PIPE_REG || d_step == nullptr || step_inc == 1,
                "tn_sgd_update_net: the step counter advances by one outside the pipelined schedule");
     switch (mode) {
         case TN_UPD_PLAIN:
@@ -901,8 +978,11 @@ int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void* h_s
             TN_REQUIRE(rowloss == nullptr, "tn_sgd_update_net (delayed): no cost rider in this mode");
             return upd_delayed(ctx, static_cast<const tn_sgd_seg*>(d_segs), nseg, max_n, d_lr, gscale, d_step, flags);
         case TN_UPD_PIPE:
-            return upd_pipe(ctx, static_cast<const tn_pipe_seg*>(d_segs), static_cast<const tn_pipe_seg*>(h_segs), nseg, max_n,
-                            d_lr, d_step, step_inc, flags & 1, rowloss, nrow, cost_scale, d_cost);
+            return upd_pipe<false>(ctx, static_cast<const tn_pipe_seg*>(d_segs), static_cast<const tn_pipe_seg*>(h_segs), nseg,
+                                   max_n, d_lr, d_step, step_inc, flags & 1, rowloss, nrow, cost_scale, d_cost);
+        case TN_UPD_PIPE_REG:
+            return upd_pipe<true>(ctx, static_cast<const tn_pipe_reg_seg*>(d_segs), static_cast<const tn_pipe_reg_seg*>(h_segs),
+                                  nseg, max_n, d_lr, d_step, step_inc, flags & 1, rowloss, nrow, cost_scale, d_cost);
         default:
             return tn_fail(ctx, TN_E_ARG, "tn_sgd_update_net: mode %d", mode);
     }

@@ -757,6 +757,33 @@ int tn_wtcost(tn_ctx*, const float* p, size_t n, float L1, float L2, float* out,
     out[0] = (accumulate ? out[0] : 0.f) + (float)(L1 * a + L2 * s);
     return TN_OK;
 }
+// The same partition as the HIP kernel (one partial per row and TN_WTCOST_CHUNK-element chunk, added in index order; the
+// row losses as tn_reduce_sum -- this backend's rider -- adds them), so every schedule of this backend gets the same bits.
+int tn_wtcost_net(tn_ctx* ctx, const tn_wc_seg* h_tab, int ntab, const float* rowloss, int nrow, float cost_scale, float* d_cost,
+                  int accumulate) {
+    REQUIRE(ntab >= 0 && (ntab == 0 || h_tab) && d_cost && (!rowloss || nrow > 0), "tn_wtcost_net: bad arguments");
+    float w = 0.f;
+    bool any = false;
+    for (int r = 0; r < ntab; ++r) {
+        const tn_wc_seg& t = h_tab[r];
+        if (!t.n || (t.L1 == 0.f && t.L2 == 0.f)) continue;
+        any = true;
+        for (uint64_t c0 = 0; c0 < t.n; c0 += TN_WTCOST_CHUNK) {
+            const uint64_t ce = std::min<uint64_t>(t.n, c0 + TN_WTCOST_CHUNK);
+            float a = 0.f, s = 0.f;
+            for (uint64_t i = c0; i < ce; ++i) { a += std::fabs(t.p[i]); s = std::fma(t.p[i], t.p[i], s); }
+            w += std::fma(t.L2, s, t.L1 * a);
+        }
+    }
+    float out = w;
+    if (rowloss) {
+        float c = 0.f;
+        tn_reduce_sum(ctx, rowloss, nrow, cost_scale, &c, 0);
+        out = any ? c + w : c;
+    }
+    d_cost[0] = accumulate ? d_cost[0] + out : out;
+    return TN_OK;
+}
 int tn_error_stats(tn_ctx*, const int32_t* pred, const int32_t* y, int64_t y_row0, const float* rowp, int B, float* out2) {
     double e = 0.0, p = 0.0;
     for (int i = 0; i < B; ++i) { e += pred[i] != y[y_row0 + i]; p += rowp[i]; }
@@ -771,17 +798,26 @@ int tn_defer_flush_step(tn_ctx*, uint32_t* d_step) { if (d_step) *d_step += 1; r
 int tn_defer_discard(tn_ctx*) { return TN_OK; }
 
 // ================================== momentum SGD + maxnorm (layer.py:70-107) ==================================
+// g' = g + L1*sign(p) + 2*L2*p, every rounding spelled out: the forms that add the term (one step at a time, two steps in
+// flight, the catch-up of the velocity) must agree bit for bit whatever the compiler contracts around them
+static inline float reg_grad(float gg, float pv, float L1, float L2) {
+    if (L1 != 0.f) gg += L1 * (float)((pv > 0.f) - (pv < 0.f));        // (the product is exact)
+    if (L2 != 0.f) gg = std::fma(2.f * L2, pv, gg);
+    return gg;
+}
+// the two expressions of the update with their roundings spelled out, as the HIP kernels have them (common.h tn_vel,
+// tn_stepped): every form below applies them, so the schedules agree bit for bit
+static inline float vel(float m, float v, float g) { return std::fma(m, v, (1.f - m) * g); }
+static inline float stepped(float p, float step, float v) { return std::fma(-step, v, p); }
 static void sgd_seg(float* p, float* v, const float* g, size_t n, float m, float rate, float lr, float L1, float L2,
                     float gscale) {
     const float step = rate * lr;
 #pragma omp parallel for
     for (long long i = 0; i < (long long)n; ++i) {
         const float pv = p[i], vv = v[i];
-        float gg = g[i] * gscale;
-        if (L1 != 0.f) gg += L1 * ((pv > 0.f) - (pv < 0.f));
-        if (L2 != 0.f) gg += 2.f * L2 * pv;
-        v[i] = m * vv + (1.f - m) * gg;
-        p[i] = pv - step * vv;                     // the OLD velocity moves p (simultaneous Theano updates)
+        const float gg = reg_grad(g[i] * gscale, pv, L1, L2);
+        v[i] = vel(m, vv, gg);
+        p[i] = stepped(pv, step, vv);              // the OLD velocity moves p (simultaneous Theano updates)
     }
 }
 int tn_sgd_update(tn_ctx*, float* p, float* v, const float* g, size_t n, float momentum, float rate, const float* d_lr,
@@ -824,6 +860,8 @@ static int upd_cost(tn_ctx* ctx, const tn_sgd_seg* segs, int nseg, const float* 
 }
 static int upd_delayed(tn_ctx* ctx, const tn_sgd_seg* segs, int nseg, const float* d_lr, float gscale, uint32_t* d_step_inc,
                        int mode) {
+    const bool reg = (mode & 4) != 0;       // flags bit 2: L1 / L2 at seg.p
+    mode &= ~4;
     REQUIRE(nseg > 0 && segs && d_lr && mode >= 1 && mode <= 3, "tn_sgd_update_net (delayed): bad arguments");
     for (int s = 0; s < nseg; ++s) {
         const tn_sgd_seg& sg = segs[s];
@@ -831,25 +869,37 @@ static int upd_delayed(tn_ctx* ctx, const tn_sgd_seg* segs, int nseg, const floa
 #pragma omp parallel for
         for (long long i = 0; i < (long long)sg.n; ++i) {
             float vv = sg.v[i];
-            if (mode != 2) { vv = m * vv + (1.f - m) * (sg.g[i] * gscale); sg.v[i] = vv; }
-            if (mode != 3) sg.p[i] -= step * vv;
+            if (mode != 2) {
+                float gg = sg.g[i] * gscale;
+                if (reg) gg = reg_grad(gg, sg.p[i], sg.L1, sg.L2);
+                vv = vel(m, vv, gg);
+                sg.v[i] = vv;
+            }
+            if (mode != 3) sg.p[i] = stepped(sg.p[i], step, vv);
         }
     }
     if (d_step_inc) *d_step_inc += 1;
     return TN_OK;
 }
-static int upd_pipe(tn_ctx* ctx, const tn_pipe_seg* segs, int nseg, const float* d_lr, uint32_t* d_step, uint32_t step_inc,
+// segs: tn_pipe_seg, or (reg) tn_pipe_reg_seg -- TN_UPD_PIPE_REG: the stepping stream's own p still holds what g was taken at
+static int upd_pipe(tn_ctx* ctx, const void* segs, bool reg, int nseg, const float* d_lr, uint32_t* d_step, uint32_t step_inc,
                     int update_v, const float* rowloss, int nrow, float cost_scale, float* d_cost) {
     REQUIRE(nseg > 0 && segs && d_lr, "tn_sgd_update_net (pipe): bad arguments");
     if (rowloss) tn_reduce_sum(ctx, rowloss, nrow, cost_scale, d_cost, 0);      // the previous step's cost
     for (int s = 0; s < nseg; ++s) {
-        const tn_pipe_seg& sg = segs[s];
+        tn_pipe_reg_seg sg{};
+        if (reg) {
+            sg = static_cast<const tn_pipe_reg_seg*>(segs)[s];
+        } else {
+            const tn_pipe_seg& q = static_cast<const tn_pipe_seg*>(segs)[s];
+            sg.p = q.p; sg.psrc = q.psrc; sg.v = q.v; sg.g = q.g; sg.n = q.n; sg.momentum = q.momentum; sg.rate = q.rate;
+        }
         const float step = sg.rate * d_lr[0], m = sg.momentum;
 #pragma omp parallel for
         for (long long i = 0; i < (long long)sg.n; ++i) {
             float vv = sg.v[i];
-            if (update_v) { vv = m * vv + (1.f - m) * sg.g[i]; sg.v[i] = vv; }
-            sg.p[i] = sg.psrc[i] - step * vv;
+            if (update_v) { vv = vel(m, vv, reg_grad(sg.g[i], sg.p[i], sg.L1, sg.L2)); sg.v[i] = vv; }
+            sg.p[i] = stepped(sg.psrc[i], step, vv);
         }
     }
     if (d_step) *d_step += step_inc;
@@ -859,7 +909,7 @@ static int upd_pipe(tn_ctx* ctx, const tn_pipe_seg* segs, int nseg, const float*
 int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void*, int nseg, size_t, const float* d_lr, float gscale,
                       uint32_t* d_step, uint32_t step_inc, int flags, const float* rowloss, int nrow, float cost_scale,
                       float* d_cost) {
-    REQUIRE(mode == TN_UPD_PIPE || d_step == nullptr || step_inc == 1,
+    REQUIRE(mode == TN_UPD_PIPE || mode == TN_UPD_PIPE_REG || d_step == nullptr || step_inc == 1,
             "tn_sgd_update_net: the step counter advances by one outside the pipelined schedule");
     switch (mode) {
         case TN_UPD_PLAIN:
@@ -871,7 +921,8 @@ int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void*, in
             REQUIRE(rowloss == nullptr, "tn_sgd_update_net (delayed): no cost rider in this mode");
             return upd_delayed(ctx, static_cast<const tn_sgd_seg*>(d_segs), nseg, d_lr, gscale, d_step, flags);
         case TN_UPD_PIPE:
-            return upd_pipe(ctx, static_cast<const tn_pipe_seg*>(d_segs), nseg, d_lr, d_step, step_inc, flags & 1, rowloss, nrow,
+        case TN_UPD_PIPE_REG:
+            return upd_pipe(ctx, d_segs, mode == TN_UPD_PIPE_REG, nseg, d_lr, d_step, step_inc, flags & 1, rowloss, nrow,
                             cost_scale, d_cost);
         default:
             return fail(ctx, TN_E_ARG, "tn_sgd_update_net: mode %d", mode);

@@ -45,7 +45,10 @@ class DpSchedule:
             want = os.environ.get("TN_DP_BUCKETS", "auto")
             if want == "1" or (want == "auto" and self.cand[1] * 4 >= (64 << 10)):
                 self.bucket = self.cand
-        # delayed: a second flat buffer (g_{t+1} is produced while G_t is in flight), gradients free of the weights (no L1/L2)
+        # delayed: a second flat buffer (g_{t+1} is produced while G_t is in flight), gradients free of the weights (no L1/L2).
+        # Nets with weight costs stay off it: when G_t arrives the weights have moved on, and the L1 / L2 terms of g_t are
+        # taken at the weights g_t was computed at -- which this schedule, unlike the single-GPU pipelined one (whose
+        # stepping stream still holds them, TN_UPD_PIPE_REG), no longer has.
         self.can_delay = len(host) > 0 and not net._has_wtcost
         if self.can_delay:
             self.flat_ab = [net.flat_grads, net.ctx.zeros(net.flat_grads.shape)]
@@ -80,7 +83,9 @@ class DpSchedule:
 
     def catch_up(self, d_segs, d_step=None, inc=0, which=3):
         """The velocity is one gradient behind, the one table ``d_segs`` names (of a net of this net's layout): fold it in.
-        (The delayed schedule's own update is the same launch with a step counter and another ``which``.)"""
+        (The delayed schedule's own update is the same launch with a step counter and another ``which``; ``which`` + 4: with
+        the segments' L1 / L2 terms at their ``p`` -- the pipelined schedule of a weight-cost net, whose ``p`` is what the
+        gradient was taken at.)"""
         net = self.net
         net.ctx.call("tn_sgd_update_net", _lib.TN_UPD_DELAYED, d_segs.ptr, None, net._n_segs, net._max_seg,
                      net.cur_learn_rate.ptr, 1.0, d_step, inc, which, None, 0, 0.0, None)

@@ -111,6 +111,7 @@ class NeuralNet():
     _cost_pending = None      # pipelined: the last step's cost waits for the update that opens the stream's next step
     _cost_guard_ev = None     # a step_cost() loop's copy of d_cost that the next launch writing d_cost must wait for
     _mn_tab = None            # _maxnorm_table's table
+    _wc_tab = None            # _wtcost_table's table
     # what bench.py and the data-parallel workers read of the schedules (dpsched.py)
     dp_schedule = property(lambda self: self.dp.schedule)
     dp_tuned_ms = property(lambda self: self.dp.tuned_ms)
@@ -409,6 +410,10 @@ class NeuralNet():
         # data-parallel step (TN_DP_FORCE=1: exercise it with a 1-rank communicator)
         self._dp = self.world.size > 1 or os.environ.get("TN_DP_FORCE") == "1"
         self._cost_rider = self.fused_step and (not has_wtcost) and not self._dp
+        # ... and with weight costs on a single GPU: ONE launch of its own right behind the output layer's forward, when
+        # the step's weights are current and its row losses exist (tn_wtcost_net)
+        self._cost_net = self.fused_step and has_wtcost and not self._dp
+        self._wtcost_table()
         # which layers must propagate a gradient to their input
         self._need_gin = []
         seen = False
@@ -498,17 +503,23 @@ class NeuralNet():
         finally:
             ctx.fc_head(False)
         # Where the step's cost (-mean logprob[n, y_n], this rank's share of the global mean) is summed -- one of:
-        leaf = not self._cost_rider     # here: weight costs are added onto it, or it travels through the all-reduce
+        whole = self._cost_net          # here, weight costs included, in one launch: nothing is parked, nothing pending
+        leaf = not self._cost_rider and not whole   # here: it travels through the all-reduce, or the generic schedule
         rides = self._cost_rider and not pipe_stride    # in the update launch at the end of the step
         # two steps in flight: it, and the finishing slab sums, wait for the update launch that opens this stream's next step
-        parks = self._cost_rider and bool(pipe_stride)
+        parks = (self._cost_rider or whole) and bool(pipe_stride)
         # ... and when the caller reads it, ALSO now: the update's cost block on its own (same order, same bits)
         sent = self._cost_rider and self._want_outputs
         if sent:
             self._sum_cost()
+        if whole:
+            self._guard_cost()
+            tab = self._wc_tab
+            ctx.call("tn_wtcost_net", tab.ctypes.data, len(tab), out.rowloss.ptr, self.local_bsz, 1.0 / self.batch_sz,
+                     self.d_cost.ptr, 0)
         if self._want_outputs:
-            self._send_outputs(out, sent)
-        if sent or parks:
+            self._send_outputs(out, sent or whole)
+        if self._cost_rider and (sent or parks):
             self._cost_pending = not sent
         if leaf:
             self._guard_cost()
@@ -570,8 +581,15 @@ class NeuralNet():
             self._c8_tiles.stale()
             return
         delayed = self.dp.end_sequential(tail)    # the all-reduce (the delayed schedule: with its update)
-        for lyr in self.tr_layers:
-            lyr.get_wtcost(self.d_cost)
+        if whole:
+            pass
+        elif self.fused_step and self._has_wtcost:
+            # data-parallel: the row losses have travelled through the all-reduce; every rank adds the weight costs
+            tab = self._wc_tab
+            ctx.call("tn_wtcost_net", tab.ctypes.data, len(tab), None, 0, 0.0, self.d_cost.ptr, 1)
+        else:
+            for lyr in self.tr_layers:
+                lyr.get_wtcost(self.d_cost)
         if rides:
             self._guard_cost()
         cost_args = (out.rowloss.ptr if rides else None, self.local_bsz, 1.0 / self.batch_sz, self.d_cost.ptr if rides else None)
@@ -636,6 +654,21 @@ class NeuralNet():
         for i in range(0, len(tab), 32):
             chunk = tab[i:i + 32]
             self.ctx.call("tn_maxnorm_multi", chunk.ctypes.data, len(chunk))
+
+    def _wtcost_table(self):
+        """tn_wtcost_net's table (tn_wc_seg rows): every parameter tensor of every layer with a non-zero L1 or L2, frozen
+        layers included (Layer.get_wtcost adds their cost too, layer.py:109-117).  Kept alive: recorded steps bake its address."""
+        tab = self._wc_tab
+        if tab is None:
+            rows = []
+            for lyr in self.tr_layers:
+                reg = getattr(lyr, "reg", None)
+                if reg and lyr.params and (reg['L1'] or reg['L2']):
+                    rows.extend((p.ptr, p.size, float(reg['L1']), float(reg['L2'])) for p in lyr.params)
+            dt = np.dtype([('p', 'u8'), ('n', 'u8'), ('L1', 'f4'), ('L2', 'f4')])
+            assert dt.itemsize == 24          # tn_wc_seg
+            tab = self._wc_tab = np.array(rows, dtype=dt) if rows else np.zeros((0,), dt)
+        return tab
 
     def _maxnorm_table(self):
         tab = self._mn_tab
@@ -703,7 +736,9 @@ class NeuralNet():
             return False
         if self._dp and os.environ.get("TN_DP_PIPELINE", "1") == "0":
             return False
-        return not take_index_list and self._n_segs > 0 and not self._has_wtcost and not self._injecting()
+        if self._has_wtcost and not self._cost_net:
+            return False        # data-parallel steps add the weight costs behind the all-reduce, at the end of the step
+        return not take_index_list and self._n_segs > 0 and not self._injecting()
 
     def reset_accumulated_gradients(self):
         self._prepare_training()
@@ -793,11 +828,16 @@ class NeuralNet():
         if fn is not None and fn._seq is None and fn._twin is not None and fn.t > 0:
             # two steps in flight: the velocity on the device is one gradient behind (that of step t-1, still with the
             # stream that ran it, and folded in by that stream's next update): fold it in on the host, same expression
-            # as the kernels (common.h tn_vel: fma(m, v, rn((1-m) g)))
+            # as the kernels (common.h tn_vel: fma(m, v, rn((1-m) g))).  A net with weight costs has folded it in on
+            # the device when its weights were brought up to date (_PipeTrainFn.sync_weights): nothing is pending.
             fn._flush_parked()
+            if self._has_wtcost:
+                fn.sync_weights()
             self.ctx.sync()
             X = fn.nets[(fn.t - 1) & 1]
-            pend, step = (lambda i, j: X.tr_layers[i].grads[j].get_value()), fn._base + fn.t
+            step = fn._base + fn.t
+            if not fn._v_done[(fn.t - 1) & 1]:
+                pend = lambda i, j: X.tr_layers[i].grads[j].get_value()
         elif self.dp.pending_grads() is not None:
             # delayed all-reduce (TN_DP_OVERLAP=2): the same situation, the last reduced gradient travels on the second stream
             self.ctx.sync()

@@ -438,6 +438,8 @@ class _PipeTrainFn:
         self._plan = StepPlan(net.ctx, net.batch_sz, net.shard_lo)
         self._led = _CostLedger(net.ctx)     # step_cost(): costs read four calls late
         self._ord = _RowOrder(net.ctx, x_data, y_data)       # set_order(): a shuffled epoch
+        # weight-cost nets: stream k's last gradient is in the velocity already (sync_weights) -- its next update leaves v alone
+        self._v_done = [False, False]
 
     # -- set-up of the twin on first use ---------------------------------------------------------
     def _build(self):
@@ -468,15 +470,20 @@ class _PipeTrainFn:
         twin.dp.segs_rebuilt()
         self._twin = twin
         self.nets = (net, twin)
+        # nets with weight costs: tn_pipe_reg_seg rows (TN_UPD_PIPE_REG: the L1 / L2 gradient terms are taken at the
+        # stepping stream's own weights, p_{t-2}, before the update overwrites them)
+        reg = self._reg = bool(net._has_wtcost)
+        self._mode = _lib.TN_UPD_PIPE_REG if reg else _lib.TN_UPD_PIPE
         seg_dt = np.dtype([('p', 'u8'), ('psrc', 'u8'), ('v', 'u8'), ('g', 'u8'), ('n', 'u8'),
-                           ('momentum', 'f4'), ('rate', 'f4')])
+                           ('momentum', 'f4'), ('rate', 'f4')] + ([('L1', 'f4'), ('L2', 'f4')] if reg else []))
         self._segs, self._hsegs, self._lr, self._lr_set = [], [], [], [None, None]
         for X, Y in ((net, twin), (twin, net)):
             rows = []
             for lx, ly in zip(X.tr_layers, Y.tr_layers):
                 if lx.has_updates():
                     for p, ps, v, g in zip(lx.params, ly.params, lx.accumulated_updates, lx.grads):
-                        rows.append((p.ptr, ps.ptr, v.ptr, g.ptr, p.size, lx.reg['momentum'], lx.reg['rate']))
+                        rows.append((p.ptr, ps.ptr, v.ptr, g.ptr, p.size, lx.reg['momentum'], lx.reg['rate'])
+                                    + ((lx.reg['L1'], lx.reg['L2']) if reg else ()))
             host = np.array(rows, dtype=seg_dt)
             self._hsegs.append(host)             # kept alive: the update matches pending slab sums against it
             self._segs.append(ctx.array(host.view(np.uint8)))
@@ -528,7 +535,7 @@ class _PipeTrainFn:
         lr = self._lr_now()
         return self._seq is None and self._twin is not None and not self._updated and not self._want \
             and self.t >= 4 and lr == self._lr_prev and self._lr_set[0] == lr and self._lr_set[1] == lr \
-            and not self._blocked()
+            and not self._blocked() and not any(self._v_done)
 
     # -- the start-of-step update -----------------------------------------------------------------
     def _update_for(self, t):
@@ -547,12 +554,30 @@ class _PipeTrainFn:
         rider = X._cost_pending
         if rider:
             X._guard_cost()
-        X._update_and_maxnorm(_lib.TN_UPD_PIPE, self._segs[k].ptr, self._hsegs[k].ctypes.data, self._nseg,
-                              self._max_seg, self._lr[k].ptr, 1.0, X.d_step.ptr, 2 if t >= 2 else 0, 1 if t >= 2 else 0,
+        upd_v = t >= 2 and not self._v_done[k]
+        self._v_done[k] = False
+        X._update_and_maxnorm(self._mode, self._segs[k].ptr, self._hsegs[k].ctypes.data, self._nseg,
+                              self._max_seg, self._lr[k].ptr, 1.0, X.d_step.ptr, 2 if t >= 2 else 0, 1 if upd_v else 0,
                               out.rowloss.ptr if rider else None, X.local_bsz, 1.0 / X.batch_sz,
                               X.d_cost.ptr if rider else None)
         X._cost_pending = False
         ctx.call("tn_event_record", self._ev[k])
+
+    def _catch_up_v(self, t):
+        """Weight-cost nets, behind ``_update_for(t)`` when something is about to read the weights: the gradient of step
+        t-1 goes into the velocity NOW, on the device, while the net that ran that step still holds the weights it was
+        taken at (its L1 / L2 terms need them; bringing the net's own weights up to date may overwrite them, and so does
+        nothing else before that stream's next update, which then leaves the velocity alone).  On step t's stream,
+        behind its update: v_{t-1} is complete there."""
+        ctx, k = self.net.ctx, t & 1
+        Y = self.nets[1 - k]
+        ctx.call("tn_stream_select", 1 - k)
+        ctx.call("tn_defer_reductions", 0)            # the gradient of step t-1: finish its slab sums
+        ctx.call("tn_stream_wait", k, 1 - k)
+        ctx.call("tn_stream_select", k)
+        self.net.dp.catch_up(Y._d_segs, which=3 | 4)
+        ctx.call("tn_event_record", self._ev[k])
+        self._v_done[1 - k] = True
 
     def sync_weights(self):
         """Bring the net's own weights up to date (p_t after t steps) before anything reads them."""
@@ -562,6 +587,8 @@ class _PipeTrainFn:
         if not self._updated:
             self._update_for(t)
             self._updated = True
+            if self._reg:
+                self._catch_up_v(t)
         if t & 1:                                         # the twin holds p_t: copy into the net
             ctx.call("tn_stream_select", 0)
             ctx.call("tn_event_wait", self._ev[1])
@@ -594,7 +621,8 @@ class _PipeTrainFn:
             # the velocity is one gradient behind (that of step t-1, held by the stream that ran it)
             Y = self.nets[(self.t - 1) & 1]
             ctx.call("tn_stream_select", 0)
-            net.dp.catch_up(Y._d_segs)
+            if not self._v_done[(self.t - 1) & 1]:        # (weight-cost nets: sync_weights has folded it in, L1 / L2 included)
+                net.dp.catch_up(Y._d_segs)
             ctx.call("tn_set_u32", net.d_step.ptr, self._base + self.t)
             ctx.sync()
         net._pipe_fn = None
