@@ -568,6 +568,9 @@ int tn_defer_flush_step(tn_ctx* ctx, uint32_t* d_step);
  * travels with its stream across tn_stream_select).  tn_defer_discard forgets the recorded sums of both
  * streams without running them -- for windows whose owner (its gradient buffers) is gone.               */
 int tn_defer_discard(tn_ctx* ctx);
+/* number of finishing sums recorded in the current stream's open tn_defer_reductions window; if rec4 != NULL and
+ * 0 <= i < that number, rec4 = {n, S, stride, flip} of record i.  Enqueues nothing. */
+int tn_defer_pending(tn_ctx* ctx, int i, uint32_t* rec4);
 
 /* ---- momentum SGD + maxnorm (replaces Layer.get_updates; layer.py:70-107) ----
  * g' = g*gscale + L1*sign(p) + 2*L2*p ; v_new = m*v + (1-m)*g' ; p_new = p - rate*lr*v_OLD

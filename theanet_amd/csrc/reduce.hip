@@ -194,6 +194,15 @@ extern "C" int tn_defer_discard(tn_ctx* ctx) {
     return TN_OK;
 }
 
+// A read-only look at the open window (tests: which walk of the update a recorded stack will take)
+extern "C" int tn_defer_pending(tn_ctx* ctx, int i, uint32_t* rec4) {
+    if (rec4 && i >= 0 && i < ctx->npend) {
+        const tn_red_rec& r = ctx->pend[i];
+        rec4[0] = r.n; rec4[1] = r.S; rec4[2] = r.stride; rec4[3] = r.flip;
+    }
+    return ctx->npend;
+}
+
 extern "C" int tn_defer_reductions(tn_ctx* ctx, int on) {
     if (on) {
         ctx->defer = true;

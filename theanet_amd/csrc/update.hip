@@ -14,9 +14,7 @@ __global__ __launch_bounds__(256) void sgd_update_kernel(float* __restrict__ p, 
     const size_t stride = (size_t)gridDim.x * 256;
     for (; i < n; i += stride) {
         const float pv = p[i], vv = v[i];
-        float gg = g[i] * gscale;
-        if (L1 != 0.f) gg += L1 * ((pv > 0.f) - (pv < 0.f));
-        if (L2 != 0.f) gg += 2.f * L2 * pv;
+        const float gg = sgd_reg_grad(g[i] * gscale, pv, L1, L2);
         v[i] = tn_vel(momentum, vv, gg);
         p[i] = tn_stepped(pv, step, vv);
     }
@@ -34,14 +32,7 @@ __global__ __launch_bounds__(256) void sgd_update_multi_kernel(const tn_sgd_seg*
                            blockIdx.x, blockIdx.y, gridDim.x, red);
 }
 
-// g' = g + L1*sign(p) + 2*L2*p (layer.py:74-76) for a gradient already scaled, p = the weights it was taken at.  ONE
-// inline function for every form that adds the term behind a flat or lazy gradient (sgd_apply, the TN_UPD_PIPE_REG
-// kernels, TN_UPD_DELAYED with flags bit 2): same operation order and contraction, so the same bits.
-__device__ __forceinline__ float sgd_reg_grad(float gg, float pv, float L1, float L2) {
-    if (L1 != 0.f) gg += L1 * ((pv > 0.f) - (pv < 0.f));
-    if (L2 != 0.f) gg += 2.f * L2 * pv;
-    return gg;
-}
+// (sgd_reg_grad, the L1 / L2 gradient terms of every form below: update_body.h)
 // segment type of the pipelined update: REG = with L1 / L2 (TN_UPD_PIPE_REG)
 template <bool REG> struct PipeSeg { typedef tn_pipe_seg type; };
 template <> struct PipeSeg<true> { typedef tn_pipe_reg_seg type; };
@@ -824,8 +815,9 @@ static int upd_pipe(tn_ctx* ctx, const typename PipeSeg<REG>::type* d_segs, cons
                              size_t max_n, const float* d_lr, uint32_t* d_step, uint32_t step_inc, int update_v,
                              const float* rowloss, int nrow, float cost_scale, float* d_cost,
                              const tn_mn_seg* h_mn = nullptr, int nmn = 0) {
-    TN_REQUIRE(nseg > 0 && d_segs && d_lr, "tn_sgd_update_net (pipe): bad arguments");
     const bool rider = rowloss != nullptr;
+    // (nseg == 0 with a cost rider: the launch is that block alone, as in every mode)
+    TN_REQUIRE((nseg > 0 && d_segs && d_lr) || (nseg == 0 && rider), "tn_sgd_update_net (pipe): bad arguments");
     TN_REQUIRE(!rider || (d_cost != nullptr && nrow > 0), "tn_sgd_update_net (pipe): bad cost arguments");
     int bx = cdiv(max_n, 1024);
     if (bx > 2048) bx = 2048;
@@ -893,8 +885,10 @@ static int upd_lazy(tn_ctx* ctx, const tn_sgd_seg* d_segs, const tn_sgd_seg* h_s
                              size_t max_n, const float* d_lr, float gscale, uint32_t* d_step_inc,
                              const float* rowloss, int nrow, float cost_scale, float* d_cost,
                              const tn_mn_seg* h_mn = nullptr, int nmn = 0) {
-    TN_REQUIRE(nseg > 0 && nseg <= TN_LAZY_SEGS && d_segs && h_segs && d_lr, "tn_sgd_update_net (lazy): bad arguments");
     const bool rider = rowloss != nullptr;
+    // (nseg == 0 with a cost rider: the launch is that block alone, as in every mode)
+    TN_REQUIRE((nseg > 0 && nseg <= TN_LAZY_SEGS && d_segs && h_segs && d_lr) || (nseg == 0 && rider),
+               "tn_sgd_update_net (lazy): bad arguments");
     TN_REQUIRE(!rider || (d_cost != nullptr && nrow > 0), "tn_sgd_update_net (lazy): bad cost arguments");
     // pending slab sums whose output is the gradient of one of the segments are folded into the update;
     // the others (and everything when deferral is off) are finished by the ordinary reduction launch

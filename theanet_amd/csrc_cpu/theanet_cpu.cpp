@@ -796,12 +796,15 @@ int tn_error_stats(tn_ctx*, const int32_t* pred, const int32_t* y, int64_t y_row
 int tn_defer_reductions(tn_ctx*, int) { return TN_OK; }
 int tn_defer_flush_step(tn_ctx*, uint32_t* d_step) { if (d_step) *d_step += 1; return TN_OK; }
 int tn_defer_discard(tn_ctx*) { return TN_OK; }
+int tn_defer_pending(tn_ctx*, int, uint32_t*) { return 0; }        // nothing is ever recorded here
 
 // ================================== momentum SGD + maxnorm (layer.py:70-107) ==================================
 // g' = g + L1*sign(p) + 2*L2*p, every rounding spelled out: the forms that add the term (one step at a time, two steps in
 // flight, the catch-up of the velocity) must agree bit for bit whatever the compiler contracts around them
 static inline float reg_grad(float gg, float pv, float L1, float L2) {
-    if (L1 != 0.f) gg += L1 * (float)((pv > 0.f) - (pv < 0.f));        // (the product is exact)
+    // the product is exact, so the fma has the bits of gg + L1*sign(p) -- and, written as one, it leaves -ffp-contract=fast
+    // no sum to fold a caller's g*gscale into: fl(g*gscale) stays a rounding of its own, as in the HIP kernels
+    if (L1 != 0.f) gg = std::fma(L1, (float)((pv > 0.f) - (pv < 0.f)), gg);
     if (L2 != 0.f) gg = std::fma(2.f * L2, pv, gg);
     return gg;
 }
@@ -884,7 +887,7 @@ static int upd_delayed(tn_ctx* ctx, const tn_sgd_seg* segs, int nseg, const floa
 // segs: tn_pipe_seg, or (reg) tn_pipe_reg_seg -- TN_UPD_PIPE_REG: the stepping stream's own p still holds what g was taken at
 static int upd_pipe(tn_ctx* ctx, const void* segs, bool reg, int nseg, const float* d_lr, uint32_t* d_step, uint32_t step_inc,
                     int update_v, const float* rowloss, int nrow, float cost_scale, float* d_cost) {
-    REQUIRE(nseg > 0 && segs && d_lr, "tn_sgd_update_net (pipe): bad arguments");
+    REQUIRE((nseg > 0 && segs && d_lr) || (nseg == 0 && rowloss), "tn_sgd_update_net (pipe): bad arguments");
     if (rowloss) tn_reduce_sum(ctx, rowloss, nrow, cost_scale, d_cost, 0);      // the previous step's cost
     for (int s = 0; s < nseg; ++s) {
         tn_pipe_reg_seg sg{};
