@@ -664,6 +664,29 @@ int tn_sgd_update_net_maxnorm(tn_ctx* ctx, int mode, const void* d_segs, const v
                               const float* rowloss, int nrow, float cost_scale, float* d_cost, const tn_mn_seg* h_mn,
                               int nmn);
 
+/* ---- averaged weights (training param WT_AVG: d, 0 < d < 1; Polyak averaging) ----
+ * Every tensor of a layer with updates has an fp32 average a of its own shape; a_0 = the weights the net starts from.
+ * Let p_t (t >= 1) be the weights the forward pass of step t+1 reads, i.e. after the momentum step and after the
+ * max-norm projection.  Every p_t enters the average exactly once, in order, wherever the schedule produces it:
+ *     c   = fl(1 - d)                            rounded once on the host
+ *     a_t = fma(c, fl(p_t - a_{t-1}), a_{t-1})   (__fsub_rn / __fmaf_rn, the way tn_vel is spelled)
+ * p is never written.  No atomics: the same bits every run; data-parallel ranks each keep the identical average and
+ * exchange nothing.
+ * tn_avg_net: d_segs = DEVICE array of nseg tn_avg_seg (built once, like the update's segment table); max_n = the
+ * largest n among them (sizes the grid).  mode TN_AVG_UPDATE: the rule above for every segment.  mode TN_AVG_EXCHANGE:
+ * p and a change places, a bit copy both ways (c is not used) -- an evaluation at the averaged weights runs between two
+ * of them.  One launch for any nseg; a segment may start at any 4-byte boundary.  TN_E_ARG and nothing launched for a
+ * NULL table with nseg > 0, max_n == 0 with nseg > 0, c outside [0, 1] or an unknown mode; nseg == 0 does nothing.  */
+typedef struct tn_avg_seg {
+    float* p;
+    float* a;
+    uint64_t n;
+    uint64_t reserved;      /* pads the row to 32 bytes */
+} tn_avg_seg;
+#define TN_AVG_UPDATE 0
+#define TN_AVG_EXCHANGE 1
+int tn_avg_net(tn_ctx* ctx, const tn_avg_seg* d_segs, int nseg, size_t max_n, float c, int mode);
+
 /* ---- elastic input stage (replaces ElasticLayer's graph; inlayers.py:63-144) ----
  * draws layout (float32, device): [0:2] translation u(-1,1) ; [2:4] origin u(.25,.75) ;
  * [4:6] zoom u(-1,1) ; [6] theta u(-1,1) ; [7] pad ; [8 : 8+2hw] N(0,1) noise planes.

@@ -30,6 +30,7 @@ def backend():
 TN_ACT_LINEAR, TN_ACT_LEAKY, TN_ACT_TANH, TN_ACT_SIGMOID, TN_ACT_SOFTPLUS, TN_ACT_SCALED_TANH = range(6)
 TN_UNIQUE_ID_BYTES = 128
 TN_UPD_PLAIN, TN_UPD_LAZY, TN_UPD_DELAYED, TN_UPD_PIPE, TN_UPD_PIPE_REG = range(5)     # modes of tn_sgd_update_net
+TN_AVG_UPDATE, TN_AVG_EXCHANGE = range(2)     # modes of tn_avg_net
 TN_WTCOST_CHUNK = 16384   # elements one block of tn_wtcost_net sums (include/theanet_hip.h)
 
 P = c_void_p          # device or host pointer passed as integer
@@ -166,6 +167,7 @@ SIGNATURES = {
     "tn_sgd_update_net": (c_int, [CTX, c_int, P, P, c_int, c_size_t, P, c_float, P, c_uint32, c_int, P, c_int, c_float, P]),
     "tn_sgd_update_net_maxnorm": (c_int, [CTX, c_int, P, P, c_int, c_size_t, P, c_float, P, c_uint32, c_int, P, c_int, c_float, P,
                                           P, c_int]),
+    "tn_avg_net": (c_int, [CTX, P, c_int, c_size_t, c_float, c_int]),
     "tn_softmax_cost_ws_bytes": (c_size_t, [c_int]),
     "tn_softmax_nll_cost": (c_int, [CTX, P, P, c_int64, P, P, P, P, P, P, c_int, c_int, c_float,
                                     c_float, P, P]),

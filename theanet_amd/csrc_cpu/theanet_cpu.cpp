@@ -932,6 +932,38 @@ int tn_sgd_update_net(tn_ctx* ctx, int mode, const void* d_segs, const void*, in
     }
 }
 
+// ================================== averaged weights (WT_AVG) ==================================
+// a = fma(c, fl(p - a), a), the roundings of the HIP kernel (wtavg.hip); mode 1: p and a change places bit for bit
+int tn_avg_net(tn_ctx* ctx, const tn_avg_seg* segs, int nseg, size_t max_n, float c, int mode) {
+    REQUIRE(mode == TN_AVG_UPDATE || mode == TN_AVG_EXCHANGE, "tn_avg_net: mode %d", mode);
+    REQUIRE(c >= 0.f && c <= 1.f, "tn_avg_net: c = %g is not in [0, 1]", (double)c);
+    REQUIRE(nseg >= 0 && (nseg == 0 || segs != nullptr), "tn_avg_net: no segment table");
+    if (nseg == 0) return TN_OK;
+    REQUIRE(max_n > 0, "tn_avg_net: empty segments (max_n == 0)");
+    for (int s = 0; s < nseg; ++s) {
+        float* p = segs[s].p;
+        float* a = segs[s].a;
+        const long long n = (long long)segs[s].n;
+        if (mode == TN_AVG_UPDATE) {
+#pragma omp parallel for
+            for (long long i = 0; i < n; ++i) {
+                const float d = p[i] - a[i];
+                a[i] = std::fma(c, d, a[i]);
+            }
+        } else {
+            uint32_t* pu = reinterpret_cast<uint32_t*>(p);
+            uint32_t* au = reinterpret_cast<uint32_t*>(a);
+#pragma omp parallel for
+            for (long long i = 0; i < n; ++i) {
+                const uint32_t x = pu[i];
+                pu[i] = au[i];
+                au[i] = x;
+            }
+        }
+    }
+    return TN_OK;
+}
+
 // ================================== elastic input stage (inlayers.py:63-144) ==================================
 #define EL_HDR 8
 size_t tn_elastic_draws_count(int h, int w) { return (size_t)EL_HDR + 2 * (size_t)h * w; }

@@ -1,7 +1,9 @@
 """When a data-parallel net all-reduces its flat gradient buffer.  ``plain``: once, between backward pass and update.
 ``overlap`` (TN_DP_OVERLAP=1): the dense group on top of the net, the tail of the buffer, on the second stream under the conv
 blocks' backward.  ``delayed`` (=2): under the whole of the next step, which updates with the previous step's reduced
-gradient.  ``pipelined``: two steps in flight (_PipeTrainFn), on the communication stream.  Same weights bit for bit."""
+gradient.  ``pipelined``: two steps in flight (_PipeTrainFn), on the communication stream.  Same weights bit for bit -- and so the
+same averaged weights (WT_AVG): the averages' launch follows the update wherever the schedule puts it (the end of
+NeuralNet._train_step, behind ``end_sequential``'s delayed update too; _PipeTrainFn._update_for), never this module."""
 import ctypes
 import os
 import sys

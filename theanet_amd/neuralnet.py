@@ -11,6 +11,8 @@ Data-parallel: one process per GPU (RANK/WORLD_SIZE from torch.distributed.run);
 rank r works on rows [i*B + r*B/R, i*B + (r+1)*B/R) of minibatch i and the flat
 gradient buffer (+ the scalar cost) is sum-all-reduced once per step over RCCL.
 """
+import contextlib
+import numbers
 import os
 import sys
 import weakref
@@ -112,6 +114,11 @@ class NeuralNet():
     _cost_guard_ev = None     # a step_cost() loop's copy of d_cost that the next launch writing d_cost must wait for
     _mn_tab = None            # _maxnorm_table's table
     _wc_tab = None            # _wtcost_table's table
+    # WT_AVG: per layer the averages of its tensors (None: a layer without updates), tn_avg_net's device table for this
+    # net's own weight buffers (the twin of the pipelined schedule: its weights, the SAME averages), rows, largest row
+    _avg = _avg_tab = None
+    _avg_nseg = _avg_max = 0
+    _avg_swapped = False      # inside _at_avg_wts: the weight buffers hold the averages
     # what bench.py and the data-parallel workers read of the schedules (dpsched.py)
     dp_schedule = property(lambda self: self.dp.schedule)
     dp_tuned_ms = property(lambda self: self.dp.tuned_ms)
@@ -155,6 +162,15 @@ class NeuralNet():
         assert not (self.conv_mm == 'bfloat16' and self.dtype in ('float16', 'bfloat16')), (
             "CONV 'bfloat16' with DTYPE '{}': the 16-bit conv stack already runs 16-bit products on every conv layer it "
             "takes; CONV is for float32 nets".format(self.dtype))
+        # WT_AVG: d, 0 < d < 1 -- an exponential moving average of the weights (Polyak averaging) that test functions and
+        # checkpoints use: a_t = a_{t-1} + c (p_t - a_{t-1}), c = fl(1 - d), p_t = the weights after step t's update and
+        # max-norm projection, a_0 = the weights the net starts from (include/theanet_hip.h, tn_avg_net).  Absent, None
+        # or 0: off -- no buffer, no call.
+        d = training_params.get('WT_AVG')
+        assert d is None or (isinstance(d, numbers.Real) and not isinstance(d, bool) and (d == 0 or 0 < d < 1)), \
+            "WT_AVG must be a decay d with 0 < d < 1 (None or 0: no averaging), not {!r}".format(d)
+        self.wt_avg = float(d) if d else 0.0
+        self._avg_c = float(np.float32(1.0 - self.wt_avg))        # rounded once, here
         self._apply_dtype()
         self.world = comm.get_world()
         self._dev_group = None
@@ -229,6 +245,13 @@ class NeuralNet():
         self.te_layers[-1].inv_batch = 1.0 / self.batch_sz
 
         self._grads_ready = False
+        if self.wt_avg and not self._is_twin:
+            self._avg = [[self.ctx.empty(p.shape) for p in lyr.params] if lyr.has_updates() else None
+                         for lyr in self.tr_layers]
+            for lyr, avs in zip(self.tr_layers, self._avg):
+                for p, a in zip(lyr.params, avs or ()):
+                    self.ctx.call("tn_d2d", a.ptr, p.ptr, p.size * 4)
+            self._build_avg_table(self)
 
         # Set Epoch and learning rate
         if 'CUR_EPOCH' not in training_params:
@@ -458,6 +481,55 @@ class NeuralNet():
             self._h_segs = host                       # kept alive: tn_sgd_update_net (TN_UPD_LAZY) reads it
         return host
 
+    def _build_avg_table(self, main):
+        """tn_avg_net's table (tn_avg_seg rows) for THIS net's weight buffers and ``main``'s averages (the twin of the
+        pipelined schedule keeps none of its own: the averages are one chain across both streams).  Built once."""
+        seg_dt = np.dtype([('p', 'u8'), ('a', 'u8'), ('n', 'u8'), ('reserved', 'u8')])
+        assert seg_dt.itemsize == 32          # tn_avg_seg
+        rows = [(p.ptr, a.ptr, p.size, 0) for lyr, avs in zip(self.tr_layers, main._avg)
+                for p, a in zip(lyr.params, avs or ())]
+        self._avg_nseg, self._avg_max = len(rows), max([r[2] for r in rows] or [0])
+        self._avg_tab = self.ctx.array(np.array(rows, dtype=seg_dt).view(np.uint8)) if rows else None
+
+    def _avg_update(self):
+        """Behind whatever has just produced p_t in this net's weight buffers (update and max-norm projection), on its
+        stream: p_t enters the averages.  Without WT_AVG: nothing."""
+        if self._avg_tab is not None:
+            self.ctx.call("tn_avg_net", self._avg_tab.ptr, self._avg_nseg, self._avg_max, self._avg_c, _lib.TN_AVG_UPDATE)
+
+    def _avg_exchange(self):
+        """Weights and averages change places (tn_avg_net, TN_AVG_EXCHANGE: bit copies); the 16-bit stack's arranged
+        operand tiles are no longer the weights'."""
+        self.ctx.call("tn_avg_net", self._avg_tab.ptr, self._avg_nseg, self._avg_max, self._avg_c, _lib.TN_AVG_EXCHANGE)
+        self._c8_tiles.stale()
+
+    def _averaged(self, averaged):
+        """What ``averaged`` of get_test_model / get_data_test_model means for this net: None = iff WT_AVG is on."""
+        if averaged is None:
+            return self._avg_tab is not None
+        assert not averaged or self._avg_tab is not None, "averaged=True: this net keeps no averaged weights (WT_AVG is off)"
+        return bool(averaged)
+
+    @contextlib.contextmanager
+    def _at_avg_wts(self, averaged):
+        """An evaluation at the averaged weights: ONE exchange in front of everything it does and one behind it (also when
+        it raises), whatever the number of minibatches in between.  The net is brought up to date first; afterwards the
+        device is idle, so a training step on either stream finds the weights back."""
+        if not averaged:
+            yield
+            return
+        assert not self._avg_swapped, "an evaluation at the averaged weights inside another"
+        self._sync_weights()
+        self._apply_dtype()
+        self._avg_exchange()
+        self._avg_swapped = True
+        try:
+            yield
+        finally:
+            self._avg_swapped = False
+            self._avg_exchange()
+            self.ctx.sync()
+
     def _send_outputs(self, out, with_cost=False):
         """The step's features / logprob start travelling to page-locked host memory now (ordered behind the
         output layer's forward, on the context's copy stream): the copies run under the backward pass instead
@@ -613,6 +685,7 @@ class NeuralNet():
             first._cur, first._pre_valid = nxt, True
         if not mn_done:
             self._apply_maxnorm_all()
+        self._avg_update()
         self._c8_tiles.stale()
 
     def _update_and_maxnorm(self, *args):
@@ -727,6 +800,8 @@ class NeuralNet():
 
     def _sync_weights(self):
         """With two steps in flight (_PipeTrainFn) the net's own weight buffers lag behind: catch up."""
+        if self._avg_swapped:
+            return      # up to date since _at_avg_wts began -- and the twin's copy of the weights must not land on the averages
         if self._pipe_fn is not None:
             self._pipe_fn.sync_weights()
 
@@ -750,7 +825,9 @@ class NeuralNet():
             for au in (lyr.accumulated_updates or ()):
                 au.fill_bytes(0)
 
-    def get_test_model(self, x_data, y_data, aux_data=None, preds_feats=False):
+    def get_test_model(self, x_data, y_data, aux_data=None, preds_feats=False, averaged=None):
+        """``averaged``: evaluate at the averaged weights (WT_AVG) -- None: iff the net keeps them; False: at the last
+        iterate; True without WT_AVG is an assertion."""
         print('Compiling testing function... ')
         self._check_images(x_data, y_data)
         if hasattr(self, 'aux_inpt_te'):
@@ -758,13 +835,14 @@ class NeuralNet():
             aux_data = share(aux_data)
         else:
             aux_data = None
-        return _TestFn(self, share(x_data), share(y_data, np.int32), preds_feats, aux_data)
+        return _TestFn(self, share(x_data), share(y_data, np.int32), preds_feats, aux_data, self._averaged(averaged))
 
     def takes_aux(self):
         return hasattr(self, 'aux_inpt_te')
 
-    def get_data_test_model(self, get_output_of_layers=()):
+    def get_data_test_model(self, get_output_of_layers=(), averaged=None):
         print('Compiling full test function...')
+        averaged = self._averaged(averaged)       # (as in get_test_model)
         if self.tr_prms['BATCH_SZ'] != 1:
             print("\n****WARNING****: BATCH SIZE IS NOT 1. "
                   "WILL BE EXPECTING A BATCH OF INPUT IMAGES AT A TIME.\n")
@@ -779,6 +857,10 @@ class NeuralNet():
                 lyr.fused_pool.fused_conv, lyr.fused_pool = None, None
 
         def fn(x, aux=None):
+            with self._at_avg_wts(averaged):
+                return run(x, aux)
+
+        def run(x, aux):
             self._sync_weights()
             self._apply_dtype()
             self._c8_tiles.arrange(self.te_layers)
@@ -815,11 +897,38 @@ class NeuralNet():
         out = {"layers": self.layers,
                "training_params": self.tr_prms,
                "allwts": [l.get_wts() for l in self.tr_layers]}
+        if self._avg is not None:                 # WT_AVG: the averaged weights beside the raw ones (load_avg_wts)
+            out["avg_wts"] = self.get_avg_wts()
         if with_opt_state is None:
             with_opt_state = bool(self.tr_prms.get('SAVE_OPT_STATE', False))
         if with_opt_state:
             out["opt_state"] = self._opt_state()
         return out
+
+    def get_avg_wts(self):
+        """The averaged weights (WT_AVG) in the nesting of ``[l.get_wts() for l in tr_layers]``; a tensor that is never
+        updated has no average and comes as it is.  None when averaging is off."""
+        if self._avg is None:
+            return None
+        self._sync_weights()                      # two steps in flight: the last p_t enters the averages first
+        out = []
+        for lyr, avs in zip(self.tr_layers, self._avg):
+            wts = lyr.get_wts()
+            for j, a in enumerate(avs or ()):
+                wts[j] = a.get_value()
+            out.append(wts)
+        return out
+
+    def load_avg_wts(self, lst):
+        """Averaged weights saved by get_avg_wts / get_init_params()["avg_wts"]: training carries the averages on from them."""
+        assert self._avg is not None, "load_avg_wts: this net keeps no averaged weights (WT_AVG is off)"
+        assert len(lst) == len(self.tr_layers), "load_avg_wts: {} layers for a net of {}".format(len(lst), len(self.tr_layers))
+        self._sync_weights()
+        for avs, wts in zip(self._avg, lst):
+            for a, w in zip(avs or (), wts):
+                w = np.asarray(w, np.float32)
+                assert w.shape == a.shape, "load_avg_wts: a tensor of shape {} for one of {}".format(w.shape, a.shape)
+                a.set_value(w)
 
     def _opt_state(self):
         self._prepare_training()

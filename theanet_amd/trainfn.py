@@ -421,7 +421,8 @@ class _PipeTrainFn:
     backward passes while the other stream is still busy with step t-1 -- the two fill each other's
     launch gaps and lock-step phases (-18 % per step on mnist.prms).  Same weights, costs and outputs as
     the sequential schedule, bit for bit (tests/test_gpu_net.py::test_pipelined_steps_equal_sequential);
-    reading weights (get_wts, test functions, checkpoints) first brings the net up to date."""
+    reading weights (get_wts, test functions, checkpoints) first brings the net up to date.  With WT_AVG every update
+    launch is followed by the averages' on the same stream (tn_avg_net): each p_t enters them once, in order."""
 
     def __init__(self, net, x_data, y_data):
         import ctypes
@@ -468,6 +469,8 @@ class _PipeTrainFn:
         # (it is what _fall_back folds the last gradient through when the twin ran the last step)
         twin._build_seg_table()
         twin.dp.segs_rebuilt()
+        if net._avg is not None:                 # WT_AVG: ONE average per tensor, fed from whichever stream steps
+            twin._build_avg_table(net)
         self._twin = twin
         self.nets = (net, twin)
         # nets with weight costs: tn_pipe_reg_seg rows (TN_UPD_PIPE_REG: the L1 / L2 gradient terms are taken at the
@@ -561,6 +564,9 @@ class _PipeTrainFn:
                               out.rowloss.ptr if rider else None, X.local_bsz, 1.0 / X.batch_sz,
                               X.d_cost.ptr if rider else None)
         X._cost_pending = False
+        # WT_AVG: these are the weights step t reads, p_t; the averages are one chain across both streams, so the event
+        # the other stream's next update waits for covers this launch as well
+        X._avg_update()
         ctx.call("tn_event_record", self._ev[k])
 
     def _catch_up_v(self, t):
@@ -778,11 +784,13 @@ class _PipeTrainFn:
 
 class _TestFn:
     """``get_test_model``'s function: ``fn(i) -> [sym_err, P(MLE)](, features, y_preds)``; ``sweep(indices)`` evaluates a
-    run of minibatches with one weight sync, one collective and one copy back."""
+    run of minibatches with one weight sync, one collective and one copy back.  ``averaged`` (WT_AVG): a call, whatever the
+    number of minibatches, evaluates at the averaged weights (NeuralNet._at_avg_wts)."""
 
-    def __init__(self, net, x_data, y_data, preds_feats, aux_data=None):
+    def __init__(self, net, x_data, y_data, preds_feats, aux_data=None, averaged=False):
         self.net, self.x_data, self.y_data, self.preds_feats = net, x_data, y_data, preds_feats
         self.aux_data = aux_data
+        self.averaged = averaged        # WT_AVG: a call runs between two exchanges of weights and averages
         self._sweep_stats = None        # (len, 2) device rows of sweep(), grown when a longer sweep arrives
 
     def _prepare(self):
@@ -814,8 +822,12 @@ class _TestFn:
                  net.local_bsz, d_stats.ptr)
 
     def __call__(self, i):
+        _batch_in_range(i, self.x_data.shape[0], self.net.batch_sz)
+        with self.net._at_avg_wts(self.averaged):
+            return self._call(i)
+
+    def _call(self, i):
         net = self.net
-        _batch_in_range(i, self.x_data.shape[0], net.batch_sz)
         self._prepare()
         out = net.te_layers[-1]
         self._enqueue(i, out.d_stats)
@@ -845,6 +857,11 @@ class _TestFn:
         n = len(indices)
         if n == 0:
             return []
+        with net._at_avg_wts(self.averaged):
+            return self._sweep(indices)
+
+    def _sweep(self, indices):
+        net, n = self.net, len(indices)
         if self._sweep_stats is None or self._sweep_stats.shape[0] < n:
             self._sweep_stats = net.ctx.empty((n, 2))
         rows = self._sweep_stats.view(0, (n, 2))

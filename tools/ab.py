@@ -6,6 +6,11 @@ median lies outside it (round 5 credited -2.3 % to a code path no configuration 
 
     python tools/ab.py [--reps 4] [--args "--prms wide6.prms --dtype f16"] "" "TN_X=1" "TN_X=2 TN_Y=3"
     python tools/ab.py --libs old.so new.so            (two builds of the library, through TN_HIP_LIB)
+    python tools/ab.py --script tools/bench_wt_avg.py --args "--json --only mnist" "AB_TREE=../parent" "" "BENCH_WT_AVG=.999"
+
+--script: every arm runs that program (a path inside the tree, given --args alone) in place of bench.py; its last line of
+output is one JSON object with "ms_per_step".  AB_TREE=dir in an arm is not passed on: the arm runs the program of THAT
+checkout of the project (built there), from that directory -- this commit against its parent in one interleaved run.
 
 Order inside a repetition rotates (A B A', B A' A, ...) so that no arm always runs first.  Prints every run, per-arm
 median / min / max of ms_per_step (the timed region) and of the sustained figure, the A/A spread, and a verdict per arm."""
@@ -17,7 +22,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = sys.argv[1:]
-reps, extra, libs = 4, "", False
+reps, extra, libs, script = 4, "", False, None
 while args and args[0].startswith("--"):
     if args[0] == "--reps":
         reps = int(args[1]); args = args[2:]
@@ -25,6 +30,8 @@ while args and args[0].startswith("--"):
         extra = args[1]; args = args[2:]
     elif args[0] == "--libs":
         libs = True; args = args[1:]
+    elif args[0] == "--script":
+        script = args[1]; args = args[2:]
     else:
         sys.exit("unknown option " + args[0])
 arms = args or [""]
@@ -42,15 +49,19 @@ def run(label):
     for kv in envs[label].split():
         k, v = kv.split("=", 1)
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-other-configs",
-           "--no-roofline", "--steps", "400", "--warmup", "50"] + extra.split()
-    out = subprocess.run(cmd, env=env, capture_output=True, text=True)
+    tree = os.path.abspath(env.pop("AB_TREE", ROOT))
+    if script:
+        cmd = [sys.executable, os.path.join(tree, script)] + extra.split()
+    else:
+        cmd = [sys.executable, os.path.join(tree, "bench.py"), "--full", "--no-cpu-baseline", "--no-other-configs",
+               "--no-roofline", "--steps", "400", "--warmup", "50"] + extra.split()
+    out = subprocess.run(cmd, env=env, cwd=tree, capture_output=True, text=True)
     try:
         j = json.loads(out.stdout.strip().split("\n")[-1])
         return j["ms_per_step"], (j.get("sustained") or {}).get("ms_per_step", float("nan"))
     except Exception:
-        print("FAILED [%s]: %s" % (label, (out.stdout + out.stderr)[-800:]))
-        return None
+        # (nothing more is started: an arm short of a run skews its median, and a program that died on the GPU is looked at first)
+        sys.exit("FAILED [%s] (exit status %s): %s" % (label, out.returncode, (out.stdout + out.stderr)[-800:]))
 
 
 for r in range(reps):

@@ -176,6 +176,8 @@ def run(dataset_name, prms_file_name, redirect):
 
         print("\nInitializing the net ... ")
         net = nn.NeuralNet(layers, tr_prms, allwts)
+        if params.get('avg_wts') is not None and tr_prms.get('WT_AVG'):   # a resumed run carries its averaged weights on
+            net.load_avg_wts(params['avg_wts'])
         if params.get('opt_state') is not None:        # (this build's optional extension of the pickle: momentum + RNG counter)
             net.load_opt_state(params['opt_state'])
         print(net)
