@@ -482,6 +482,39 @@ int tn_fc_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float
 int tn_fc_fwd_dropout(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B,
                       int n_in, int n_out, int act, float act_param, uint8_t* mask_out, float pdrop,
                       uint64_t seed, uint32_t step, const uint32_t* d_step, uint64_t elem0);
+/* Which kernels a tn_fc_* call of this shape launches in MATMUL mode 0 (fp32; the 'bf16x3' and 'bfloat16' modes have
+ * kernels of their own) -- the launchers' own selection (the plan functions of theanet_amd/csrc/gemm.hip and
+ * fc_skinny.hip, which the entry points run), made without a context or a device.
+ *   op       0 tn_fc_fwd, 1 tn_fc_fwd_dropout, 2 tn_fc_wgrad, 3 tn_fc_dgrad, 4 tn_fc_bwd, 5 tn_fc_softmax_nll,
+ *            6 tn_fc_softmax_train
+ *   num_cus  the CU count the selection assumes; 0: the current device's, 256 where no GPU answers
+ *   flags    everything else the selection looks at; 0 is the common case
+ *            bit 0  the operand pointers (workspace included) are NOT 16-byte aligned, the byte masks not 4-byte aligned
+ *            bit 1  no mask and no prev_a (ops 0, 3, 4, 6; op 6 otherwise passes prev_a = x)
+ *            bit 2  a rider is pending in the context (tn_rider_elastic_field; ops 4, 6); it needs 256 * (flags >> 8)
+ *                   bytes of LDS
+ *            bit 3  elem0 is not a multiple of 4 (op 1)
+ *   The knobs (TN_GEMM_*, TN_FC_*, TN_PAIR_DMA, TN_SOFTMAX_TRAIN) are read as the library loaded them.
+ * A call launches up to three products (op 6 on a wide head: forward, weight gradient, input gradient; op 4: weight
+ * gradient, input gradient; the skinny pair and train kernels count as one).  Per product 17 ints:
+ *    0 family   0 skinny matrix-core (fc_skinny.hip), 1 scalar (fc_skinny_*_kernel), 2 tiled, 3 deep, 4 pair,
+ *               5 pair-DMA
+ *    1 kernel   0 gemm_f32_generic, 1 gemm_f32_fast, 2 gemm_f32_dma, 3 gemm_f32_deep, 4 gemm_f32_pair,
+ *               5 gemm_f32_pair_dma, 6 / 7 / 8 fc_skinny_fwd / wgrad / dgrad_kernel, 9 fc_skinny_fwd_mfma,
+ *               10 fc_skinny_wgrad_mfma, 11 fc_skinny_dgrad_v4, 12 fc_skinny_bwd_pair, 13 fc_skinny_softmax_train
+ *    2-4        AKC, BKC, BSUM (the gemm kernels' operand form: forward 1 0 0, weight gradient 0 0 1, input gradient 1 1 0)
+ *    5 tile rows (gemm kernels: 64 or 128; deep: 32; skinny and scalar kernels: rows per block or slab)
+ *    6 ring stages (DMA kernels) or waves (deep kernel), else 0
+ *    7 c_vec    the 16-byte epilogue
+ *    8, 9       K slabs launched, slab depth (gemm kernels)
+ *   10, 11      MT, NT: row / column tiles (deep: 32 x 32; else 64 columns; skinny: blocks)
+ *   12          a finishing or reduction launch follows
+ *   13          the dropout mask is drawn in the epilogue
+ *   14, 15      NOUT, RB template arguments of the skinny kernels (0: the kernel has none)
+ *   16          the pending rider travels in this (pair) launch
+ * Writes up to nout ints to out and returns how many the plan has; TN_E_ARG where the call would refuse the shape (and
+ * always on the CPU backend).                                                                                       */
+int tn_fc_plan(int op, int B, int n_in, int n_out, int num_cus, unsigned flags, int* out, int nout);
 
 /* ---- dropout (replaces RandomStreams.binomial; dropout.py:9-31) ----
  * mask[i] = uniform(seed, *d_step + step, elem0 + i) >= pdrop  (Philox4x32-10), i < n.

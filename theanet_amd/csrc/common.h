@@ -111,6 +111,31 @@ int tn_red_wgrad(tn_ctx* ctx, const float* w_slabs, float* dW, uint32_t n_w, uin
 // sizes the workspace from it)
 __host__ __device__ inline int sk_train_rb(int B) { return B < 2048 ? 4 : 16; }
 bool tn_fc_skinny_ok(int n_in, int n_out, const void* p0, const void* p1, const void* p2);
+// What one product of a dense layer launches.  The plan functions of gemm.hip (fc_*_plan, gemm_plan, deep_plan) and
+// tn_fc_skinny_plan (fc_skinny.hip) make the whole choice and fill this; the launchers only map it onto templates, and
+// tn_fc_plan (include/theanet_hip.h, which documents the fields) reports it.
+enum FcFamily { FCF_SKINNY, FCF_SCALAR, FCF_TILED, FCF_DEEP, FCF_PAIR, FCF_PAIR_DMA };
+enum FcKernel {
+    FCK_GENERIC, FCK_FAST, FCK_DMA, FCK_DEEP, FCK_PAIR, FCK_PAIR_DMA,      // gemm_f32_*
+    FCK_SC_FWD, FCK_SC_WGRAD, FCK_SC_DGRAD,                                // fc_skinny_*_kernel (scalar)
+    FCK_SK_FWD, FCK_SK_WGRAD, FCK_SK_DGRAD, FCK_SK_PAIR, FCK_SK_TRAIN      // fc_skinny.hip (matrix core)
+};
+struct FcProd {
+    int family, kernel;
+    int akc, bkc, bsum;        // the gemm kernels' operand form
+    int tile_m;                // rows of an output tile
+    int stages;                // ring stages (DMA kernels) or waves (deep kernel)
+    int c_vec;                 // 16-byte epilogue
+    int S, kchunk;             // K slabs launched and the slab depth
+    int MT, NT;                // output tiles
+    int finish;                // a finishing / reduction launch follows
+    int drop;                  // dropout drawn in the epilogue
+    int nout, rb;              // skinny kernels: the NOUT / RB template arguments (0: none)
+    int rider;                 // pair launches: a pending rider travels in this launch
+};
+#define FC_PROD_INTS 17
+// kernel: FCK_SK_FWD / _WGRAD / _DGRAD / _PAIR / _TRAIN (the softmax head's forward is FCK_SK_FWD)
+FcProd tn_fc_skinny_plan(int kernel, int B, int n_in, int n_out);
 int tn_fc_skinny_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B,
                      int n_in, int n_out, int act, float prm, const uint8_t* mask);
 int tn_fc_skinny_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B,

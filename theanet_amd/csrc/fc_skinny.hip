@@ -458,10 +458,39 @@ bool tn_fc_skinny_ok(int n_in, int n_out, const void* p0, const void* p1, const 
            (!p2 || ((uintptr_t)p2 & 3) == 0);
 }
 
+// The skinny launchers' whole choice (common.h: FcProd): the NOUT / RB template arguments and the slabs.  Geometry:
+//   FCK_SK_FWD    blocks of 16 rows (MT of them); n_out is a runtime argument
+//   FCK_SK_WGRAD  S slabs of 128 rows x NT blocks of 64 k (the db row is k = n_in); sk_red finishes
+//   FCK_SK_DGRAD  <NOUT>: MT blocks of SKD_ROWS rows x NT groups of 128 float4 columns
+//   FCK_SK_PAIR   <NOUT>: the two above as one launch
+//   FCK_SK_TRAIN  <NOUT, RB>: S blocks (= slabs) of RB rows; sk_red finishes
+FcProd tn_fc_skinny_plan(int kernel, int B, int n_in, int n_out) {
+    FcProd p{};
+    p.family = FCF_SKINNY; p.kernel = kernel; p.S = 1;
+    const bool templ = kernel == FCK_SK_DGRAD || kernel == FCK_SK_PAIR || kernel == FCK_SK_TRAIN;
+    if (templ) p.nout = n_out < 1 ? 1 : n_out > SK_MAX ? SK_MAX : n_out;
+    if (kernel == FCK_SK_FWD) {
+        p.tile_m = 16; p.MT = cdiv(B, 16);
+    } else if (kernel == FCK_SK_TRAIN) {
+        p.rb = sk_train_rb(B);
+        p.tile_m = p.rb; p.S = cdiv(B, p.rb); p.MT = p.S; p.bsum = 1; p.finish = 1;
+    } else {
+        if (kernel != FCK_SK_DGRAD) {
+            p.tile_m = 128; p.S = cdiv(B, 128); p.NT = cdiv(n_in + 1, 64); p.bsum = 1; p.finish = 1;
+        }
+        if (kernel != FCK_SK_WGRAD) {
+            p.MT = cdiv(B, SKD_ROWS);
+            if (kernel == FCK_SK_DGRAD) { p.tile_m = SKD_ROWS; p.NT = cdiv(n_in / 4, 128); }
+        }
+    }
+    return p;
+}
+
 int tn_fc_skinny_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B,
                      int n_in, int n_out, int act, float prm, const uint8_t* mask) {
     SkSoftmax sm{};
-    fc_skinny_fwd_mfma<<<cdiv(B, 16), 256, 0, ctx->stream>>>(x, W, b, a, B, n_in, n_out, act, prm, mask, sm);
+    const FcProd p = tn_fc_skinny_plan(FCK_SK_FWD, B, n_in, n_out);
+    fc_skinny_fwd_mfma<<<p.MT, 256, 0, ctx->stream>>>(x, W, b, a, B, n_in, n_out, act, prm, mask, sm);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
@@ -474,7 +503,8 @@ int tn_fc_skinny_softmax(tn_ctx* ctx, const float* x, const float* W, const floa
     SkSoftmax sm{};
     sm.y = y; sm.y_row0 = y_row0; sm.d_row0 = d_row0; sm.logprob = logprob; sm.rowloss = rowloss;
     sm.pred = pred; sm.rowp = rowp; sm.dz = dz; sm.inv_batch = inv_batch;
-    fc_skinny_fwd_mfma<<<cdiv(B, 16), 256, 0, ctx->stream>>>(x, W, b, logits, B, n_in, n_out,
+    const FcProd p = tn_fc_skinny_plan(FCK_SK_FWD, B, n_in, n_out);
+    fc_skinny_fwd_mfma<<<p.MT, 256, 0, ctx->stream>>>(x, W, b, logits, B, n_in, n_out,
                                                             TN_ACT_LINEAR, 0.f, nullptr, sm);
     TN_LAUNCH_CHECK();
     return TN_OK;
@@ -489,8 +519,9 @@ static int sk_red(tn_ctx* ctx, const float* ws, float* dW, float* db, int S, int
 
 int tn_fc_skinny_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int B,
                        int n_in, int n_out, float* ws) {
-    const int S = cdiv(B, 128);
-    fc_skinny_wgrad_mfma<<<dim3(cdiv(n_in + 1, 64), S), 256, 0, ctx->stream>>>(x, dz, ws, B, n_in, n_out);
+    const FcProd p = tn_fc_skinny_plan(FCK_SK_WGRAD, B, n_in, n_out);
+    const int S = p.S;
+    fc_skinny_wgrad_mfma<<<dim3(p.NT, S), 256, 0, ctx->stream>>>(x, dz, ws, B, n_in, n_out);
     TN_LAUNCH_CHECK();
     return sk_red(ctx, ws, dW, db, S, n_in, n_out);
 }
@@ -498,15 +529,16 @@ int tn_fc_skinny_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, 
 int tn_fc_skinny_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, float* dW, float* db,
                      float* dx, int B, int n_in, int n_out, float* ws, const float* prev_a, int act,
                      float prm, const uint8_t* mask) {
-    const int S = cdiv(B, 128), gxW = cdiv(n_in + 1, 64), nW = gxW * S;
-    const int gxD = cdiv(n_in / 4, 128), nD = gxD * cdiv(B, SKD_ROWS);
+    const FcProd p = tn_fc_skinny_plan(FCK_SK_PAIR, B, n_in, n_out);
+    const int S = p.S, gxW = p.NT, nW = gxW * S;
+    const int gxD = cdiv(n_in / 4, 128), nD = gxD * p.MT;
     const int grid = nW + cdiv(nD, 2);
 #define SKP_GO(N_)                                                                              \
     case N_:                                                                                    \
         fc_skinny_bwd_pair<N_><<<grid, 256, 0, ctx->stream>>>(x, dz, W, ws, dx, B, n_in, prev_a, act, prm, \
                                                              mask, gxW, nW, gxD);               \
         break
-    switch (n_out) {
+    switch (p.nout) {
         SKP_GO(1); SKP_GO(2); SKP_GO(3); SKP_GO(4); SKP_GO(5); SKP_GO(6); SKP_GO(7); SKP_GO(8);
         SKP_GO(9); SKP_GO(10); SKP_GO(11); SKP_GO(12); SKP_GO(13); SKP_GO(14); SKP_GO(15);
         default: SKP_GO(16);
@@ -525,7 +557,8 @@ int tn_fc_skinny_softmax_train(tn_ctx* ctx, const float* x, const float* W, cons
     SkSoftmax sm{};
     sm.y = y; sm.y_row0 = y_row0; sm.d_row0 = d_row0; sm.logprob = logprob; sm.rowloss = rowloss;
     sm.pred = pred; sm.rowp = rowp; sm.dz = dz; sm.inv_batch = inv_batch;
-    const int rb = sk_train_rb(B), S = cdiv(B, rb);
+    const FcProd p = tn_fc_skinny_plan(FCK_SK_TRAIN, B, n_in, n_out);
+    const int rb = p.rb, S = p.S;
 #define SKT_GO(N_)                                                                              \
     case N_:                                                                                    \
         if (rb == 4)                                                                            \
@@ -535,7 +568,7 @@ int tn_fc_skinny_softmax_train(tn_ctx* ctx, const float* x, const float* W, cons
             fc_skinny_softmax_train<N_, 16><<<S, 256, 0, ctx->stream>>>(x, W, b, logits, sm, ws, dx, B, n_in, act, \
                                                                         prm, mask, fuse_act);   \
         break
-    switch (n_out) {
+    switch (p.nout) {
         SKT_GO(1); SKT_GO(2); SKT_GO(3); SKT_GO(4); SKT_GO(5); SKT_GO(6); SKT_GO(7); SKT_GO(8);
         SKT_GO(9); SKT_GO(10); SKT_GO(11); SKT_GO(12); SKT_GO(13); SKT_GO(14); SKT_GO(15);
         default: SKT_GO(16);
@@ -547,12 +580,13 @@ int tn_fc_skinny_softmax_train(tn_ctx* ctx, const float* x, const float* W, cons
 
 int tn_fc_skinny_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, int n_in,
                        int n_out, const float* prev_a, int act, float prm, const uint8_t* mask) {
-    const dim3 grid(cdiv(n_in / 4, 128), cdiv(B, SKD_ROWS));
+    const FcProd p = tn_fc_skinny_plan(FCK_SK_DGRAD, B, n_in, n_out);
+    const dim3 grid(p.NT, p.MT);
 #define SKD_GO(N_)                                                                              \
     case N_:                                                                                    \
         fc_skinny_dgrad_v4<N_><<<grid, 128, 0, ctx->stream>>>(dz, W, dx, B, n_in, prev_a, act, prm, mask); \
         break
-    switch (n_out) {
+    switch (p.nout) {
         SKD_GO(1); SKD_GO(2); SKD_GO(3); SKD_GO(4); SKD_GO(5); SKD_GO(6); SKD_GO(7); SKD_GO(8);
         SKD_GO(9); SKD_GO(10); SKD_GO(11); SKD_GO(12); SKD_GO(13); SKD_GO(14); SKD_GO(15);
         default: SKD_GO(16);

@@ -1054,8 +1054,7 @@ static inline int vec_ok(const void* p, int ld) {
 
 // FAST needs aligned operands; row-contiguous operands also need an extent % 4 == 0 so that
 // clamped float4 groups stay inside the matrix
-template <bool AKC, bool BKC>
-static bool gemm_fast_ok(const GemmArgs& g) {
+static bool gemm_fast_ok(const GemmArgs& g, bool AKC, bool BKC) {
     return g.a_vec && g.b_vec && (AKC || (g.M % 4 == 0 && g.M >= 4)) &&
            (BKC || (g.N % 4 == 0 && g.N >= 4));
 }
@@ -1068,25 +1067,41 @@ static bool gemm_cvec_ok(const GemmArgs& g) {
            al(g.mask, 3) && al(g.drop_out, 3) && (g.elem0 & 3) == 0;
 }
 
+// ---- the selection: plain host functions of the product's GemmArgs, the CU count and the knobs.  They read pointers only
+// for their alignment and launch nothing, so tn_fc_plan runs them on stand-in pointers; the launch_* functions below map
+// the FcProd (common.h) they fill onto templates and decide nothing themselves.
+
+// grid of a 64-column-tile kernel over MT x NT tiles and S slabs
+static inline int gemm_grid(int S, int MT, int NT) { return (S == 1) ? 8 * cdiv(MT, 8) * NT : gemm_grid_split(S, MT * NT); }
+
 // DEEP pays while the 64 x 64 tiles cannot fill the chip and the L2 re-reads (M*N*K/4 bytes) stay small
-template <bool BKC>
-static bool gemm_deep_ok(tn_ctx* ctx, const GemmArgs& g) {
+static bool gemm_deep_ok(int num_cus, const GemmArgs& g) {
     if (!tn_knob(TN_K_GEMM_DEEP) || !g.a_vec || !g.b_vec || !gemm_cvec_ok(g) || g.K % 4 != 0 || g.K < 128) return false;
     if (tn_knob(TN_K_GEMM_DEEP) > 1) return true;
     const long long tiles64 = (long long)cdiv(g.M, 64) * cdiv(g.N, 64);
-    return tiles64 <= ctx->num_cus && (long long)g.M * g.N * g.K / 4 <= (128ll << 20);
+    return tiles64 <= num_cus && (long long)g.M * g.N * g.K / 4 <= (128ll << 20);
+}
+// gemm_f32_deep<BKC, NW> (forward products only: A k-contiguous): 32 x 32 tiles, 4 or 8 waves split K
+static FcProd deep_plan(int num_cus, const GemmArgs& g, bool BKC) {
+    FcProd p{};
+    p.family = FCF_DEEP; p.kernel = FCK_DEEP; p.akc = 1; p.bkc = BKC;
+    p.S = 1; p.kchunk = g.kchunk; p.c_vec = 1; p.tile_m = 32;
+    p.MT = cdiv(g.M, 32);
+    p.NT = cdiv(g.N, 32);
+    const int grid = p.MT * p.NT;
+    p.stages = (grid <= 2 * num_cus && g.K >= 512) ? 8 : 4;
+    const int deep = tn_knob(TN_K_GEMM_DEEP);
+    if (deep == 4 || deep == 8) p.stages = deep;
+    return p;
 }
 template <bool BKC>
-static void launch_deep(tn_ctx* ctx, GemmArgs& g) {
+static void launch_deep(tn_ctx* ctx, GemmArgs& g, const FcProd& p) {
     g.S = 1;
     g.c_vec = 1;
-    g.MT = cdiv(g.M, 32);
-    g.NT = cdiv(g.N, 32);
+    g.MT = p.MT;
+    g.NT = p.NT;
     const int grid = g.MT * g.NT;
-    int nw = (grid <= 2 * ctx->num_cus && g.K >= 512) ? 8 : 4;
-    const int deep = tn_knob(TN_K_GEMM_DEEP);
-    if (deep == 4 || deep == 8) nw = deep;
-    if (nw == 8)
+    if (p.stages == 8)
         gemm_f32_deep<BKC, 8><<<grid, 512, 0, ctx->stream>>>(g);
     else
         gemm_f32_deep<BKC, 4><<<grid, 256, 0, ctx->stream>>>(g);
@@ -1099,9 +1114,8 @@ extern "C" int tn_gemm_dbg_read(tn_ctx* ctx, unsigned long long* host, int nrec)
     return hipMemcpy(host, gemm_dbg_buf, (size_t)nrec * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
 }
 // DMA kernel: FAST's preconditions, every K slab holds a full tile, per-lane byte offsets fit 32 bits
-template <bool AKC, bool BKC>
-static bool gemm_dma_ok(const GemmArgs& g, int S) {
-    if (!tn_knob(TN_K_GEMM_DMA) || !gemm_fast_ok<AKC, BKC>(g)) return false;
+static bool gemm_dma_ok(const GemmArgs& g, int S, bool AKC, bool BKC) {
+    if (!tn_knob(TN_K_GEMM_DMA) || !gemm_fast_ok(g, AKC, BKC)) return false;
     const long long lastk = (long long)g.K - (long long)(S - 1) * g.kchunk;
     if (g.kchunk < 256 || lastk < 16) return false;      // short reductions (< 16 tiles) gain nothing from the ring: wide6's 128-row weight gradient measured 1.5 % of a step slower
     const long long ea = AKC ? (long long)g.M * g.lda : (long long)g.kchunk * g.lda + g.M;
@@ -1131,43 +1145,71 @@ static void launch_dma(tn_ctx* ctx, GemmArgs& g, int grid, int pad, int nb) {
 // The tile (128 x 64 once that still gives every CU two blocks, else 64 x 64) and the K-tile depth (16) are fixed: forcing
 // 64 x 64 or 128 x 64 everywhere lost to this rule in the sweeps of rounds 1-2, and a K tile of 32 measured slower at the
 // layer shapes of the configs.
-template <bool AKC, bool BKC, bool BSUM>
-static void launch_gemm(tn_ctx* ctx, GemmArgs& g, int S) {
-    const bool fast = gemm_fast_ok<AKC, BKC>(g);
-    const bool big = fast && (long long)cdiv(g.M, 128) * cdiv(g.N, 64) * S >= 2 * ctx->num_cus;
-    g.c_vec = fast && gemm_cvec_ok(g);
-    g.S = S;
-    g.NT = cdiv(g.N, 64);
-    g.MT = cdiv(g.M, big ? 128 : 64);
-    const int grid = (S == 1) ? 8 * cdiv(g.MT, 8) * g.NT : gemm_grid_split(S, g.MT * g.NT);
-    if (!fast)
-        gemm_f32_generic<AKC, BKC, BSUM><<<grid, 256, 0, ctx->stream>>>(g);
-    else if ((!big || tn_knob(TN_K_GEMM_DMA) == 2) && gemm_dma_ok<AKC, BKC>(g, S)) {
-        g.MT = cdiv(g.M, 64);
-        const int nb = (S == 1) ? 8 * cdiv(g.MT, 8) * g.NT : gemm_grid_split(S, g.MT * g.NT);
-        const int pad = tn_knob(TN_K_GEMM_DMA_PAD), nsf = tn_knob(TN_K_GEMM_DMA_NS);
-        const int grid = nb + ((BSUM && !BKC) ? S * g.NT : 0);
+static FcProd gemm_plan(int num_cus, const GemmArgs& g, int S, bool AKC, bool BKC, bool BSUM) {
+    FcProd p{};
+    p.family = FCF_TILED; p.akc = AKC; p.bkc = BKC; p.bsum = BSUM;
+    p.S = S; p.kchunk = g.kchunk;
+    const bool fast = gemm_fast_ok(g, AKC, BKC);
+    const bool big = fast && (long long)cdiv(g.M, 128) * cdiv(g.N, 64) * S >= 2 * num_cus;
+    p.c_vec = fast && gemm_cvec_ok(g);
+    p.NT = cdiv(g.N, 64);
+    p.tile_m = big ? 128 : 64;
+    p.MT = cdiv(g.M, p.tile_m);
+    p.kernel = fast ? FCK_FAST : FCK_GENERIC;
+    if (fast && (!big || tn_knob(TN_K_GEMM_DMA) == 2) && gemm_dma_ok(g, S, AKC, BKC)) {
+        p.kernel = FCK_DMA;
+        p.tile_m = 64;
+        p.MT = cdiv(g.M, 64);
         // two blocks per CU or fewer: the deep ring; else four stages
-        switch (nsf ? nsf : (nb <= 2 * ctx->num_cus ? 8 : 4)) {
+        const int nsf = tn_knob(TN_K_GEMM_DMA_NS);
+        const int ns = nsf ? nsf : (gemm_grid(S, p.MT, p.NT) <= 2 * num_cus ? 8 : 4);
+        p.stages = (ns == 8 || ns == 2) ? ns : 4;
+    }
+    return p;
+}
+template <bool AKC, bool BKC, bool BSUM>
+static void launch_gemm(tn_ctx* ctx, GemmArgs& g, const FcProd& p) {
+    const int S = p.S;
+    g.c_vec = p.c_vec;
+    g.S = S;
+    g.NT = p.NT;
+    g.MT = p.MT;
+    const int nb = gemm_grid(S, g.MT, g.NT);
+    if (p.kernel == FCK_GENERIC)
+        gemm_f32_generic<AKC, BKC, BSUM><<<nb, 256, 0, ctx->stream>>>(g);
+    else if (p.kernel == FCK_DMA) {
+        const int pad = tn_knob(TN_K_GEMM_DMA_PAD);
+        const int grid = nb + ((BSUM && !BKC) ? S * g.NT : 0);
+        switch (p.stages) {
             case 8: launch_dma<AKC, BKC, 8>(ctx, g, grid, pad, nb); break;
             case 2: launch_dma<AKC, BKC, 2>(ctx, g, grid, pad, nb); break;
             default: launch_dma<AKC, BKC, 4>(ctx, g, grid, pad, nb);
         }
-    } else if (big)
-        gemm_f32_fast<AKC, BKC, BSUM, 2, 1, 16><<<grid, 256, 0, ctx->stream>>>(g);
+    } else if (p.tile_m == 128)
+        gemm_f32_fast<AKC, BKC, BSUM, 2, 1, 16><<<nb, 256, 0, ctx->stream>>>(g);
     else
-        gemm_f32_fast<AKC, BKC, BSUM, 1, 1, 16><<<grid, 256, 0, ctx->stream>>>(g);
+        gemm_f32_fast<AKC, BKC, BSUM, 1, 1, 16><<<nb, 256, 0, ctx->stream>>>(g);
+}
+// a planned product of the tiled or deep family, in the three operand forms the dense layers use
+static void fc_launch(tn_ctx* ctx, GemmArgs& g, const FcProd& p) {
+    if (p.kernel == FCK_DEEP)
+        launch_deep<false>(ctx, g, p);
+    else if (p.bsum)
+        launch_gemm<false, false, true>(ctx, g, p);      // weight gradient
+    else if (p.bkc)
+        launch_gemm<true, true, false>(ctx, g, p);       // input gradient
+    else
+        launch_gemm<true, false, false>(ctx, g, p);      // forward
 }
 
 // prepares g for the 64 x 64 fast kernel; returns its grid size (0: not eligible)
-template <bool AKC, bool BKC>
-static int gemm_setup_small(GemmArgs& g, int S) {
-    if (!gemm_fast_ok<AKC, BKC>(g)) return 0;
+static int gemm_setup_small(GemmArgs& g, int S, bool AKC, bool BKC) {
+    if (!gemm_fast_ok(g, AKC, BKC)) return 0;
     g.c_vec = gemm_cvec_ok(g);
     g.S = S;
     g.NT = cdiv(g.N, 64);
     g.MT = cdiv(g.M, 64);
-    return (S == 1) ? 8 * cdiv(g.MT, 8) * g.NT : gemm_grid_split(S, g.MT * g.NT);
+    return gemm_grid(S, g.MT, g.NT);
 }
 
 static int wgrad_splits(int B, int n_in, int n_out) {
@@ -1351,12 +1393,16 @@ enum FcRoute {
 //   forward          (x, W)    (x, -, -)
 //   weight gradient  (x, dz)   (x, -, -)          [tn_fc_bwd asks with (x, W)]
 //   input gradient   (dz, W)   (dx, prev_a, prev_mask)
+// (MATMUL mode 0, and what the other modes leave to it: no context)
+static FcRoute fc_route_f32(int n_in, int n_out, const void* s0, const void* s1, const void* s2) {
+    if (tn_fc_skinny_ok(n_in, n_out, s0, s1, s2)) return FC_SKINNY;
+    return n_out <= SK_MAX ? FC_SCALAR : FC_TILED;
+}
 static FcRoute fc_route(tn_ctx* ctx, int B, int n_in, int n_out, const float* p, const float* q, const void* s0,
                         const void* s1, const void* s2) {
     if (ctx->fc_bf16) return FC_BF16;
     if (ctx->fc_b3 && tn_b3_fc_ok(p, q, B, n_in, n_out)) return FC_B3;
-    if (tn_fc_skinny_ok(n_in, n_out, s0, s1, s2)) return FC_SKINNY;
-    return n_out <= SK_MAX ? FC_SCALAR : FC_TILED;
+    return fc_route_f32(n_in, n_out, s0, s1, s2);
 }
 
 // a (B, n_out) = act(x W + b) * mask
@@ -1421,7 +1467,271 @@ struct FcHeadExact {
     ~FcHeadExact() { ctx->fc_bf16 = keep; }
 };
 
+// ---- short-and-deep forward products (wide6's 128 x 16384 x 1024): too few output tiles to fill
+// the chip, so the reduction is split into S slabs (plain partial products) and a finishing kernel
+// adds the slabs in order and applies bias + activation (+ dropout mask).
+__global__ __launch_bounds__(256) void fc_fwd_finish_kernel(const float* __restrict__ ws, int S, size_t MN,
+                                                           int n_out, const float* __restrict__ bias,
+                                                           const uint8_t* __restrict__ mask,
+                                                           float* __restrict__ out, int act, float prm) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= MN) return;
+    float v = 0.f;
+    for (int z = 0; z < S; ++z) v += ws[(size_t)z * MN + i];
+    v = tn_act_fwd(v + bias[i % n_out], act, prm);
+    if (mask) v = mask[i] ? v : 0.f;
+    out[i] = v;
+}
+
+static int fc_fwd_splits(int num_cus, int B, int n_in, int n_out) {
+    const long long tiles = (long long)cdiv(B, 64) * cdiv(n_out, 64);
+    if (tiles * 4 > num_cus || n_in < 64 * BK) return 1;
+    int S = (int)(2 * num_cus / tiles);
+    if (S > n_in / (8 * BK)) S = n_in / (8 * BK);
+    if (S >= 8) S &= ~7;
+    return S < 2 ? 1 : S;
+}
+
+__global__ __launch_bounds__(256) void fc_dgrad_finish_kernel(const float* __restrict__ ws, int S, size_t MN,
+                                                             const float* __restrict__ prev_a,
+                                                             const uint8_t* __restrict__ mask, float* __restrict__ out,
+                                                             int act, float prm) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= MN) return;
+    float v = 0.f;
+    for (int z = 0; z < S; ++z) v += ws[(size_t)z * MN + i];
+    if (prev_a) v *= tn_act_grad_from_out(prev_a[i], act, prm);
+    if (mask) v = mask[i] ? v : 0.f;
+    out[i] = v;
+}
+
+static int fc_dgrad_splits(int B, int n_in, int n_out) {
+    if (tn_knob(TN_K_FC_DGRAD_SPLIT) > 0) return tn_knob(TN_K_FC_DGRAD_SPLIT);
+    if (B > 256 || n_out < 32 * BK || n_in < 2048) return 1;
+    int S = n_out / (8 * BK);                  // >= 8 K-tiles per slab
+    if (S > 8) S = 8;
+    return S < 2 ? 1 : S;
+}
+
+// =====================================================================================
+// dense layers in MATMUL mode 0: what every entry point launches (the whole choice; the entry points below run it and
+// tn_fc_plan reports it).  A plan function prepares the product's GemmArgs as the launch takes them -- except the C of a
+// product that is split over K into scratch slabs: the launcher asks for the scratch once the plan says how many slabs,
+// and until then C is NULL, which stands for that 16-byte-aligned buffer.
+// =====================================================================================
+static FcProd fc_scalar_prod(int kernel, int B, int n_in, int n_out) {
+    FcProd p{};
+    p.family = FCF_SCALAR; p.kernel = kernel; p.S = 1;
+    if (kernel == FCK_SC_FWD) {
+        p.tile_m = 8; p.MT = cdiv(B, 8);
+    } else if (kernel == FCK_SC_WGRAD) {
+        p.tile_m = SK_WROWS; p.S = cdiv(B, SK_WROWS); p.NT = cdiv(n_in, 256); p.bsum = 1; p.finish = 1;
+    } else {
+        p.tile_m = 16; p.MT = cdiv(B, 16); p.NT = cdiv(n_in, 256);
+    }
+    return p;
+}
+
+// forward.  g: fc_fwd_args
+static FcProd fc_fwd_plan(int num_cus, GemmArgs& g) {
+    const int B = g.M, n_in = g.K, n_out = g.N;
+    const FcRoute route = fc_route_f32(n_in, n_out, g.A, nullptr, nullptr);
+    if (route == FC_SKINNY) return tn_fc_skinny_plan(FCK_SK_FWD, B, n_in, n_out);
+    // (a W beyond the scalar kernel's LDS runs tiled)
+    if (route == FC_SCALAR && (size_t)n_in * (n_out + 1) * sizeof(float) <= 60 * 1024)
+        return fc_scalar_prod(FCK_SC_FWD, B, n_in, n_out);
+    const int S = fc_fwd_splits(num_cus, B, n_in, n_out);
+    if (S > 1) {
+        // S partial products + the finishing kernel, which takes over bias, activation and mask
+        g.kchunk = cdiv(cdiv(g.K, S), BK) * BK;
+        g.C = nullptr; g.epi = EPI_PLAIN; g.mask = nullptr; g.drop_out = nullptr; g.bias = nullptr;
+        FcProd p = gemm_plan(num_cus, g, cdiv(g.K, g.kchunk), true, false, false);
+        p.finish = 1;
+        return p;
+    }
+    if (gemm_deep_ok(num_cus, g)) return deep_plan(num_cus, g, false);
+    return gemm_plan(num_cus, g, 1, true, false, false);
+}
+
+// forward with dropout.  g: fc_fwd_args without a mask, the dropout fields set.  The mask is drawn in the product's
+// epilogue (p.drop) only on the tiled route, with one K slab and a 16-byte epilogue; every other shape takes the mask
+// from its own launch -- the same bits -- and then runs the plain forward with that mask: g becomes that call's
+// fc_fwd_args.
+static FcProd fc_fwd_dropout_plan(int num_cus, GemmArgs& g) {
+    const int B = g.M, n_in = g.K, n_out = g.N;
+    if (fc_route_f32(n_in, n_out, g.A, nullptr, nullptr) == FC_TILED && fc_fwd_splits(num_cus, B, n_in, n_out) == 1 &&
+        gemm_fast_ok(g, true, false) && gemm_cvec_ok(g)) {
+        FcProd p = gemm_deep_ok(num_cus, g) ? deep_plan(num_cus, g, false) : gemm_plan(num_cus, g, 1, true, false, false);
+        p.drop = 1;
+        return p;
+    }
+    g = fc_fwd_args(g.A, g.B, g.bias, g.C, B, n_in, n_out, g.act, g.act_prm, g.drop_out);
+    return fc_fwd_plan(num_cus, g);
+}
+
+// weight gradient.  Tiled route: g = fc_wgrad_args, p.S slabs (fc_wgrad_sum finishes where there are several)
+static FcProd fc_wgrad_plan(int num_cus, GemmArgs& g, const float* x, const float* dz, float* dW, float* db, int B, int n_in,
+                            int n_out, void* ws) {
+    const FcRoute route = fc_route_f32(n_in, n_out, x, nullptr, nullptr);
+    if (route == FC_SKINNY) return tn_fc_skinny_plan(FCK_SK_WGRAD, B, n_in, n_out);
+    if (route == FC_SCALAR) return fc_scalar_prod(FCK_SC_WGRAD, B, n_in, n_out);
+    int Sx;
+    g = fc_wgrad_args(x, dz, dW, db, B, n_in, n_out, ws, &Sx);
+    FcProd p = gemm_plan(num_cus, g, Sx, false, false, true);
+    p.finish = Sx > 1;
+    return p;
+}
+
+// input gradient.  Tiled route: g = fc_dgrad_args
+static FcProd fc_dgrad_plan(int num_cus, GemmArgs& g, const float* dz, const float* W, float* dx, int B, int n_in, int n_out,
+                            const float* prev_a, int prev_act, float prev_act_param, const uint8_t* prev_mask) {
+    const FcRoute route = fc_route_f32(n_in, n_out, dx, prev_a, prev_mask);
+    if (route == FC_SKINNY) return tn_fc_skinny_plan(FCK_SK_DGRAD, B, n_in, n_out);
+    if (route == FC_SCALAR) return fc_scalar_prod(FCK_SC_DGRAD, B, n_in, n_out);
+    g = fc_dgrad_args(dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
+    const int S = fc_dgrad_splits(B, n_in, n_out);
+    if (S > 1) {
+        // few rows, a long reduction and a big weight matrix (wide6's 128 x 16384 <- 1024): a block per output
+        // tile is a long latency-bound chain over its 64 weight rows; S slabs of the reduction put S times
+        // as many blocks in flight, a finishing kernel adds them in order and applies act' * mask
+        g.kchunk = cdiv(cdiv(n_out, S), BK) * BK;
+        g.C = nullptr; g.epi = EPI_PLAIN; g.prev_a = nullptr; g.mask = nullptr;
+        FcProd p = gemm_plan(num_cus, g, cdiv(n_out, g.kchunk), true, true, false);
+        p.finish = 1;
+        return p;
+    }
+    return gemm_plan(num_cus, g, 1, true, true, false);
+}
+
+// paired backward.  mode: 0 = each product on its own (tn_fc_wgrad, then tn_fc_dgrad: p[0], p[1]), 1 = the skinny pair
+// kernel (p[0]), 2 = weight gradient (split-K slabs) and input gradient as ONE launch of interleaved blocks (p[0], p[1];
+// g1, g2 set up, n1 / n2 their block counts), where both are eligible for the 64 x 64 fast kernel
+struct FcBwdPlan {
+    int mode, n;
+    FcProd p[2];
+    GemmArgs g1, g2;
+    int n1, n2;
+};
+// rider_lds: the LDS bytes a rider pending in the context needs, < 0: none pending
+static FcBwdPlan fc_bwd_plan(int num_cus, long long rider_lds, const float* x, const float* dz, const float* W, float* dW,
+                             float* db, float* dx, int B, int n_in, int n_out, void* ws, const float* prev_a, int prev_act,
+                             float prev_act_param, const uint8_t* prev_mask) {
+    FcBwdPlan bp{};
+    // A family runs the pair only where BOTH products qualify for it; otherwise each product takes its own route
+    const FcRoute rw = fc_route_f32(n_in, n_out, x, nullptr, nullptr);
+    const FcRoute rd = fc_route_f32(n_in, n_out, dx, prev_a, prev_mask);
+    if (rw == FC_SKINNY && rd == FC_SKINNY) {
+        bp.mode = 1; bp.n = 1;
+        bp.p[0] = tn_fc_skinny_plan(FCK_SK_PAIR, B, n_in, n_out);
+        return bp;
+    }
+    if (n_out > SK_MAX && fc_dgrad_splits(B, n_in, n_out) == 1) {
+        int Sx;
+        bp.g1 = fc_wgrad_args(x, dz, dW, db, B, n_in, n_out, ws, &Sx);
+        bp.g2 = fc_dgrad_args(dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
+        bp.n1 = gemm_setup_small(bp.g1, Sx, false, false);
+        bp.n2 = gemm_setup_small(bp.g2, 1, true, true);
+        if (bp.n1 > 0 && bp.n2 > 0) {
+            const int pns = tn_knob(TN_K_PAIR_DMA);      // ring stages * 10 + waves per SIMD (experiments)
+            const bool use_dma = gemm_dma_ok(bp.g1, Sx, false, false) && gemm_dma_ok(bp.g2, 1, true, true);
+            // the rider works in the STATIC LDS of the kernel that is launched: the DMA form declares its ring
+            // (gemm_dma_smem_floats<NS>: 17 408 bytes at two stages), the register form 20 480 bytes -- a field that needs
+            // more than the chosen kernel has runs standalone (tn_elastic_field) instead of riding
+            const size_t rider_cap = sizeof(float) * (!use_dma ? (size_t)gemm_smem_floats<1, 1, 16>()
+                                                      : pns / 10 >= 8 ? (size_t)gemm_dma_smem_floats<8>()
+                                                      : pns / 10 >= 4 ? (size_t)gemm_dma_smem_floats<4>()
+                                                                      : (size_t)gemm_dma_smem_floats<2>());
+            bp.mode = 2; bp.n = 2;
+            for (int i = 0; i < 2; ++i) {
+                const GemmArgs& g = i ? bp.g2 : bp.g1;
+                FcProd& p = bp.p[i];
+                p.family = use_dma ? FCF_PAIR_DMA : FCF_PAIR;
+                p.kernel = use_dma ? FCK_PAIR_DMA : FCK_PAIR;
+                p.akc = i; p.bkc = i; p.bsum = !i;
+                p.tile_m = 64; p.stages = use_dma ? pns / 10 : 0;
+                p.c_vec = g.c_vec; p.S = g.S; p.kchunk = g.kchunk; p.MT = g.MT; p.NT = g.NT;
+                p.finish = !i && Sx > 1;
+                p.rider = rider_lds >= 0 && (size_t)rider_lds <= rider_cap;
+            }
+            return bp;
+        }
+    }
+    bp.mode = 0; bp.n = 2;
+    bp.p[0] = fc_wgrad_plan(num_cus, bp.g1, x, dz, dW, db, B, n_in, n_out, ws);
+    bp.p[1] = fc_dgrad_plan(num_cus, bp.g2, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
+    return bp;
+}
+
+// the softmax heads: the one-launch forms where the skinny kernels take the layer
+static bool fc_head_nll_skinny(int n_in, int n_out, const float* x) { return tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr); }
+static bool fc_head_train_skinny(int n_in, int n_out, const float* x, const float* dx, const uint8_t* prev_mask) {
+    return tn_knob(TN_K_SOFTMAX_TRAIN) && tn_fc_skinny_ok(n_in, n_out, x, dx, prev_mask);
+}
+
+// the current device's CU count (what tn_ctx_create stores in ctx->num_cus), 256 = MI355X where no device answers
+static int fc_current_cus() {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        return 256;
+    }
+    return n;
+}
+
 extern "C" {
+
+// What a tn_fc_* call of this shape launches in MATMUL mode 0, from the plan functions above on stand-in pointers (they
+// are read for their alignment only).  Layout and flags: include/theanet_hip.h.
+int tn_fc_plan(int op, int B, int n_in, int n_out, int num_cus, unsigned flags, int* out, int nout) {
+    if (B <= 0 || n_in <= 0 || n_out <= 0 || op < 0 || op > 6 || num_cus < 0 || (nout > 0 && !out)) return TN_E_ARG;
+    if (num_cus == 0) num_cus = fc_current_cus();
+    const bool unal = flags & 1, bare = flags & 2, rider = flags & 4, elem_odd = flags & 8;
+    float* const f = reinterpret_cast<float*>(static_cast<uintptr_t>(unal ? 0x1004 : 0x1000));
+    uint8_t* const m = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(unal ? 0x1001 : 0x1000));
+    const float* prev_a = bare ? nullptr : f;
+    const uint8_t* mask = bare ? nullptr : m;
+    const long long rider_lds = rider ? (long long)(flags >> 8) * 256 : -1;
+    FcProd pr[3];
+    int n = 0;
+    GemmArgs g{};
+    if (op == 0 || (op == 5 && !fc_head_nll_skinny(n_in, n_out, f))) {
+        g = fc_fwd_args(f, f, f, f, B, n_in, n_out, TN_ACT_LINEAR, 0.f, op == 0 ? mask : nullptr);
+        pr[n++] = fc_fwd_plan(num_cus, g);
+    } else if (op == 5) {
+        pr[n++] = tn_fc_skinny_plan(FCK_SK_FWD, B, n_in, n_out);
+    } else if (op == 1) {
+        g = fc_fwd_args(f, f, f, f, B, n_in, n_out, TN_ACT_LINEAR, 0.f, nullptr);
+        g.drop_out = m; g.elem0 = elem_odd ? 1 : 0;
+        pr[n++] = fc_fwd_dropout_plan(num_cus, g);
+    } else if (op == 2) {
+        pr[n++] = fc_wgrad_plan(num_cus, g, f, f, f, f, B, n_in, n_out, f);
+    } else if (op == 3) {
+        pr[n++] = fc_dgrad_plan(num_cus, g, f, f, f, B, n_in, n_out, prev_a, TN_ACT_LINEAR, 0.f, mask);
+    } else if (op == 6 && fc_head_train_skinny(n_in, n_out, f, f, mask)) {
+        pr[n++] = tn_fc_skinny_plan(FCK_SK_TRAIN, B, n_in, n_out);
+    } else {
+        if (op == 6) {       // tn_fc_softmax_nll, then tn_fc_bwd
+            if (fc_head_nll_skinny(n_in, n_out, f))
+                pr[n++] = tn_fc_skinny_plan(FCK_SK_FWD, B, n_in, n_out);
+            else {
+                g = fc_fwd_args(f, f, f, f, B, n_in, n_out, TN_ACT_LINEAR, 0.f, nullptr);
+                pr[n++] = fc_fwd_plan(num_cus, g);
+            }
+        }
+        const FcBwdPlan bp = fc_bwd_plan(num_cus, rider_lds, f, f, f, f, f, f, B, n_in, n_out, f, prev_a, TN_ACT_LINEAR, 0.f, mask);
+        for (int i = 0; i < bp.n; ++i) pr[n++] = bp.p[i];
+    }
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        const FcProd& p = pr[i];
+        const int v[FC_PROD_INTS] = {p.family, p.kernel, p.akc, p.bkc, p.bsum, p.tile_m, p.stages, p.c_vec, p.S, p.kchunk,
+                                     p.MT, p.NT, p.finish, p.drop, p.nout, p.rb, p.rider};
+        for (int j = 0; j < FC_PROD_INTS; ++j, ++k)
+            if (k < nout) out[k] = v[j];
+    }
+    return k;
+}
 
 int tn_fc_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float* b, float* logits, int B,
                         int n_in, int n_out, const int32_t* y, int64_t y_row0, const int64_t* d_row0,
@@ -1432,7 +1742,7 @@ int tn_fc_softmax_train(tn_ctx* ctx, const float* x, const float* W, const float
                "tn_fc_softmax_train: bad arguments");
     TN_REQUIRE(prev_a == nullptr || prev_a == x, "tn_fc_softmax_train: prev_a must be the layer input");
     const FcHeadExact head(ctx);
-    if (tn_knob(TN_K_SOFTMAX_TRAIN) && tn_fc_skinny_ok(n_in, n_out, x, dx, prev_mask))
+    if (fc_head_train_skinny(n_in, n_out, x, dx, prev_mask))
         return tn_fc_skinny_softmax_train(ctx, x, W, b, logits, B, n_in, n_out, y, y_row0, d_row0, logprob,
                                           rowloss, pred, rowp, dz, inv_batch, dW, db, dx, (float*)ws,
                                           prev_a != nullptr, prev_act, prev_act_param, prev_mask);
@@ -1451,7 +1761,7 @@ int tn_fc_softmax_nll(tn_ctx* ctx, const float* x, const float* W, const float* 
     TN_REQUIRE(y != nullptr || (rowloss == nullptr && dz == nullptr && rowp == nullptr),
                "tn_fc_softmax_nll: labels required for loss/gradient outputs");
     const FcHeadExact head(ctx);
-    if (tn_fc_skinny_ok(n_in, n_out, x, nullptr, nullptr))
+    if (fc_head_nll_skinny(n_in, n_out, x))
         return tn_fc_skinny_softmax(ctx, x, W, b, logits, B, n_in, n_out, y, y_row0, d_row0, logprob,
                                     rowloss, pred, rowp, dz, inv_batch);
     int rc = tn_fc_fwd(ctx, x, W, b, logits, B, n_in, n_out, TN_ACT_LINEAR, 0.f, nullptr);
@@ -1460,92 +1770,34 @@ int tn_fc_softmax_nll(tn_ctx* ctx, const float* x, const float* W, const float* 
                           inv_batch);
 }
 
-// ---- short-and-deep forward products (wide6's 128 x 16384 x 1024): too few output tiles to fill
-// the chip, so the reduction is split into S slabs (plain partial products) and a finishing kernel
-// adds the slabs in order and applies bias + activation (+ dropout mask).
-__global__ __launch_bounds__(256) void fc_fwd_finish_kernel(const float* __restrict__ ws, int S, size_t MN,
-                                                           int n_out, const float* __restrict__ bias,
-                                                           const uint8_t* __restrict__ mask,
-                                                           float* __restrict__ out, int act, float prm) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= MN) return;
-    float v = 0.f;
-    for (int z = 0; z < S; ++z) v += ws[(size_t)z * MN + i];
-    v = tn_act_fwd(v + bias[i % n_out], act, prm);
-    if (mask) v = mask[i] ? v : 0.f;
-    out[i] = v;
-}
-
-static int fc_fwd_splits(tn_ctx* ctx, int B, int n_in, int n_out) {
-    const long long tiles = (long long)cdiv(B, 64) * cdiv(n_out, 64);
-    if (tiles * 4 > ctx->num_cus || n_in < 64 * BK) return 1;
-    int S = (int)(2 * ctx->num_cus / tiles);
-    if (S > n_in / (8 * BK)) S = n_in / (8 * BK);
-    if (S >= 8) S &= ~7;
-    return S < 2 ? 1 : S;
-}
-
-// g: the forward GemmArgs (EPI_FWD); runs it as S partial products + the finishing kernel
-static int fc_fwd_splitk(tn_ctx* ctx, GemmArgs g, int S, const uint8_t* mask) {
-    const size_t MN = (size_t)g.M * g.N;
-    float* out = g.C;
-    g.kchunk = cdiv(cdiv(g.K, S), BK) * BK;
-    const int Sx = cdiv(g.K, g.kchunk);
-    float* ws;
-    int rc = tn_scratch_get(ctx, (size_t)Sx * MN * sizeof(float), &ws);
-    if (rc) return rc;
-    g.C = ws; g.epi = EPI_PLAIN; g.mask = nullptr; g.drop_out = nullptr;
-    const float* bias = g.bias;
-    g.bias = nullptr;
-    launch_gemm<true, false, false>(ctx, g, Sx);
-    TN_LAUNCH_CHECK();
-    fc_fwd_finish_kernel<<<cdiv(MN, 256), 256, 0, ctx->stream>>>(ws, Sx, MN, g.N, bias, mask, out, g.act, g.act_prm);
-    TN_LAUNCH_CHECK();
-    return TN_OK;
-}
-
-__global__ __launch_bounds__(256) void fc_dgrad_finish_kernel(const float* __restrict__ ws, int S, size_t MN,
-                                                             const float* __restrict__ prev_a,
-                                                             const uint8_t* __restrict__ mask, float* __restrict__ out,
-                                                             int act, float prm) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= MN) return;
-    float v = 0.f;
-    for (int z = 0; z < S; ++z) v += ws[(size_t)z * MN + i];
-    if (prev_a) v *= tn_act_grad_from_out(prev_a[i], act, prm);
-    if (mask) v = mask[i] ? v : 0.f;
-    out[i] = v;
-}
-
-static int fc_dgrad_splits(tn_ctx* ctx, int B, int n_in, int n_out) {
-    if (tn_knob(TN_K_FC_DGRAD_SPLIT) > 0) return tn_knob(TN_K_FC_DGRAD_SPLIT);
-    if (B > 256 || n_out < 32 * BK || n_in < 2048) return 1;
-    int S = n_out / (8 * BK);                  // >= 8 K-tiles per slab
-    if (S > 8) S = 8;
-    return S < 2 ? 1 : S;
-}
-
 int tn_fc_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int B, int n_in,
               int n_out, int act, float act_param, const uint8_t* mask) {
     TN_REQUIRE(B > 0 && n_in > 0 && n_out > 0, "tn_fc_fwd: bad shape");
     const FcRoute route = fc_route(ctx, B, n_in, n_out, x, W, x, nullptr, nullptr);
     if (route == FC_BF16) return tn_bf_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
     if (route == FC_B3) return tn_b3_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
-    if (route == FC_SKINNY) return tn_fc_skinny_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
-    const size_t sk_lds = (size_t)n_in * (n_out + 1) * sizeof(float);
-    if (route == FC_SCALAR && sk_lds <= 60 * 1024) {      // (a W beyond the kernel's LDS runs tiled)
-        fc_skinny_fwd_kernel<<<cdiv(B, 8), 256, sk_lds, ctx->stream>>>(
-            x, W, b, a, B, n_in, n_out, act, act_param, mask);
+    GemmArgs g = fc_fwd_args(x, W, b, a, B, n_in, n_out, act, act_param, mask);
+    const FcProd p = fc_fwd_plan(ctx->num_cus, g);
+    if (p.family == FCF_SKINNY) return tn_fc_skinny_fwd(ctx, x, W, b, a, B, n_in, n_out, act, act_param, mask);
+    if (p.family == FCF_SCALAR) {
+        const size_t sk_lds = (size_t)n_in * (n_out + 1) * sizeof(float);
+        fc_skinny_fwd_kernel<<<p.MT, 256, sk_lds, ctx->stream>>>(x, W, b, a, B, n_in, n_out, act, act_param, mask);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
-    GemmArgs g = fc_fwd_args(x, W, b, a, B, n_in, n_out, act, act_param, mask);
-    const int S = fc_fwd_splits(ctx, B, n_in, n_out);
-    if (S > 1) return fc_fwd_splitk(ctx, g, S, mask);
-    if (gemm_deep_ok<false>(ctx, g))
-        launch_deep<false>(ctx, g);
-    else
-        launch_gemm<true, false, false>(ctx, g, 1);
+    if (p.finish) {
+        const size_t MN = (size_t)B * n_out;
+        float* ws;
+        int rc = tn_scratch_get(ctx, (size_t)p.S * MN * sizeof(float), &ws);
+        if (rc) return rc;
+        g.C = ws;
+        fc_launch(ctx, g, p);
+        TN_LAUNCH_CHECK();
+        fc_fwd_finish_kernel<<<cdiv(MN, 256), 256, 0, ctx->stream>>>(ws, p.S, MN, n_out, b, mask, a, act, act_param);
+        TN_LAUNCH_CHECK();
+        return TN_OK;
+    }
+    fc_launch(ctx, g, p);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
@@ -1558,17 +1810,15 @@ int tn_fc_fwd_dropout(tn_ctx* ctx, const float* x, const float* W, const float* 
     GemmArgs g = fc_fwd_args(x, W, b, a, B, n_in, n_out, act, act_param, nullptr);
     g.drop_out = mask_out; g.pdrop = pdrop; g.dk0 = (uint32_t)seed; g.dk1 = (uint32_t)(seed >> 32);
     g.dstep = step; g.d_step = d_step; g.elem0 = elem0;
-    // The mask is drawn in the product's epilogue only on the tiled fp32 route, with one K slab and a 16-byte epilogue;
-    // every other route (MATMUL 'bfloat16' included) takes the mask from its own launch -- the same bits -- and then
-    // runs the product with that mask.
-    if (fc_route(ctx, B, n_in, n_out, x, W, x, nullptr, nullptr) == FC_TILED && fc_fwd_splits(ctx, B, n_in, n_out) == 1 &&
-        gemm_fast_ok<true, false>(g) && gemm_cvec_ok(g)) {
-        if (gemm_deep_ok<false>(ctx, g))
-            launch_deep<false>(ctx, g);
-        else
-            launch_gemm<true, false, false>(ctx, g, 1);  // mask drawn in the epilogue
-        TN_LAUNCH_CHECK();
-        return TN_OK;
+    // (MATMUL 'bfloat16' / 'bf16x3' draw no mask in an epilogue: the mask's own launch, then tn_fc_fwd's dispatch)
+    const FcRoute route = fc_route(ctx, B, n_in, n_out, x, W, x, nullptr, nullptr);
+    if (route != FC_BF16 && route != FC_B3) {
+        const FcProd p = fc_fwd_dropout_plan(ctx->num_cus, g);
+        if (p.drop) {
+            fc_launch(ctx, g, p);                        // mask drawn in the epilogue
+            TN_LAUNCH_CHECK();
+            return TN_OK;
+        }
     }
     int rc = tn_dropout_mask(ctx, mask_out, (size_t)B * n_out, pdrop, seed, step, d_step, elem0);
     if (rc) return rc;
@@ -1594,23 +1844,23 @@ int tn_fc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* 
         return tn_bf_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
     if (route == FC_B3)
         return tn_b3_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws, wgrad_splits(B, n_in, n_out));
-    if (route == FC_SKINNY) return tn_fc_skinny_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws);
-    if (route == FC_SCALAR) {
-        const int chunks = cdiv(B, SK_WROWS);
+    GemmArgs g{};
+    const FcProd p = fc_wgrad_plan(ctx->num_cus, g, x, dz, dW, db, B, n_in, n_out, ws);
+    if (p.family == FCF_SKINNY) return tn_fc_skinny_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, (float*)ws);
+    if (p.family == FCF_SCALAR) {
+        const int chunks = p.S;
         float* wsC = (float*)ws;
         float* wsB = wsC + (size_t)chunks * n_in * n_out;
-        fc_skinny_wgrad_kernel<<<dim3(cdiv(n_in, 256), chunks), 256, 0, ctx->stream>>>(
+        fc_skinny_wgrad_kernel<<<dim3(p.NT, chunks), 256, 0, ctx->stream>>>(
             x, dz, wsC, wsB, B, n_in, n_out);
         TN_LAUNCH_CHECK();
         const int MN = n_in * n_out;
         return tn_red_wgrad(ctx, wsC, dW, (uint32_t)MN, (uint32_t)chunks, (uint32_t)MN, wsB, db, (uint32_t)n_out,
                             (uint32_t)chunks, (uint32_t)n_out);
     }
-    int Sx;
-    GemmArgs g = fc_wgrad_args(x, dz, dW, db, B, n_in, n_out, ws, &Sx);
-    launch_gemm<false, false, true>(ctx, g, Sx);
+    fc_launch(ctx, g, p);
     TN_LAUNCH_CHECK();
-    return fc_wgrad_sum(ctx, g, Sx, dW, db);
+    return fc_wgrad_sum(ctx, g, p.S, dW, db);
 }
 
 int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, float* dW, float* db,
@@ -1632,68 +1882,57 @@ int tn_fc_bwd(tn_ctx* ctx, const float* x, const float* dz, const float* W, floa
         if (rc) return rc;
         return tn_b3_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     }
-    if (rw == FC_SKINNY && rd == FC_SKINNY)
+    // (a product that MATMUL 'bf16x3' takes alone is found again by tn_fc_wgrad / tn_fc_dgrad at the bottom; the pair
+    // forms never depended on it)
+    FcBwdPlan bp = fc_bwd_plan(ctx->num_cus, ctx->rider_valid ? (long long)ctx->rider_lds : -1, x, dz, W, dW, db, dx, B, n_in,
+                               n_out, ws, prev_a, prev_act, prev_act_param, prev_mask);
+    if (bp.mode == 1 && rw == FC_SKINNY && rd == FC_SKINNY)
         return tn_fc_skinny_bwd(ctx, x, dz, W, dW, db, dx, B, n_in, n_out, (float*)ws, prev_a, prev_act,
                                 prev_act_param, prev_mask);
-    if (n_out > SK_MAX && fc_dgrad_splits(ctx, B, n_in, n_out) == 1) {
-        // weight gradient (split-K slabs) and input gradient as ONE launch of interleaved blocks, where both are
-        // eligible for the 64 x 64 fast kernel (gemm_setup_small)
-        int Sx;
-        GemmArgs g1 = fc_wgrad_args(x, dz, dW, db, B, n_in, n_out, ws, &Sx);
-        GemmArgs g2 = fc_dgrad_args(dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
-        const int n1 = gemm_setup_small<false, false>(g1, Sx), n2 = gemm_setup_small<true, true>(g2, 1);
-        if (n1 > 0 && n2 > 0) {
-            int nrider = 0;
-            size_t rlds = 0;
-            ElField rider{};
-            const int pns = tn_knob(TN_K_PAIR_DMA);      // ring stages * 10 + waves per SIMD (experiments)
-            const bool use_dma = gemm_dma_ok<false, false>(g1, Sx) && gemm_dma_ok<true, true>(g2, 1);
-            // the rider works in the STATIC LDS of the kernel that is launched: the DMA form declares its ring
-            // (gemm_dma_smem_floats<NS>: 17 408 bytes at two stages), the register form 20 480 bytes -- a field that needs
-            // more than the chosen kernel has runs standalone (tn_elastic_field) instead of riding
-            const size_t rider_cap = sizeof(float) * (!use_dma ? (size_t)gemm_smem_floats<1, 1, 16>()
-                                                      : pns / 10 >= 8 ? (size_t)gemm_dma_smem_floats<8>()
-                                                      : pns / 10 >= 4 ? (size_t)gemm_dma_smem_floats<4>()
-                                                                      : (size_t)gemm_dma_smem_floats<2>());
-            if (ctx->rider_valid && ctx->rider_lds <= rider_cap) {
-                rider = ctx->rider;
-                nrider = cdiv(rider.h * rider.w, 4);
-                rlds = 0;                                  // the rider works in the tile's static LDS
-                ctx->rider_valid = false;
-            }
-            {
-                // Residency cap while two steps are in flight: 8 KB of unused dynamic LDS per block = five blocks per
-                // CU instead of six.  Alone on the GPU six are faster (60.2 vs 63.2 us); with two steps in flight the
-                // launch shares the chip with the other stream's forward kernels, and five blocks x 80 registers
-                // leave them a fifth of the register file (six leave 32 registers per lane: nothing else fits and the
-                // streams take turns): 176-177 vs 180 us per step.  "In flight" = the second stream was selected
-                // within the last few heavy launches (tn_stream_select); TN_PAIR_LDS_PAD=n forces a pad for an A/B.
-                const int pad = tn_knob(TN_K_PAIR_LDS_PAD);
-                if (pad >= 0)
-                    rlds += (size_t)pad;
-                else if (ctx->heavy_since_side < 3) {
-                    ctx->heavy_since_side++;
-                    // (launches with many block rounds per CU gain nothing from sharing: cifar_like's 3072-block
-                    // fc backward is 0.7 % of a step slower with the pad)
-                    if (n1 + n2 <= 8 * ctx->num_cus) rlds += 8192;
-                }
-            }
-            if (use_dma) {
-                const int ncs = Sx * g1.NT;
-                const int grid = n1 + n2 + ncs + nrider;
-#define TN_PAIR_CASE(NS_, W_) case NS_ * 10 + W_: gemm_f32_pair_dma<false, false, true, true, NS_, W_><<<grid, 256, rlds, ctx->stream>>>(g1, g2, n1, n2, ncs, rider); break;
-                switch (pns) {
-                    TN_PAIR_CASE(2, 6) TN_PAIR_CASE(2, 5) TN_PAIR_CASE(2, 4) TN_PAIR_CASE(4, 5) TN_PAIR_CASE(4, 4) TN_PAIR_CASE(4, 3)
-                    TN_PAIR_CASE(8, 2)
-                    default: return tn_fail(ctx, TN_E_ARG, "TN_PAIR_DMA: unknown variant %d", pns);
-                }
-#undef TN_PAIR_CASE
-            } else
-                gemm_f32_pair<false, false, true, true, true, false><<<n1 + n2 + nrider, 256, rlds, ctx->stream>>>(
-                    g1, g2, n1, n2, rider);
-            TN_LAUNCH_CHECK();
-            return fc_wgrad_sum(ctx, g1, Sx, dW, db);
+    if (bp.mode == 2) {
+        GemmArgs &g1 = bp.g1, &g2 = bp.g2;
+        const int n1 = bp.n1, n2 = bp.n2, Sx = bp.p[0].S;
+        int nrider = 0;
+        size_t rlds = 0;
+        ElField rider{};
+        if (bp.p[0].rider) {
+            rider = ctx->rider;
+            nrider = cdiv(rider.h * rider.w, 4);
+            rlds = 0;                                  // the rider works in the tile's static LDS
+            ctx->rider_valid = false;
         }
+        {
+            // Residency cap while two steps are in flight: 8 KB of unused dynamic LDS per block = five blocks per
+            // CU instead of six.  Alone on the GPU six are faster (60.2 vs 63.2 us); with two steps in flight the
+            // launch shares the chip with the other stream's forward kernels, and five blocks x 80 registers
+            // leave them a fifth of the register file (six leave 32 registers per lane: nothing else fits and the
+            // streams take turns): 176-177 vs 180 us per step.  "In flight" = the second stream was selected
+            // within the last few heavy launches (tn_stream_select); TN_PAIR_LDS_PAD=n forces a pad for an A/B.
+            const int pad = tn_knob(TN_K_PAIR_LDS_PAD);
+            if (pad >= 0)
+                rlds += (size_t)pad;
+            else if (ctx->heavy_since_side < 3) {
+                ctx->heavy_since_side++;
+                // (launches with many block rounds per CU gain nothing from sharing: cifar_like's 3072-block
+                // fc backward is 0.7 % of a step slower with the pad)
+                if (n1 + n2 <= 8 * ctx->num_cus) rlds += 8192;
+            }
+        }
+        if (bp.p[0].kernel == FCK_PAIR_DMA) {
+            const int ncs = Sx * g1.NT;
+            const int grid = n1 + n2 + ncs + nrider;
+#define TN_PAIR_CASE(NS_, W_) case NS_ * 10 + W_: gemm_f32_pair_dma<false, false, true, true, NS_, W_><<<grid, 256, rlds, ctx->stream>>>(g1, g2, n1, n2, ncs, rider); break;
+            switch (tn_knob(TN_K_PAIR_DMA)) {
+                TN_PAIR_CASE(2, 6) TN_PAIR_CASE(2, 5) TN_PAIR_CASE(2, 4) TN_PAIR_CASE(4, 5) TN_PAIR_CASE(4, 4) TN_PAIR_CASE(4, 3)
+                TN_PAIR_CASE(8, 2)
+                default: return tn_fail(ctx, TN_E_ARG, "TN_PAIR_DMA: unknown variant %d", tn_knob(TN_K_PAIR_DMA));
+            }
+#undef TN_PAIR_CASE
+        } else
+            gemm_f32_pair<false, false, true, true, true, false><<<n1 + n2 + nrider, 256, rlds, ctx->stream>>>(
+                g1, g2, n1, n2, rider);
+        TN_LAUNCH_CHECK();
+        return fc_wgrad_sum(ctx, g1, Sx, dW, db);
     }
     int rc = tn_fc_wgrad(ctx, x, dz, dW, db, B, n_in, n_out, ws);
     if (rc) return rc;
@@ -1708,35 +1947,30 @@ int tn_fc_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int B, 
         return tn_bf_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
     if (route == FC_B3)
         return tn_b3_fc_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
-    if (route == FC_SKINNY)
+    GemmArgs g{};
+    const FcProd p = fc_dgrad_plan(ctx->num_cus, g, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
+    if (p.family == FCF_SKINNY)
         return tn_fc_skinny_dgrad(ctx, dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
-    if (route == FC_SCALAR) {
-        fc_skinny_dgrad_kernel<<<dim3(cdiv(n_in, 256), cdiv(B, 16)), 256, 0, ctx->stream>>>(
+    if (p.family == FCF_SCALAR) {
+        fc_skinny_dgrad_kernel<<<dim3(p.NT, p.MT), 256, 0, ctx->stream>>>(
             dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
-    GemmArgs g = fc_dgrad_args(dz, W, dx, B, n_in, n_out, prev_a, prev_act, prev_act_param, prev_mask);
-    const int S = fc_dgrad_splits(ctx, B, n_in, n_out);
-    if (S > 1) {
-        // few rows, a long reduction and a big weight matrix (wide6's 128 x 16384 <- 1024): a block per output
-        // tile is a long latency-bound chain over its 64 weight rows; S slabs of the reduction put S times
-        // as many blocks in flight, a finishing kernel adds them in order and applies act' * mask
+    if (p.finish) {
         const size_t MN = (size_t)B * n_in;
-        g.kchunk = cdiv(cdiv(n_out, S), BK) * BK;
-        const int Sx = cdiv(n_out, g.kchunk);
         float* ws;
-        int rc = tn_scratch_get(ctx, (size_t)Sx * MN * sizeof(float), &ws);
+        int rc = tn_scratch_get(ctx, (size_t)p.S * MN * sizeof(float), &ws);
         if (rc) return rc;
-        g.C = ws; g.epi = EPI_PLAIN; g.prev_a = nullptr; g.mask = nullptr;
-        launch_gemm<true, true, false>(ctx, g, Sx);
+        g.C = ws;
+        fc_launch(ctx, g, p);
         TN_LAUNCH_CHECK();
-        fc_dgrad_finish_kernel<<<cdiv(MN, 256), 256, 0, ctx->stream>>>(ws, Sx, MN, prev_a, prev_mask, dx, prev_act,
+        fc_dgrad_finish_kernel<<<cdiv(MN, 256), 256, 0, ctx->stream>>>(ws, p.S, MN, prev_a, prev_mask, dx, prev_act,
                                                                       prev_act_param);
         TN_LAUNCH_CHECK();
         return TN_OK;
     }
-    launch_gemm<true, true, false>(ctx, g, 1);
+    fc_launch(ctx, g, p);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }

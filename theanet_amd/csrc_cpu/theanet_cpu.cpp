@@ -563,6 +563,7 @@ int tn_fc_fwd_dropout(tn_ctx* ctx, const float* x, const float* W, const float* 
     if (rc) return rc;
     return tn_fc_fwd(ctx, x, W, b, a, B, n_in, n_out, act, prm, mask_out);
 }
+int tn_fc_plan(int, int, int, int, int, unsigned, int*, int) { return TN_E_ARG; }
 int tn_scale_mask(tn_ctx*, const float* x, const uint8_t* mask, float scale, float* y, size_t n, const float* prev_a,
                   int prev_act, float prm) {
 #pragma omp parallel for
