@@ -57,6 +57,22 @@ __device__ __forceinline__ float cm_shr(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x110 + N, 0xf, 0xf, false));
 }
 
+// the same with bound_ctrl: the lanes beyond the row's start read 0 -- no v_mov 0 into the destination first, and an
+// add in the same block may take the shift as its own DPP operand (x + 0.0 either way)
+template <int N>
+__device__ __forceinline__ float cm_shrz(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x110 + N, 0xf, 0xf, true));
+}
+
+// bit B of m ? v : +0.0 as bit-field extract (0 / -1) and AND: two instructions, no VCC (in assembly: the compiler
+// turns the builtin back into compare and select)
+template <int B>
+__device__ __forceinline__ float cm_bit_and(int m, float v) {
+    int s;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(s) : "v"(m), "n"(B));
+    return __int_as_float(s & __float_as_int(v));
+}
+
 // n / d for 0 <= n < 2^16 given rd = 1/d to 1 ulp (exact: (n + .5) / d stays >= .5/d away from
 // the next integer, far more than the rounding of the product)
 __device__ __forceinline__ int cm_div(int n, float rd) { return __float2int_rz(((float)n + .5f) * rd); }
@@ -431,20 +447,20 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     float* sx = wbase;                                // x tile (zero padded)
     float* sdx = sx + q.xf;                           // dx tile
     float* sdz = sdx + q.xf;                          // [4*KS2][npixp], pixels in window order
-    const int ZERO = q.xf - 4, ONE = q.xf - 3;        // constant cells behind the x tile
-    const int DUMMY = q.xf - 2;                       // write-only cell for out-of-range lanes
+    const int ZERO = q.xf - 4, ONE = q.xf - 2;        // constant cells behind the x tile, two of each: a lane that reads a
+                                                      // constant shares the live lanes' +1 offsets
 
     for (int i = threadIdx.x; i < 4 * q.PT; i += 256) {
         const int w = min(i, HpWp - 1);
         const int wy = w / q.Wp, wx = w - wy * q.Wp;
-        wtab[i] = 2 * wy * q.Wx + 2 * wx;
+        wtab[i] = (2 * wy * q.Wx + 2 * wx) * (W44 ? 4 : 1);          // (W44: in bytes)
     }
     // x tile: the pads stay zero for the whole kernel.  dz tile: the staging rewrites the cells of
     // the K x Hp*Wp windows for each image; everything else (tile padding, rows >= K) stays zero.
     for (int i = lane * 4; i < q.xf; i += 256) *reinterpret_cast<float4*>(sx + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = lane * 4; i < q.dzf + 4; i += 256) *reinterpret_cast<float4*>(sdz + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
-    if (lane == 0) sx[ONE] = 1.f;
+    if (lane < 2) sx[ONE + lane] = 1.f;
 
     // ---- loop-invariant operands ------------------------------------------------------------
     auto ckk_off = [&](int ckk) {
@@ -470,15 +486,34 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     constexpr int NM = (KS2 + 1) / 2;
     const int g2 = lane >> 5, a8 = (lane >> 2) & 7, r4 = lane & 3, g8 = lane >> 3, a2 = (lane >> 2) & 1;
     const int fM = 4 * a8 + r4, tM = lane & 31, tR = 32 + 4 * a2 + r4;
-    const int arowM = fM < K ? fM * q.npixp : q.dzf, amskM = fM < K ? -1 : 0;
-    const int offM = tM < CKK ? ckk_off(min(tM, CKK - 1)) : (tM == CKK ? ONE : ZERO), mskM = tM < CKK ? -1 : 0;
-    const int offR = tR < CKK ? ckk_off(min(tR, CKK - 1)) : (tR == CKK ? ONE : ZERO), mskR = tR < CKK ? -1 : 0;
-    int arowR[NM], amskR[NM];
+    // Every address of step Q (windows 2Q + g2) is a lane base fixed here plus, on the dz side, 8 floats a step, and on
+    // the x side a per-lane multiple of the window's table entry: 0 for a lane that reads a constant (columns >= C*9:
+    // the 1.0 / 0.0 cells).  In bytes.  The dz side needs no such lanes: the rows K .. 4 KS2 - 1 of the tile are zero,
+    // and a lane whose filter lies beyond them (block >= KS2 of the main product, block 1 of the last remainder
+    // register when KS2 is odd) is one whose A no instruction selects (CBSZ takes block ABID's A for the whole group,
+    // ABID < KS2: tools/probe/mfma44_cbsz.hip) -- it reads the tile's last row to stay inside the slice.
+    const int offM = tM < CKK ? ckk_off(min(tM, CKK - 1)) : (tM == CKK ? ONE : ZERO);
+    const int offR = tR < CKK ? ckk_off(min(tR, CKK - 1)) : (tR == CKK ? ONE : ZERO);
+    const int er4 = g8 & 3;                                                     // remainder product: the lane's pixel of its window
+    const char* const smb = reinterpret_cast<const char*>(sm);
+    const int sxo = 4 * (q.tabf + wv * q.wavef), sdzo = sxo + 8 * q.xf;         // the wave's x and dz tiles (bytes from sm)
+    constexpr bool ALLM = CKK >= 32;                                            // every main-product column is a tap
+    int oA = sdzo + 4 * (min(fM, 4 * KS2 - 1) * q.npixp + 4 * g2);              // walks 32 bytes a step, back after the image
+    const int oBt = sxo + 4 * offM;                                             // the window's top pixel pair, bottom pair
+    const int oBb = sxo + 4 * (offM + (tM < CKK ? q.Wx : 0));
+    const int mulM = tM < CKK ? 1 : 0;
+    const int oBR = sxo + 4 * (offR + (tR < CKK ? (er4 >> 1) * q.Wx + (er4 & 1) : 0));
+    int mulR = tR < CKK ? 1 : 0;
+    asm volatile("" : "+v"(mulR));      // (a multiplier to the compiler too: one multiply-add, not extract and select)
+    int oAR[NM];
 #pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        const int f = 8 * m + 4 * a2 + r4;
-        arowR[m] = f < K ? f * q.npixp : q.dzf;
-        amskR[m] = f < K ? -1 : 0;
+    for (int m = 0; m < NM; ++m)
+        oAR[m] = sdzo + 4 * (min(8 * m + 4 * a2 + r4, 4 * KS2 - 1) * q.npixp + 4 * g2 + er4);
+    const int oTab = 4 * g2;                                                    // the lane's window of step Q: entry 2Q + g2
+    if (W44) {      // whole addresses, one register each: the loop adds immediates
+        asm volatile("" : "+v"(oA));
+#pragma unroll
+        for (int m = 0; m < NM; ++m) asm volatile("" : "+v"(oAR[m]));
     }
     f32x4 accM[KS2], accR[KS2];
 #pragma unroll
@@ -492,7 +527,8 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
             const float v = W[((size_t)min(k, K - 1) * C + min(c, C - 1)) * FF + (FF - 1 - min(ab, FF - 1))];
             Aw2[mt][s] = (k < K && c < C && ab < FF) ? v : 0.f;
         }
-    int tabr[CM_XR];           // image element lane+64j -> offset in the x / dx tile
+    int tabr[CM_XR];           // image element lane+64j -> offset in the x / dx tile (the prefetch clamps alike: the
+                               // lanes beyond the image hold, and stage, the last element once more)
     int dzo[CM_XR];            // pooled element lane+64j = (k, window) -> its 4 dz cells
     const float rHW = __builtin_amdgcn_rcpf((float)HW), rWd = __builtin_amdgcn_rcpf((float)q.Wd);
     const float rHpWp = __builtin_amdgcn_rcpf((float)HpWp);
@@ -500,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     for (int j = 0; j < CM_XR; ++j) {
         const int i = min(lane + 64 * j, CHW - 1);
         const int c = cm_div(i, rHW), r = i - c * HW, yy = cm_div(r, rWd), xx = r - yy * q.Wd;
-        tabr[j] = (lane + 64 * j < CHW) ? c * q.xplane + (yy + q.pad) * q.Wx + xx + q.pad : DUMMY;
+        tabr[j] = c * q.xplane + (yy + q.pad) * q.Wx + xx + q.pad;      // lanes beyond C*H*W: the last element's cell
         const int e = min(lane + 64 * j, KHW - 1);
         const int k = cm_div(e, rHpWp), w = e - k * HpWp;
         dzo[j] = k * q.npixp + 4 * w;       // lanes beyond K*Hp*Wp rewrite the last element's cells
@@ -522,7 +558,8 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     const float tie = prm > 0.f ? 1.f + prm : 0.f;          // leaky slope at an exact 0
     // dgrad product column lo = tile column x': the dz pixel (y, x') in window order, or a zero cell
     const int dcol = lo < q.Wo ? 4 * (lo >> 1) + (lo & 1) : 16 * q.PT;
-    const int dmsk = lo < q.Wo ? -1 : 0;
+    const int oD = sdzo + 4 * (qd * q.npixp + dcol);        // ... of filter qd in window row 0 (bytes from sm)
+    const int incD = lo < q.Wo ? 16 * q.Wp : 0;             // bytes per window row
     for (; n < q.N; n += nw) {
         // ---- stage: x tile, and dz = mask bit ? g * act'(y) : 0 (branch-free, see tabr / dzo) ----
 #pragma unroll
@@ -538,61 +575,73 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
             }
             const float gy = gr[j] * gp;
             *reinterpret_cast<float4*>(sdz + dzo[j]) =
-                make_float4((m & 1) ? gy : 0.f, (m & 2) ? gy : 0.f, (m & 4) ? gy : 0.f, (m & 8) ? gy : 0.f);
+                make_float4(cm_bit_and<0>(m, gy), cm_bit_and<1>(m, gy), cm_bit_and<2>(m, gy), cm_bit_and<3>(m, gy));
         }
         if (n + nw < q.N) CM_PREFETCH(n + nw);
         cm_wave_sync();
         CM_STAMP();  // image staged
         if constexpr (W44) {
             // ---- wgrad on the 16-block MFMA: step Q = pooling windows 2Q and 2Q + 1 (8 pixels) ----
-            float4 a4c;
-            float b4c[4], arc[NM], brc = 0.f;
-#define CM_W4_LOAD(Q_, A_, B_, AR_, BR_)                                                    \
-            {                                                                               \
-                const int w_ = 2 * (Q_) + g2, wo_ = wtab[w_];                               \
-                A_ = *reinterpret_cast<const float4*>(sdz + arowM + ((4 * w_) & amskM));    \
-                _Pragma("unroll") for (int r = 0; r < 4; ++r)                               \
-                    B_[r] = sx[offM + ((wo_ + (r >> 1) * q.Wx + (r & 1)) & mskM)];          \
-                if (REM) {                                                                  \
-                    const int wr_ = 2 * (Q_) + (g8 >> 2), er_ = g8 & 3;                     \
-                    _Pragma("unroll") for (int m = 0; m < NM; ++m)                          \
-                        AR_[m] = sdz[arowR[m] + ((4 * wr_ + er_) & amskR[m])];              \
-                    BR_ = sx[offR + ((wtab[wr_] + (er_ >> 1) * q.Wx + (er_ & 1)) & mskR)];  \
-                }                                                                           \
+            // Two steps per trip (2 PT is even) on two operand sets, each loaded during the other's products; a
+            // window's table entry is read one step before the loads that need it, behind a step's products too.
+            float4 a4[2];
+            float b4[2][4], ar[2][NM], br[2] = {0.f, 0.f};
+#define CM_W4_TAB(Q_) (*reinterpret_cast<const int*>(smb + oTab + 8 * (Q_)))
+#define CM_W4_LOAD(OFF_, S_, WO_)                                                                           \
+            {                                                                                               \
+                a4[S_] = *reinterpret_cast<const float4*>(smb + oA + (OFF_));                               \
+                const int wm_ = ALLM ? (WO_) : __mul24((WO_), mulM);                                        \
+                const float* t_ = reinterpret_cast<const float*>(smb + oBt + wm_);                          \
+                const float* u_ = reinterpret_cast<const float*>(smb + oBb + wm_);                          \
+                b4[S_][0] = t_[0]; b4[S_][1] = t_[1]; b4[S_][2] = u_[0]; b4[S_][3] = u_[1];                 \
+                if (REM) {                                                                                  \
+                    _Pragma("unroll") for (int m = 0; m < NM; ++m)                                          \
+                        ar[S_][m] = *reinterpret_cast<const float*>(smb + oAR[m] + (OFF_));                 \
+                    br[S_] = *reinterpret_cast<const float*>(smb + oBR + __mul24((WO_), mulR));             \
+                }                                                                                           \
             }
-            CM_W4_LOAD(0, a4c, b4c, arc, brc);
+#define CM_M4(S_, AB) if (AB < KS2) accM[AB < KS2 ? AB : 0] = __builtin_amdgcn_mfma_f32_4x4x1f32(a_, b4[S_][s_], accM[AB < KS2 ? AB : 0], 3, AB, 0);
+#define CM_W4_PRODUCTS(S_)                                                                                  \
+            if (!nowg) {                                                                                    \
+                _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) {                                          \
+                    const float a_ = s_ == 0 ? a4[S_].x : s_ == 1 ? a4[S_].y : s_ == 2 ? a4[S_].z : a4[S_].w; \
+                    CM_M4(S_, 0) CM_M4(S_, 1) CM_M4(S_, 2) CM_M4(S_, 3) CM_M4(S_, 4) CM_M4(S_, 5) CM_M4(S_, 6) CM_M4(S_, 7) \
+                }                                                                                           \
+                if (REM) {                                                                                  \
+                    _Pragma("unroll") for (int m = 0; m < NM; ++m) {                                        \
+                        accR[2 * m] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[S_][m], br[S_], accR[2 * m], 1, 0, 0); \
+                        if (2 * m + 1 < KS2)                                                                \
+                            accR[2 * m + 1 < KS2 ? 2 * m + 1 : 0] = __builtin_amdgcn_mfma_f32_4x4x1f32(     \
+                                ar[S_][m], br[S_], accR[2 * m + 1 < KS2 ? 2 * m + 1 : 0], 1, 1, 0);         \
+                    }                                                                                       \
+                }                                                                                           \
+            }
+            // The dz side walks on past the last step by one (its table entry is the last step's again): 8 floats
+            // further in a row are its padding and the next row's first window, or the zero cells behind the tile.
+            const int QL = 2 * q.PT - 1;            // the last step (odd)
+            const int nowg = __builtin_amdgcn_readfirstlane(q.dbg & 1);
+            int woE = CM_W4_TAB(0), woO = CM_W4_TAB(1);
+            CM_W4_LOAD(0, 0, woE);
+            woE = CM_W4_TAB(min(2, QL));
 #pragma unroll 1
-            for (int Q = 0; Q < 2 * q.PT; ++Q) {
-                float4 a4n;
-                float b4n[4], arn[NM], brn = 0.f;
-                const int Qn = min(Q + 1, 2 * q.PT - 1);
-                CM_W4_LOAD(Qn, a4n, b4n, arn, brn);     // next step's operands travel during this step's products
-                if (!(q.dbg & 1)) {
-#define CM_M4(AB) if (AB < KS2) accM[AB < KS2 ? AB : 0] = __builtin_amdgcn_mfma_f32_4x4x1f32(a_, b4c[s_], accM[AB < KS2 ? AB : 0], 3, AB, 0);
+            for (int Q = 0; Q < QL; Q += 2) {
+                CM_W4_LOAD(32, 1, woO);
+                woO = CM_W4_TAB(min(Q + 3, QL));
+                CM_W4_PRODUCTS(0);
+                CM_W4_LOAD(64, 0, woE);
+                woE = CM_W4_TAB(min(Q + 4, QL));
+                CM_W4_PRODUCTS(1);
+                oA += 64;
 #pragma unroll
-                    for (int s_ = 0; s_ < 4; ++s_) {
-                        const float a_ = s_ == 0 ? a4c.x : s_ == 1 ? a4c.y : s_ == 2 ? a4c.z : a4c.w;
-                        CM_M4(0) CM_M4(1) CM_M4(2) CM_M4(3) CM_M4(4) CM_M4(5) CM_M4(6) CM_M4(7)
-                    }
-#undef CM_M4
-                    if (REM) {
-#pragma unroll
-                        for (int m = 0; m < NM; ++m) {
-                            accR[2 * m] = __builtin_amdgcn_mfma_f32_4x4x1f32(arc[m], brc, accR[2 * m], 1, 0, 0);
-                            if (2 * m + 1 < KS2)
-                                accR[2 * m + 1 < KS2 ? 2 * m + 1 : 0] = __builtin_amdgcn_mfma_f32_4x4x1f32(
-                                    arc[m], brc, accR[2 * m + 1 < KS2 ? 2 * m + 1 : 0], 1, 1, 0);
-                        }
-                    }
-                }
-                a4c = a4n;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) b4c[r] = b4n[r];
-#pragma unroll
-                for (int m = 0; m < NM; ++m) arc[m] = arn[m];
-                brc = brn;
+                for (int m = 0; m < NM; ++m) oAR[m] += 64;
             }
+            oA -= 64 * q.PT;
+#pragma unroll
+            for (int m = 0; m < NM; ++m) oAR[m] -= 64 * q.PT;
+#undef CM_W4_PRODUCTS
+#undef CM_M4
 #undef CM_W4_LOAD
+#undef CM_W4_TAB
         } else {
         // ---- wgrad: dWf[k][ckk] += sum_pix dz[k][pix] * patch[pix][ckk] -------------------------
         float4 ac[NKT];
@@ -642,51 +691,67 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
             float R1 = 0.f, R2 = 0.f;
             float* dxo = sdx + qd * q.xplane + lo;
             const bool dlive = (qd < C) && (lo < q.Wo + 2);
-            float bcur[KS2];
-            {
-                const float* dzp = sdz + qd * q.npixp + dcol;
-#pragma unroll
-                for (int s = 0; s < KS2; ++s) bcur[s] = dzp[4 * s * q.npixp];
+            // Two rows per trip on two operand sets: rows 2t and 2t + 1 are the two pixel rows of window row t, 2 floats
+            // apart (the zero cells of a lane beyond the map's width are four), so one address per filter quad and
+            // trip (oD + t * incD) serves both.  The sums per row and their order are those of the one-row loop.
+            float bE[KS2], bO[KS2];
+#define CM_DG_LOAD(B_, T_, OFF_)                                                                            \
+            {                                                                                               \
+                const char* p_ = smb + oD + __mul24((T_), incD) + (OFF_);                                   \
+                _Pragma("unroll") for (int s = 0; s < KS2; ++s)                                             \
+                    B_[s] = *reinterpret_cast<const float*>(p_ + s * (16 * q.npixp));                       \
             }
+#define CM_DG_ROW(B_, YY_)                                                                                  \
+            {                                                                                               \
+                f32x4 T[NTD];                                                                               \
+                _Pragma("unroll") for (int mt = 0; mt < NTD; ++mt) T[mt] = f32x4{0.f, 0.f, 0.f, 0.f};       \
+                _Pragma("unroll") for (int s = 0; s < KS2; ++s)                                             \
+                    _Pragma("unroll") for (int mt = 0; mt < NTD; ++mt) T[mt] = cm_mfma(Aw2[mt][s], B_[s], T[mt]); \
+                const float S0 = T[0][0] + cm_shrz<1>(T[0][1]) + cm_shrz<2>(T[0][2]);                       \
+                const float S1 = T[0][3] + cm_shrz<1>(T[1][0]) + cm_shrz<2>(T[1][1]);                       \
+                const float S2 = T[1][2] + cm_shrz<1>(T[1][3]) + cm_shrz<2>(T[2][0]);                       \
+                const float out = S0 + R1;                                                                  \
+                R1 = S1 + R2;                                                                               \
+                R2 = S2;                                                                                    \
+                if (dlive) dxo[(YY_) * q.Wx] = out;                                                         \
+            }
+            const int TL = (q.Ho - 1) >> 1;         // the last window row
+            CM_DG_LOAD(bE, 0, 0);
 #pragma unroll 1
-            for (int yy = 0; yy < q.Ho; ++yy) {
-                const int yn = min(yy + 1, q.Ho - 1);
-                const int prow = 4 * (yn >> 1) * q.Wp + 2 * (yn & 1);
-                const float* dzp = sdz + qd * q.npixp + dcol + (prow & dmsk);
-                float bnxt[KS2];
-#pragma unroll
-                for (int s = 0; s < KS2; ++s) bnxt[s] = dzp[4 * s * q.npixp];
-                f32x4 T[NTD];
-#pragma unroll
-                for (int mt = 0; mt < NTD; ++mt) T[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < KS2; ++s)
-#pragma unroll
-                    for (int mt = 0; mt < NTD; ++mt) T[mt] = cm_mfma(Aw2[mt][s], bcur[s], T[mt]);
-#pragma unroll
-                for (int s = 0; s < KS2; ++s) bcur[s] = bnxt[s];
-                const float S0 = T[0][0] + cm_shr<1>(T[0][1]) + cm_shr<2>(T[0][2]);
-                const float S1 = T[0][3] + cm_shr<1>(T[1][0]) + cm_shr<2>(T[1][1]);
-                const float S2 = T[1][2] + cm_shr<1>(T[1][3]) + cm_shr<2>(T[2][0]);
-                const float out = S0 + R1;
-                R1 = S1 + R2;
-                R2 = S2;
-                if (dlive) dxo[yy * q.Wx] = out;
+            for (int t = 0; t < (q.Ho >> 1); ++t) {
+                CM_DG_LOAD(bO, t, 8);
+                __builtin_amdgcn_sched_barrier(0);      // the reads go out ahead of the row's products, not behind them
+                CM_DG_ROW(bE, 2 * t);
+                CM_DG_LOAD(bE, min(t + 1, TL), 0);
+                __builtin_amdgcn_sched_barrier(0);
+                CM_DG_ROW(bO, 2 * t + 1);
             }
+            if (q.Ho & 1) CM_DG_ROW(bE, q.Ho - 1);
+#undef CM_DG_ROW
+#undef CM_DG_LOAD
             if (dlive) {
                 dxo[q.Ho * q.Wx] = R1;
                 dxo[(q.Ho + 1) * q.Wx] = R2;
             }
             cm_wave_sync();
+            CM_STAMP();  // dgrad rows done
+            // copy-out: every read of the tile first (lanes beyond the image read the last element's cell), then the stores:
+            // one LDS latency per image, not one per store.  (A wave-uniform test for the whole groups of 64 buys
+            // nothing: the compiler folds it back into the per-lane one, whose stores already run straight through.)
             float* dxp = dx + (size_t)n * CHW;
+            float dv[CM_XR];
+#pragma unroll
+            for (int j = 0; j < CM_XR; ++j) dv[j] = sdx[tabr[j]];
+#pragma unroll
+            for (int j = 0; j < CM_XR; ++j) asm volatile("" : "+v"(dv[j]));     // (keeps the reads out of the tests below)
 #pragma unroll
             for (int j = 0; j < CM_XR; ++j) {
                 const int i = lane + 64 * j;
-                if (i < CHW) dxp[i] = sdx[tabr[j]];
+                if (i < CHW) dxp[i] = dv[j];
             }
         }
         cm_wave_sync();
-        CM_STAMP();  // dgrad done
+        CM_STAMP();  // copy-out done
     }
 #undef CM_PREFETCH
     // ---- one partial slab per block: sum the 4 waves' accumulators in wave order ---------------
