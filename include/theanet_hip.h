@@ -791,6 +791,47 @@ int tn_elastic_apply_bwd(tn_ctx* ctx, const float* g, float* dx, int N, int C, i
                          const uint8_t* flipmask, uint64_t seed, uint32_t step, const uint32_t* d_step,
                          int64_t row_global0, const float* prev_a, int prev_act, float prev_act_param);
 
+/* ---- ElasticLayer per_image: a distortion field for EVERY image of the minibatch (theanet_amd/csrc/elastic_img.hip) ----
+ * The reference draws one coordinate field per call and shares it among the images of the minibatch
+ * (inlayers.py:77-127); with per_image every image n gets its own draws -- translation (2), origin (2), zoom (2),
+ * theta (1) and the two N(0,1) noise planes of h*w values: the draws layout above, once per image -- and its field is
+ * the reference's chain applied to them: translate, smoothed displacement, un-centre, zoom, rotate, re-centre, clip,
+ * nearest / bilinear resample.  All channels of an image share its field; inversion and flip noise are
+ * tn_elastic_apply's (same keying of the flip draws).
+ *   Draws.  draws_in (N x tn_elastic_draws_count(h, w) floats) injects them; NULL: image n's element i comes from
+ * Philox(seed; counter = (i / 4, row_global0 + n, step + *d_step, stream 7)) -- a stream of its own, so a per-image draw
+ * never coincides with the batch field's (stream 3) -- through the forms of tn_elastic_draws (header uniforms of one word,
+ * both Box-Muller outputs of the word pairs (x, y) and (z, w) for the noise).  They depend on the seed, the step counter,
+ * the GLOBAL index of the image in the minibatch and the element only: not on N, the shard or the schedule.
+ *   Smoothing.  The separable form of the reference's filter: g[i] = fl32(exp(-i^2 / (2 sigma^2)) / sqrt(2 pi sigma^2)),
+ * i = -sigma .. sigma; a row pass then a column pass over el = fl32(magnitude * noise), zero beyond the borders, fp32
+ * fused multiply-adds in ascending tap order.  Mathematically elastic_filter's 'full' convolution cropped; not
+ * bit-identical to tn_elastic_field's 2-D sum with fp64 accumulation: per pixel the two differ by at most about
+ * 2 (2 sigma + 1) 2^-23 (|el| * filter) (tests/test_gpu_elastic_img.py bounds it).
+ *   Coordinates.  From the addition of the smoothed displacement on, the float64 chain of tn_elastic_field: origin,
+ * zoom as exp(log(zoom) u), rotation as R^T, clip at h - 1 - .001, rint for nearest, truncation + fractions for bilinear.
+ *   target (N x 2 x h x w doubles, may be NULL) receives the un-clipped coordinates and draws_out (layout of draws_in,
+ * may be NULL) the draws used: both exist for tests and debugging, training passes NULL.  No sample map is written.
+ *   tn_elastic_img_supported: C >= 1, h, w >= 2, sigma >= 0 and one block's LDS -- 4 doubles + (4 h (w | 1) +
+ * 2 sigma + 2 + 8) floats: two noise planes and two temporaries at an odd pitch, the 1-D filter (padded to even),
+ * the header -- within the CU's 160 KiB (64 x 64, sigma 32: 66 888 bytes, above the 64 KiB a launch gets by default: the
+ * entry points raise the kernel's limit).  True at least for every h = w <= 64, C <= 4, sigma <= 32.
+ *   tn_c8_elastic_apply_img: the same with the c8 tensor of the first conv layer as output ([N][ceil(C/8)][h*w][8], element
+ * type of the context, zero beyond C), under tn_c8_elastic_apply's condition ((h*w) % 4 == 0, unpadded maps, 16-byte
+ * aligned output); it stores exactly the rounded value of what tn_elastic_apply_img computes.
+ *   Unsupported shapes, NULL x / out, N < 1, zoom <= 0 or magnitude != 0 with sigma == 0: TN_E_ARG, nothing launched.  */
+int tn_elastic_img_supported(int C, int h, int w, int sigma);
+int tn_elastic_apply_img(tn_ctx* ctx, const float* x, int64_t x_row0, const int64_t* d_row0, float* out, int N, int C,
+                         int h, int w, int invert, int nearest, double translation, double zoom, double magnitude,
+                         int sigma, double angle, float pflip, const uint8_t* flipmask, uint64_t seed, uint32_t step,
+                         const uint32_t* d_step, int64_t row_global0, const float* draws_in, float* draws_out,
+                         double* target);
+int tn_c8_elastic_apply_img(tn_ctx* ctx, const float* x, int64_t x_row0, const int64_t* d_row0, void* out16, int N, int C,
+                            int h, int w, int invert, int nearest, double translation, double zoom, double magnitude,
+                            int sigma, double angle, float pflip, const uint8_t* flipmask, uint64_t seed, uint32_t step,
+                            const uint32_t* d_step, int64_t row_global0, const float* draws_in, float* draws_out,
+                            double* target);
+
 /* ---- ColorLayer (replaces color.py:9-52) ----
  * fac[(n*C+c)*3 + k] = exp(ln(balance|gamma|gamma) * u_k), u_k ~ U(-1,1): three random variables of shape
  * (N, C).  draws (float32, [3][N][C]) injects the uniforms (parity runs); NULL -> Philox(seed, step + *d_step,

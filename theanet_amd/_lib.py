@@ -197,6 +197,13 @@ SIGNATURES = {
                                     P, P, P, c_float, P, c_uint64, c_uint32, P, c_int64]),
     "tn_elastic_apply_bwd": (c_int, [CTX, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_float, P,
                                      c_uint64, c_uint32, P, c_int64, P, c_int, c_float]),
+    "tn_elastic_img_supported": (c_int, [c_int] * 4),
+    "tn_elastic_apply_img": (c_int, [CTX, P, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_double, c_double, c_double, c_int, c_double, c_float, P, c_uint64, c_uint32, P,
+                                     c_int64, P, P, P]),
+    "tn_c8_elastic_apply_img": (c_int, [CTX, P, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_double, c_double, c_double, c_int, c_double, c_float, P, c_uint64, c_uint32, P,
+                                        c_int64, P, P, P]),
     "tn_color_factors": (c_int, [CTX, P, c_int, c_int, c_double, c_double, P, c_uint64, c_uint32, P, c_int64]),
     "tn_color_apply": (c_int, [CTX, P, c_int64, P, P, c_int, c_int, c_int, c_float]),
     "tn_color_apply_bwd": (c_int, [CTX, P, c_int64, P, P, P, c_int, c_int, c_int, c_float, P, c_int, c_float]),

@@ -1171,6 +1171,157 @@ int tn_elastic_apply_bwd(tn_ctx* ctx, const float* g, float* dx, int N, int C, i
     return TN_OK;
 }
 
+// ---- ElasticLayer per_image: a field for every image (csrc/elastic_img.hip: same Philox keying, same operation order) ----
+enum { STREAM_ELASTIC_IMG = 7 };
+int tn_elastic_img_supported(int C, int h, int w, int sigma) {
+    if (C < 1 || h < 2 || w < 2 || sigma < 0 || h > 4096 || w > 4096 || sigma > 4096) return 0;
+    // the HIP kernel's LDS: 4 doubles + (4 h (w | 1) + 2 sigma + 2 + 8) floats within 160 KiB -- the same answer here
+    return 4 * sizeof(double) + ((size_t)4 * h * (w | 1) + (size_t)(2 * sigma + 2) + EL_HDR) * sizeof(float) <= 160 * 1024;
+}
+static void elastic_img_draw4(int q, uint32_t img, uint32_t st, uint64_t seed, float v[4]) {
+    const u32x4 r = philox4x32((uint32_t)q, img, st, STREAM_ELASTIC_IMG, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t wd[4] = {r.x, r.y, r.z, r.w};
+    if (4 * q < EL_HDR) {
+        for (int e = 0; e < 4; ++e) {
+            const int i = 4 * q + e;
+            const float u = u01(wd[e]);
+            v[e] = (i == 2 || i == 3) ? .25f + .5f * u : -1.f + 2.f * u;
+        }
+        return;
+    }
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = ((wd[2 * h] >> 8) + 1) * (1.0f / 16777216.0f);
+        const float a = 6.28318530717958647692f * u01(wd[2 * h + 1]);
+        const float rad = std::sqrt(-2.f * std::log(u1));
+        v[2 * h] = rad * std::cos(a);
+        v[2 * h + 1] = rad * std::sin(a);
+    }
+}
+// out[i] = sum_t g[t] * (scale * line[(i + t - sigma) * stride]), zero outside [0, n): ascending taps, fused multiply-adds
+static void elastic_img_pass(const float* line, int stride, int n, const float* g, int sigma, float scale, float* out, int ostride) {
+    for (int i = 0; i < n; ++i) {
+        float acc = 0.f;
+        for (int t = 0; t <= 2 * sigma; ++t) {
+            const int k = i + t - sigma;
+            const float v = (k >= 0 && k < n) ? scale * line[(size_t)k * stride] : 0.f;
+            acc = std::fmaf(g[t], v, acc);
+        }
+        out[(size_t)i * ostride] = acc;
+    }
+}
+int tn_elastic_apply_img(tn_ctx* ctx, const float* x, int64_t x_row0, const int64_t* d_row0, float* out, int N, int C,
+                         int h, int w, int invert, int nearest, double translation, double zoom, double magnitude,
+                         int sigma, double angle, float pflip, const uint8_t* flipmask, uint64_t seed, uint32_t step,
+                         const uint32_t* d_step, int64_t row_global0, const float* draws_in, float* draws_out,
+                         double* target) {
+    REQUIRE(N > 0 && x && out, "tn_elastic_apply_img: bad arguments");
+    REQUIRE(tn_elastic_img_supported(C, h, w, sigma), "tn_elastic_apply_img: %d maps of %d x %d, sigma %d: not supported "
+            "(tn_elastic_img_supported)", C, h, w, sigma);
+    REQUIRE(zoom > 0 && (magnitude == 0.0 || sigma >= 1), "tn_elastic_apply_img: zoom %g / sigma %d with magnitude %g", zoom,
+            sigma, magnitude);
+    const int hw = h * w, total = EL_HDR + 2 * hw, ks = 2 * sigma + 1;
+    const int64_t row_off = x_row0 + (d_row0 ? *d_row0 : 0);
+    const uint32_t st = step + (d_step ? *d_step : 0u);
+    const bool smooth = magnitude != 0.0, affine = zoom != 1.0 || angle != 0.0;
+    std::vector<float> g((size_t)ks, 0.f);
+    if (smooth) {
+        const double var = (double)sigma * sigma;
+        for (int t = 0; t < ks; ++t) {
+            const double i = t - sigma;
+            g[t] = (float)(std::exp(-.5 * i * i / var) / std::sqrt(2.0 * 3.14159265358979323846 * var));
+        }
+    }
+#pragma omp parallel
+    {
+        std::vector<float> d((size_t)total), tmp((size_t)2 * hw), sm((size_t)2 * hw);
+#pragma omp for
+        for (int n = 0; n < N; ++n) {
+            if (draws_in) {
+                std::memcpy(d.data(), draws_in + (size_t)n * total, sizeof(float) * total);
+            } else {
+                for (int q = 0; 4 * q < total; ++q) {
+                    float v[4];
+                    elastic_img_draw4(q, (uint32_t)(row_global0 + n), st, seed, v);
+                    for (int e = 0; e < 4 && 4 * q + e < total; ++e) d[4 * q + e] = v[e];
+                }
+            }
+            if (draws_out) std::memcpy(draws_out + (size_t)n * total, d.data(), sizeof(float) * total);
+            if (smooth) {
+                for (int pl = 0; pl < 2; ++pl) {
+                    const float* nz = d.data() + EL_HDR + (size_t)pl * hw;
+                    for (int y = 0; y < h; ++y)      // row pass over el = fl32(mag * noise)
+                        elastic_img_pass(nz + (size_t)y * w, 1, w, g.data(), sigma, (float)magnitude, tmp.data() + (size_t)pl * hw + (size_t)y * w, 1);
+                    for (int xx = 0; xx < w; ++xx)   // column pass
+                        elastic_img_pass(tmp.data() + (size_t)pl * hw + xx, w, h, g.data(), sigma, 1.f, sm.data() + (size_t)pl * hw + xx, w);
+                }
+            }
+            double zy = 1.0, zx = 1.0, cs = 1.0, sn = 0.0;
+            if (zoom != 1.0) { zy = std::exp(std::log(zoom) * (double)d[4]); zx = std::exp(std::log(zoom) * (double)d[5]); }
+            if (angle != 0.0) {
+                const double theta = (angle * 3.14159265358979323846 / 180.0) * (double)d[6];
+                cs = std::cos(theta); sn = std::sin(theta);
+            }
+            const float* xn = x + (size_t)(row_off + n) * C * hw;
+            for (int p = 0; p < hw; ++p) {
+                const int y = p / w, xx = p - y * w;
+                double ty = y, tx = xx;
+                if (translation != 0.0) {
+                    ty += (double)((float)translation * d[0]);
+                    tx += (double)((float)translation * d[1]);
+                }
+                if (smooth) { ty += (double)sm[p]; tx += (double)sm[hw + p]; }
+                if (affine) {
+                    const double oy = (double)d[2] * h, ox = (double)d[3] * w;
+                    ty -= oy; tx -= ox;
+                    if (zoom != 1.0) { ty *= zy; tx *= zx; }
+                    if (angle != 0.0) {               // tensordot(R, target, axes=(0,0)), R=[[c,-s],[s,c]] -> R^T applied
+                        const double ry = cs * ty + sn * tx, rx = -sn * ty + cs * tx;
+                        ty = ry; tx = rx;
+                    }
+                    ty += oy; tx += ox;
+                }
+                if (target) { target[((size_t)n * 2) * hw + p] = ty; target[((size_t)n * 2 + 1) * hw + p] = tx; }
+                const double cy = std::fmin(std::fmax(ty, 0.0), (double)h - 1 - .001);
+                const double cx = std::fmin(std::fmax(tx, 0.0), (double)w - 1 - .001);
+                int m;
+                float fy = 0.f, fx = 0.f;
+                if (nearest) {
+                    m = (int)std::rint(cy) * w + (int)std::rint(cx);
+                } else {
+                    const int top = (int)cy, left = (int)cx;
+                    m = top * w + left;
+                    fy = (float)(cy - top); fx = (float)(cx - left);
+                }
+                for (int c = 0; c < C; ++c) {
+                    const float* xi = xn + (size_t)c * hw;
+                    float v;
+                    if (nearest) {
+                        v = xi[m];
+                        if (invert) v = 1.f - v;
+                    } else {
+                        float a = xi[m], b = xi[m + 1], cc = xi[m + w], dd = xi[m + w + 1];
+                        if (invert) { a = 1.f - a; b = 1.f - b; cc = 1.f - cc; dd = 1.f - dd; }
+                        v = a * (1.f - fy) * (1.f - fx) + b * (1.f - fy) * fx + cc * fy * (1.f - fx) + dd * fy * fx;   // inlayers.py:134-137
+                    }
+                    const uint64_t t = ((uint64_t)n * C + c) * hw + p;
+                    if (flipmask) {
+                        if (flipmask[t]) v = 1.f - v;
+                    } else if (pflip > 0.f) {
+                        if (u01(philox_word((uint64_t)row_global0 * C * hw + t, st, STREAM_FLIP, seed)) < pflip) v = 1.f - v;
+                    }
+                    out[t] = v;
+                }
+            }
+        }
+    }
+    return TN_OK;
+}
+int tn_c8_elastic_apply_img(tn_ctx* ctx, const float*, int64_t, const int64_t*, void*, int, int, int, int, int, int, double, double,
+                            double, int, double, float, const uint8_t*, uint64_t, uint32_t, const uint32_t*, int64_t, const float*,
+                            float*, double*) {
+    NOT_HERE("tn_c8_elastic_apply_img");
+}
+
 // ---- ColorLayer (color.py:9-52) ----
 int tn_color_factors(tn_ctx* ctx, float* fac, int N, int C, double balance, double gamma, const float* draws,
                      uint64_t seed, uint32_t step, const uint32_t* d_step, int64_t row_global0) {

@@ -3,8 +3,9 @@
 ``InputLayer`` passes the minibatch through; ``ElasticLayer`` is the in-graph
 augmentation stage: invert -> one random coordinate field per CALL (translation,
 gaussian-smoothed elastic displacement, zoom, rotation; shared by every image and
-channel of the batch) -> clip -> nearest/bilinear resample -> pixel-flip noise
-(:63-144).  The field is built on the device in float64 from a small vector of
+channel of the batch; ``per_image=True``: one field per IMAGE, keyed by the image's global index in
+the minibatch -- include/theanet_hip.h, tn_elastic_apply_img) -> clip -> nearest/bilinear resample ->
+pixel-flip noise (:63-144).  The field is built on the device in float64 from a small vector of
 random draws which either comes from the on-device Philox generator or is
 injected by a parity test (``inject``).  The test version is identity + invert
 (:157-163).
@@ -72,7 +73,8 @@ class ElasticLayer(Layer):
                  angle=0,
                  rand_gen=None,
                  invert_image=False,
-                 nearest=False):
+                 nearest=False,
+                 per_image=False):
         self.inpt = inpt
         self.img_sz = img_sz
         self.translation = translation
@@ -83,6 +85,7 @@ class ElasticLayer(Layer):
         self.angle = angle
         self.invert = invert_image
         self.nearest = nearest
+        self.per_image = bool(per_image)
 
         self.out_sz = img_sz
         self.num_maps = num_maps
@@ -96,6 +99,8 @@ class ElasticLayer(Layer):
             translation, zoom, magnitude, sigma,
             pflip, angle, invert_image,
             'Nearest' if nearest else 'Linear'))
+        if self.per_image:
+            self.representation += ' Fields:PerImage'
 
         from ..device import get_context
         self.ctx = ctx = get_context()
@@ -104,7 +109,11 @@ class ElasticLayer(Layer):
 
         assert zoom > 0
         self.active = bool(magnitude or translation or pflip or angle) or zoom != 1
-        self.has_field = bool(magnitude or translation or angle) or zoom != 1
+        field = bool(magnitude or translation or angle) or zoom != 1
+        # per_image: every image its own field, built inside the resampling launch (tn_elastic_apply_img) -- the layer has
+        # no batch field: no sample maps, nothing for the step to build ahead (NeuralNet._train_step), no fused conv block
+        self.img_field = self.per_image and field
+        self.has_field = field and not self.img_field
         self.d_step = None
         self._inj_draws = False
         self._inj_flip = None
@@ -118,6 +127,15 @@ class ElasticLayer(Layer):
             else int(np.random.randint(0, 1e6))
         h = w = img_sz
         n_draws = ctx.lib.tn_elastic_draws_count(h, w)
+        if self.img_field:
+            if not ctx.lib.tn_elastic_img_supported(num_maps, h, w, int(sigma)):
+                raise ValueError("ElasticLayer per_image: %d maps of %d x %d with sigma %d do not fit the per-image kernel "
+                                 "(tn_elastic_img_supported: one block's LDS holds four planes of the image and the filter)"
+                                 % (num_maps, h, w, sigma))
+            if magnitude and int(sigma) < 1:
+                raise ValueError("ElasticLayer per_image: a magnitude needs sigma >= 1 (the filter's width)")
+            self.draws = None           # injected draws: (batch, n_draws), allocated by inject()
+            return
         self.draws = ctx.zeros((n_draws,))
         # two sample maps: while the minibatch of step t is resampled through one, the field of
         # step t+1 (it depends only on the step counter) is built into the other by a rider of the
@@ -137,6 +155,25 @@ class ElasticLayer(Layer):
                             invert_image=self.invert,
                             nearest=self.nearest)
 
+    def _inject_img(self, transln, noise, origin_u, zoom_u, theta_u):
+        """per_image: arrays with a leading batch axis -- transln / origin_u / zoom_u (N, 2), theta_u (N,), noise (N, 2, h, w)."""
+        N, hw = self.batch_sz, self.img_sz * self.img_sz
+        d = np.zeros((N, 8 + 2 * hw), np.float32)
+        if transln is not None:
+            d[:, 0:2] = np.asarray(transln, np.float32).reshape(N, 2)
+        if origin_u is not None:
+            d[:, 2:4] = np.asarray(origin_u, np.float32).reshape(N, 2)
+        if zoom_u is not None:
+            d[:, 4:6] = np.asarray(zoom_u, np.float32).reshape(N, 2)
+        if theta_u is not None:
+            d[:, 6] = np.asarray(theta_u, np.float32).reshape(N)
+        if noise is not None:
+            d[:, 8:] = np.asarray(noise, np.float32).reshape(N, 2 * hw)
+        if self.draws is None:
+            self.draws = self.ctx.empty(d.shape)
+        self.draws.set_value(d)
+        self._inj_draws = True
+
     # -- parity hooks -----------------------------------------------------------------
     def inject(self, transln=None, noise=None, origin_u=None, zoom_u=None, theta_u=None,
                flipmask=None):
@@ -146,6 +183,13 @@ class ElasticLayer(Layer):
             self._inj_draws, self._inj_flip = False, None
             return
         h = w = self.img_sz
+        if self.img_field:
+            if any(v is not None for v in (transln, noise, origin_u, zoom_u, theta_u)):
+                self._inject_img(transln, noise, origin_u, zoom_u, theta_u)
+            if flipmask is not None:
+                self._inj_flip = self.ctx.array(
+                    np.asarray(flipmask).reshape(self.output.shape).astype(np.uint8))
+            return
         d = np.zeros(self.draws.size, np.float32)
         if transln is not None:
             d[0:2] = np.asarray(transln, np.float32).reshape(2)
@@ -171,6 +215,8 @@ class ElasticLayer(Layer):
             x_ptr, row0, d_row0, rg0 = s.data.ptr, int(s.row0), s.d_row0, int(s.row_global0)
         else:       # mid-net elastic layer (neuralnet.py:132-142): plain device tensor
             x_ptr, row0, d_row0, rg0 = s.ptr, 0, None, 0
+            if self.img_field:      # the image's index in the GLOBAL minibatch: this rank's rows start at shard_lo
+                rg0 = int(getattr(self, "shard_lo", 0))
         h = w = self.img_sz
         d_row0_ptr = d_row0.ptr if d_row0 is not None else None
         if not self.active:
@@ -179,6 +225,16 @@ class ElasticLayer(Layer):
                           None, None, None, 0.0, None, 0, 0, None, rg0)
             return
         d_step_ptr = self.d_step.ptr if self.d_step is not None else None
+        if self.img_field:
+            c8 = self._c8_consumer is not None
+            self.ctx.call("tn_c8_elastic_apply_img" if c8 else "tn_elastic_apply_img", x_ptr, row0, d_row0_ptr,
+                          self._c8_consumer.x16.ptr if c8 else self.output.ptr, self.batch_sz, self.num_maps, h, w,
+                          int(self.invert), int(self.nearest), float(self.translation), float(self.zoom),
+                          float(self.magnitude), int(self.sigma), float(self.angle),
+                          float(self.pflip) if self._inj_flip is None else 0.0,
+                          self._inj_flip.ptr if self._inj_flip is not None else None, self.seed, 0, d_step_ptr, rg0,
+                          self.draws.ptr if self._inj_draws else None, None, None)
+            return
         if self.has_field:
             self.map_idx, self.map_fy, self.map_fx, self.target = self._maps[self._cur]
             if self._pre_valid and not self._inj_draws:
@@ -215,6 +271,7 @@ class ElasticLayer(Layer):
         the transposed gather, with the signs of the inversion and of the flip noise."""
         if not need_gin or isinstance(self.inpt, InputSlot):
             return None
+        assert not self.img_field, "ElasticLayer per_image has no backward pass (NeuralNet refuses such a net)"
         from .. import _lib
         b_ptr, b_act, b_prm, b_mask = below_info(below)
         if getattr(self, "gin", None) is None:
@@ -241,6 +298,8 @@ class ElasticLayer(Layer):
     @property
     def debugout(self):
         """[output, displacement field] like inlayers.py:145-147 (host copies)."""
+        assert not self.img_field, ("ElasticLayer per_image keeps no field: call tn_elastic_apply_img with its `target` "
+                                    "argument to read the coordinates of every image")
         if not self.active or not self.has_field:
             return [self.output.get_value(), np.zeros(2)]
         h = w = self.img_sz

@@ -236,6 +236,7 @@ class NeuralNet():
         for lyr in self.tr_layers:
             if isinstance(lyr, (ElasticLayer, ColorLayer)):
                 lyr.d_step = self.d_step
+                lyr.shard_lo = self.shard_lo      # (a per-image ElasticLayer in the middle of a net keys its draws by it)
             drop = getattr(lyr, "drop", None)
             if drop is not None:
                 drop.d_step = self.d_step
@@ -291,6 +292,10 @@ class NeuralNet():
                                          img_sz=prev_out_sz,
                                          rand_gen=self.rand_gen,
                                          **layer_args)
+            if getattr(curr_layer, "img_field", False) and any(lyr.has_updates() for lyr in self.tr_layers):
+                raise ValueError("ElasticLayer per_image in the middle of a net with a trainable layer below it (layer %d): "
+                                 "the backward pass of a per-image field is not implemented -- move the layer below the "
+                                 "first trainable layer or drop 'per_image'" % self.num_layers)
 
         elif curr_layer_type is ConvLayer:
             curr_layer = ConvLayer(tr_inpt,
@@ -366,11 +371,12 @@ class NeuralNet():
                 and lyrs[1].f16 and lyrs[1].x16 is not None and (lyrs[0].img_sz * lyrs[0].img_sz) % 4 == 0 \
                 and not lyrs[1].x16.padded:
             # (maps stored at a pitch > their side: the stage writes its fp32 output and the conv layer packs it into the
-            # padded layout, tn_c8_pack_pitch)
+            # padded layout, tn_c8_pack_pitch)  (a per-image layer writes it through tn_c8_elastic_apply_img)
             lyrs[0]._c8_consumer, lyrs[1]._c8_prefilled = lyrs[1], True
         # an active single-channel ElasticLayer feeding such a block: the block's forward resamples
         # the raw images itself (tn_elastic_convpool_fwd_mask)
-        if len(lyrs) >= 3 and isinstance(lyrs[0], ElasticLayer) and lyrs[0].active and \
+        # (not a per-image layer: the block reads ONE sample map)
+        if len(lyrs) >= 3 and isinstance(lyrs[0], ElasticLayer) and lyrs[0].active and not lyrs[0].img_field and \
                 lyrs[0].num_maps == 1 and not getattr(lyrs[1], "f16", False) and isinstance(lyrs[1], ConvLayer) and \
                 lyrs[1].fused_pool is lyrs[2]:
             el, conv, pool = lyrs[0], lyrs[1], lyrs[2]
