@@ -179,6 +179,47 @@ int tn_cb_conv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, in
                      int stride, int pad, int Ho, int Wo, const float* prev_a, int act, float prm);
 int tn_cb_conv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K,
                      int f, int stride, int pad, int Ho, int Wo);
+// The fp32 conv family: what one of its files calls in another.  conv_route (conv.hip) decides which of these a tn_conv2d_*
+// product runs; the fused blocks' entry points (convpool.hip, convblock*.hip) test their own *_supported functions.
+// conv.hip: the end of the family's split weight gradients (slabs in correlation layout: the sum flips every f x f block)
+int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW, float* db, int nblk, int K,
+                         int C, int f);
+// conv_mfma.hip: MFMA implicit GEMM, any f at stride 1 (tn_conv_mfma_supported)
+int tn_conv_mfma_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K,
+                     int f, int pad, int Ho, int Wo, int act, float prm);
+int tn_conv_mfma_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int f,
+                       int pad, int Ho, int Wo, const float* prev_a, int act, float prm);
+int tn_conv_mfma_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K,
+                       int f, int pad, int Ho, int Wo);
+// conv_tile.hip: the LDS-resident-tile kernels for 3x3 windows ...
+int tn_conv_tile_ok(const float* x, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
+int tn_conv_tile_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K,
+                     int pad, int Ho, int Wo, int act, float prm);
+int tn_conv_tile_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int pad,
+                       int Ho, int Wo, const float* prev_a, int act, float prm);
+int tn_conv_tile_wgrad_ok(tn_ctx* ctx, const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad,
+                          int Ho, int Wo);
+int tn_conv_tile_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K);
+// ... their weight gradient for few input channels (first layers), from a plain dz or from a block's pooling mask ...
+int tn_conv_tile_smallc_ok(const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
+int tn_conv_tile_smallc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd,
+                              int K);
+extern "C" int tn_convpool_smallc_supported(int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo, int p, int Hp,
+                                            int Wp);
+int tn_conv_tile_smallc_bwd(tn_ctx* ctx, const float* x, const float* g_, const float* y, const uint8_t* mask, float* dW,
+                            float* db, int N, int C, int H, int Wd, int K, int act, float prm);
+// ... and wide conv + act + 2x2 max-pool blocks on them (tn_convpool_tile_supported)
+int tn_conv_tile_pool_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* y, uint8_t* mask, int N, int C,
+                          int H, int Wd, int K, int act, float prm);
+int tn_conv_tile_pool_bwd(tn_ctx* ctx, const float* x, const float* W, const float* g_, const float* y, const uint8_t* mask,
+                          float* dx, float* dW, float* db, int N, int C, int H, int Wd, int K, int act, float prm,
+                          const float* prev_a, int prev_act, float prev_prm);
+// convblock_mfma.hip: matrix-core variant of tn_convblock_bwd
+int tn_convblock_mfma_supported(int C, int K, int f, int stride, int p, int H, int Wd, int pad_lo, int Ho, int Wo, int Hp,
+                                int Wp);
+int tn_convblock_mfma_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b, const float* g, float* dx, float* dW,
+                          float* db, int N, int C, int H, int Wd, int K, int pad_lo, int Ho, int Wo, int Hp, int Wp, int act,
+                          float act_param);
 int tn_red_flush(tn_ctx* ctx);
 int tn_red_flush_inc(tn_ctx* ctx, uint32_t* inc);
 
@@ -216,6 +257,33 @@ inline int tn_fail(tn_ctx* ctx, int code, const char* fmt, ...) {
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// the entry points that take fp32 activations refuse to run while a 16-bit DTYPE mode is in force
+#define TN_FP32_ONLY(ctx, name) \
+    TN_REQUIRE(!(ctx)->mm_f16, name ": fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)")
+
+// The slab prologue of the fp32 conv family's split weight gradients: scratch for nslab (the caller's rule) slabs of
+// KCFF = K*C*f*f weight sums, then nslab slabs of K bias sums (tn_conv_wgrad_finish adds them up)
+inline int conv_slabs(tn_ctx* ctx, int nslab, size_t KCFF, int K, float** partial, float** dbpartial) {
+    int rc = tn_scratch_get(ctx, (size_t)nslab * (KCFF + K) * sizeof(float), partial);
+    if (rc) return rc;
+    *dbpartial = *partial + (size_t)nslab * KCFF;
+    return TN_OK;
+}
+
+// Launch Kern with `lds` bytes of dynamic LDS: the grow-only opt-in (not a stream op: once per size), then the launch, which
+// the caller checks.  The high-water mark is per KERNEL: Kern is a template argument because all ACT instantiations of a
+// kernel share one function type, and a static keyed on that type would skip the second one's opt-in.
+template <auto Kern, class... Args>
+static int tn_launch_lds(tn_ctx* ctx, dim3 grid, dim3 block, size_t lds, Args... args) {
+    static size_t set_for = 0;
+    if (set_for < lds) {
+        TN_HIP(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        set_for = lds;
+    }
+    Kern<<<grid, block, lds, ctx->stream>>>(args...);
+    return TN_OK;
+}
+
 // ---------------------------------------------------------------------------
 // activations (theanet/layer/layer.py:27-39).  The backward pass only keeps the
 // layer OUTPUT a, so act'(z) is expressed through a:
@@ -248,6 +316,19 @@ __device__ __forceinline__ float tn_act_grad_from_out(float a, int act, float pr
         }
         default: return 1.f;
     }
+}
+
+// The fused conv blocks' form (convpool.hip, convblock.hip, convblock_mfma.hip): ACT == TN_ACT_LEAKY compiles the
+// leaky-ReLU expressions in line, any other ACT (-1) takes the run-time switch above.
+template <int ACT>
+__device__ __forceinline__ float cb_act(float z, int act, float prm) {
+    if (ACT == TN_ACT_LEAKY) return fmaxf(0.f, z) + fminf(0.f, z) * prm;
+    return tn_act_fwd(z, act, prm);
+}
+template <int ACT>
+__device__ __forceinline__ float cb_actg(float a, int act, float prm) {
+    if (ACT == TN_ACT_LEAKY) return a > 0.f ? 1.f : (a < 0.f ? prm : (prm > 0.f ? 1.f + prm : 0.f));
+    return tn_act_grad_from_out(a, act, prm);
 }
 
 // Four values behind ONE wave-uniform test of the activation kind.  Epilogues that called the two functions above

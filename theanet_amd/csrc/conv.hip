@@ -360,23 +360,6 @@ __global__ __launch_bounds__(256) void conv_dgrad_lds(
 
 // ------------------------------------------------------------------------------------
 
-// MFMA implicit-GEMM path (conv_mfma.hip)
-int tn_conv_mfma_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N,
-                     int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo, int act, float prm);
-int tn_conv_mfma_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H,
-                       int Wd, int K, int f, int pad, int Ho, int Wo, const float* prev_a, int act,
-                       float prm);
-int tn_conv_mfma_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N,
-                       int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
-extern "C" int tn_conv_mfma_supported(int C, int K, int f, int stride);
-int tn_conv_tile_smallc_ok(const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad,
-                           int Ho, int Wo);
-int tn_conv_tile_smallc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C,
-                              int H, int Wd, int K);
-int tn_conv_tile_ok(const float* x, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
-int tn_conv_tile_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C,
-                     int H, int Wd, int K, int pad, int Ho, int Wo, int act, float prm);
-
 int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
                          float* db, int nblk, int K, int C, int f) {
     // slabs are in correlation layout: the sum flips every f x f block back (reduce.hip)
@@ -384,21 +367,75 @@ int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbparti
                         db, (uint32_t)K, (uint32_t)nblk, (uint32_t)K, (uint32_t)(f * f));
 }
 
+// ---- which kernel a product of tn_conv2d_* gets: the whole ladder, in the order it is asked ------------------------
+enum ConvProduct { CONV_FWD, CONV_WGRAD, CONV_DGRAD };
+enum ConvRoute {
+    CONV_BF16,         // CONV 'bfloat16' (conv_bf16.hip): every geometry while the mode is in force
+    CONV_TILE,         // LDS-resident-tile matrix-core kernels, 3x3 (conv_tile.hip)
+    CONV_TILE_SMALLC,  // ... their weight gradient for few input channels, C*9 <= 32 (first layers)
+    CONV_MFMA,         // MFMA implicit GEMM (conv_mfma.hip)
+    CONV_LDS_DGRAD,    // conv_dgrad_lds: 3x3 input gradient over an LDS-resident dz
+    CONV_DIRECT,       // conv_*_direct
+    CONV_GENERIC       // conv_wgrad_generic + conv_bgrad_generic: filter sizes without a direct weight gradient
+};
+
+// images per block of conv_dgrad_lds (0: the filters and one haloed dz image do not fit its 60 KiB of LDS)
+static int dgrad_lds_group(int K, int Ho, int Wo, size_t* lds) {
+    const size_t per = (size_t)K * (Ho + 4) * (Wo + 4) * sizeof(float);
+    const size_t wbytes = (size_t)K * 9 * 16;
+    if (per + wbytes > 60 * 1024) return 0;
+    int G = (int)((60 * 1024 - wbytes) / per);
+    if (G > 4) G = 4;
+    *lds = wbytes + (size_t)G * per;
+    return G;
+}
+
+// p, q: the operands whose 16-byte alignment tn_conv_tile_*ok look at -- forward x, weight gradient x and dz, input
+// gradient dz.  The geometry is the LAYER's in every product.
+static ConvRoute conv_route(tn_ctx* ctx, ConvProduct prod, const float* p, const float* q, int N, int C, int H, int Wd,
+                            int K, int f, int stride, int pad, int Ho, int Wo) {
+    if (ctx->conv_bf16) return CONV_BF16;      // the mode, not the shape: asked before the entry points' shape checks,
+    if (N <= 0 || C <= 0 || K <= 0 || f <= 0 || stride <= 0 || (prod == CONV_FWD && (Ho <= 0 || Wo <= 0)))
+        return CONV_DIRECT;                    // which refuse these: nothing to ask the geometry functions
+    size_t lds;
+    switch (prod) {
+        case CONV_FWD:
+            if (tn_conv_mfma_supported(C, K, f, stride))
+                return tn_conv_tile_ok(p, N, C, H, Wd, K, f, pad, Ho, Wo) ? CONV_TILE : CONV_MFMA;
+            // few input channels (first layers): still worth the matrix core when the LDS-tile kernel applies
+            if (stride == 1 && K >= 16 && tn_conv_tile_ok(p, N, C, H, Wd, K, f, pad, Ho, Wo)) return CONV_TILE;
+            return CONV_DIRECT;
+        case CONV_WGRAD:
+            // (tn_conv_tile_wgrad_ok cuts its slabs for ctx->num_cus, the fused block's tn_convpool_tile_supported
+            // for 256 CUs whatever the chip: possibly unintended, kept as it is)
+            if (tn_conv_mfma_supported(C, K, f, stride))
+                return tn_conv_tile_wgrad_ok(ctx, p, q, N, C, H, Wd, K, f, pad, Ho, Wo) ? CONV_TILE : CONV_MFMA;
+            if (stride == 1 && tn_conv_tile_smallc_ok(p, q, N, C, H, Wd, K, f, pad, Ho, Wo)) return CONV_TILE_SMALLC;
+            return (f == 3 || f == 5 || f == 1 || f == 2) ? CONV_DIRECT : CONV_GENERIC;
+        default:
+            // dx = conv_fwd(dz, Wt) with padding f-1-pad: the roles swap -- reduction K*f*f, rows = C input maps,
+            // gathered tensor = dz (N,K,Ho,Wo)
+            if (tn_conv_mfma_supported(K, C, f, stride))
+                return tn_conv_tile_ok(p, N, K, Ho, Wo, C, f, f - 1 - pad, H, Wd) ? CONV_TILE : CONV_MFMA;
+            if (f == 3 && stride == 1 && dgrad_lds_group(K, Ho, Wo, &lds)) return CONV_LDS_DGRAD;
+            return CONV_DIRECT;
+    }
+}
+
 extern "C" {
 
 int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N,
                   int C, int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo,
                   int act, float act_param) {
-    if (ctx->conv_bf16)     // CONV 'bfloat16': every geometry (conv_bf16.hip)
-        return tn_cb_conv_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, act, act_param);
-    TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0 && Ho > 0 && Wo > 0,
-               "tn_conv2d_fwd: bad shape");
-    TN_REQUIRE(!ctx->mm_f16, "tn_conv2d_fwd: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
-    if (tn_conv_mfma_supported(C, K, f, stride))
-        return tn_conv_mfma_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, pad_lo, Ho, Wo, act, act_param);
-    // few input channels (first layers): still worth the matrix core when the LDS-tile kernel applies
-    if (stride == 1 && K >= 16 && tn_conv_tile_ok(x, N, C, H, Wd, K, f, pad_lo, Ho, Wo))
-        return tn_conv_tile_fwd(ctx, x, W, b, a, N, C, H, Wd, K, pad_lo, Ho, Wo, act, act_param);
+    const ConvRoute route = conv_route(ctx, CONV_FWD, x, nullptr, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    if (route == CONV_BF16) return tn_cb_conv_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, act, act_param);
+    TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0 && Ho > 0 && Wo > 0, "tn_conv2d_fwd: bad shape");
+    TN_FP32_ONLY(ctx, "tn_conv2d_fwd");
+    switch (route) {
+        case CONV_TILE: return tn_conv_tile_fwd(ctx, x, W, b, a, N, C, H, Wd, K, pad_lo, Ho, Wo, act, act_param);
+        case CONV_MFMA: return tn_conv_mfma_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, pad_lo, Ho, Wo, act, act_param);
+        default: break;      // CONV_DIRECT
+    }
     const long long M = (long long)N * Ho * Wo;
     const int gx = cdiv(M, 256);
 #define LAUNCH_FWD(F_, KT_)                                                                     \
@@ -419,74 +456,68 @@ int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, f
 
 int tn_conv2d_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C,
                     int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo) {
-    if (ctx->conv_bf16) return tn_cb_conv_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    const ConvRoute route = conv_route(ctx, CONV_WGRAD, x, dz, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    if (route == CONV_BF16) return tn_cb_conv_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0, "tn_conv2d_wgrad: bad shape");
-    TN_REQUIRE(!ctx->mm_f16, "tn_conv2d_wgrad: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
-    if (tn_conv_mfma_supported(C, K, f, stride))
-        return tn_conv_mfma_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, pad_lo, Ho, Wo);
-    if (stride == 1 && tn_conv_tile_smallc_ok(x, dz, N, C, H, Wd, K, f, pad_lo, Ho, Wo))   // first layers
-        return tn_conv_tile_smallc_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K);
+    TN_FP32_ONLY(ctx, "tn_conv2d_wgrad");
+    switch (route) {
+        case CONV_TILE: return tn_conv_tile_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K);
+        case CONV_MFMA: return tn_conv_mfma_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, pad_lo, Ho, Wo);
+        case CONV_TILE_SMALLC: return tn_conv_tile_smallc_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K);
+        case CONV_GENERIC:
+            conv_wgrad_generic<<<K * C * f * f, 256, 0, ctx->stream>>>(x, dz, dW, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+            TN_LAUNCH_CHECK();
+            conv_bgrad_generic<<<K, 256, 0, ctx->stream>>>(dz, db, N, K, Ho * Wo);
+            TN_LAUNCH_CHECK();
+            return TN_OK;
+        default: break;      // CONV_DIRECT
+    }
     const long long M = (long long)N * Ho * Wo;
-    if (f == 3 || f == 5 || f == 1 || f == 2) {
-        int nblk = cdiv(M, 256 * 16);
-        if (nblk > 1024) nblk = 1024;
-        if (nblk < 1) nblk = 1;
-        const size_t KCFF = (size_t)K * C * f * f;
-        const size_t need = ((size_t)nblk * (KCFF + K)) * sizeof(float);
-        float* partial;
-        int rc = tn_scratch_get(ctx, need, &partial);
-        if (rc) return rc;
-        float* dbpartial = partial + (size_t)nblk * KCFF;
+    int nblk = cdiv(M, 256 * 16);
+    if (nblk > 1024) nblk = 1024;
+    if (nblk < 1) nblk = 1;
+    float *partial, *dbpartial;
+    int rc = conv_slabs(ctx, nblk, (size_t)K * C * f * f, K, &partial, &dbpartial);
+    if (rc) return rc;
 #define LAUNCH_WG(F_, KT_, CT_)                                                                  \
     conv_wgrad_direct<F_, KT_, CT_><<<dim3(nblk, cdiv(K, KT_), cdiv(C, CT_)), 256, 0, ctx->stream>>>( \
         x, dz, partial, dbpartial, N, C, H, Wd, K, stride, pad_lo, Ho, Wo)
-        if (f == 3) {
-            if (C >= 4) LAUNCH_WG(3, 4, 4);
-            else if (C >= 2) LAUNCH_WG(3, 4, 2);
-            else LAUNCH_WG(3, 4, 1);
-        } else if (f == 5) {
-            if (C >= 2) LAUNCH_WG(5, 2, 2); else LAUNCH_WG(5, 4, 1);
-        } else if (f == 2) {
-            if (C >= 4) LAUNCH_WG(2, 4, 4); else LAUNCH_WG(2, 4, 1);
-        } else {
-            if (C >= 4) LAUNCH_WG(1, 8, 4); else LAUNCH_WG(1, 8, 1);
-        }
-#undef LAUNCH_WG
-        TN_LAUNCH_CHECK();
-        rc = tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, K, C, f);
-        if (rc) return rc;
+    if (f == 3) {
+        if (C >= 4) LAUNCH_WG(3, 4, 4);
+        else if (C >= 2) LAUNCH_WG(3, 4, 2);
+        else LAUNCH_WG(3, 4, 1);
+    } else if (f == 5) {
+        if (C >= 2) LAUNCH_WG(5, 2, 2); else LAUNCH_WG(5, 4, 1);
+    } else if (f == 2) {
+        if (C >= 4) LAUNCH_WG(2, 4, 4); else LAUNCH_WG(2, 4, 1);
     } else {
-        conv_wgrad_generic<<<K * C * f * f, 256, 0, ctx->stream>>>(x, dz, dW, N, C, H, Wd, K, f,
-                                                                  stride, pad_lo, Ho, Wo);
-        TN_LAUNCH_CHECK();
-        conv_bgrad_generic<<<K, 256, 0, ctx->stream>>>(dz, db, N, K, Ho * Wo);
-        TN_LAUNCH_CHECK();
+        if (C >= 4) LAUNCH_WG(1, 8, 4); else LAUNCH_WG(1, 8, 1);
     }
-    return TN_OK;
+#undef LAUNCH_WG
+    TN_LAUNCH_CHECK();
+    return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, K, C, f);
 }
 
 int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H,
                     int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo, const float* prev_a,
                     int prev_act, float prev_act_param) {
-    if (ctx->conv_bf16)
+    const ConvRoute route = conv_route(ctx, CONV_DGRAD, dz, nullptr, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    if (route == CONV_BF16)
         return tn_cb_conv_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0, "tn_conv2d_dgrad: bad shape");
-    TN_REQUIRE(!ctx->mm_f16, "tn_conv2d_dgrad: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
-    if (tn_conv_mfma_supported(K, C, f, stride))     // reduction K*f*f, rows = C input maps
-        return tn_conv_mfma_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, f, pad_lo, Ho, Wo, prev_a, prev_act,
-                                  prev_act_param);
-    if (f == 3 && stride == 1) {
-        const size_t per = (size_t)K * (Ho + 4) * (Wo + 4) * sizeof(float);
-        const size_t wbytes = (size_t)K * 9 * 16;
-        if (per + wbytes <= 60 * 1024) {
-            int G = (int)((60 * 1024 - wbytes) / per);
-            if (G > 4) G = 4;
-            const size_t lds = wbytes + (size_t)G * per;
+    TN_FP32_ONLY(ctx, "tn_conv2d_dgrad");
+    switch (route) {
+        case CONV_TILE: return tn_conv_tile_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
+        case CONV_MFMA: return tn_conv_mfma_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, f, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
+        case CONV_LDS_DGRAD: {
+            size_t lds;
+            const int G = dgrad_lds_group(K, Ho, Wo, &lds);
             conv_dgrad_lds<3><<<dim3(cdiv(N, G), cdiv(C, 4)), 256, lds, ctx->stream>>>(
                 dz, W, dx, N, C, H, Wd, K, pad_lo, Ho, Wo, G, prev_a, prev_act, prev_act_param);
             TN_LAUNCH_CHECK();
             return TN_OK;
         }
+        default: break;      // CONV_DIRECT
     }
     const long long M = (long long)N * H * Wd;
     const int gx = cdiv(M, 256);

@@ -15,26 +15,6 @@
 // :106-112; Theano MaxPoolGrad tie rule.
 #include "common.h"
 
-int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
-                         float* db, int nblk, int K, int C, int f);
-// convblock_mfma.hip: matrix-core variant of the same backward
-int tn_convblock_mfma_supported(int C, int K, int f, int stride, int p, int H, int Wd, int pad_lo,
-                                int Ho, int Wo, int Hp, int Wp);
-int tn_convblock_mfma_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b, const float* g,
-                          float* dx, float* dW, float* db, int N, int C, int H, int Wd, int K,
-                          int pad_lo, int Ho, int Wo, int Hp, int Wp, int act, float act_param);
-
-template <int ACT>
-__device__ __forceinline__ float cb_act(float z, int act, float prm) {
-    if (ACT == TN_ACT_LEAKY) return fmaxf(0.f, z) + fminf(0.f, z) * prm;
-    return tn_act_fwd(z, act, prm);
-}
-template <int ACT>
-__device__ __forceinline__ float cb_actg(float a, int act, float prm) {
-    if (ACT == TN_ACT_LEAKY) return a > 0.f ? 1.f : (a < 0.f ? prm : (prm > 0.f ? 1.f + prm : 0.f));
-    return tn_act_grad_from_out(a, act, prm);
-}
-
 // LDS rows are padded so that wide (b64 / b128) reads are naturally aligned:
 //   x  tile: rows of Wx = 4*ceil(Wo/4) + 4 floats (data at col 0..Wo+F-2, zero beyond)
 //   dz tile: rows of Wh = 4*ceil(Wo/4) + 4 floats, interior at col CB_LP = 4 (16-byte aligned);
@@ -281,29 +261,15 @@ static int launch_cb(tn_ctx* ctx, const float* x, const float* W, const float* b
     const int ngroups = cdiv(q.N, q.G);
     int nblk = ctx->num_cus;
     if (nblk > ngroups) nblk = ngroups;
-    const size_t KCFF = (size_t)q.K * C * F * F;
     const int nslab = nblk * q.G;
-    float* partial;
-    int rc = tn_scratch_get(ctx, (size_t)nslab * (KCFF + q.K) * sizeof(float), &partial);
+    float *partial, *dbpartial;
+    int rc = conv_slabs(ctx, nslab, (size_t)q.K * C * F * F, q.K, &partial, &dbpartial);
     if (rc) return rc;
-    float* dbpartial = partial + (size_t)nslab * KCFF;
-    if (act == TN_ACT_LEAKY) {
-        auto kern = convblock_bwd_lds<F, C, TN_ACT_LEAKY>;
-        static size_t set_for = 0;      // the attribute call is not a stream op: do it once per size
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, CB_NT, lds, ctx->stream>>>(x, W, b, g, dx, partial, dbpartial, q, act, prm);
-    } else {
-        auto kern = convblock_bwd_lds<F, C, -1>;
-        static size_t set_for = 0;
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, CB_NT, lds, ctx->stream>>>(x, W, b, g, dx, partial, dbpartial, q, act, prm);
-    }
+    if (act == TN_ACT_LEAKY)
+        rc = tn_launch_lds<convblock_bwd_lds<F, C, TN_ACT_LEAKY>>(ctx, nblk, CB_NT, lds, x, W, b, g, dx, partial, dbpartial, q, act, prm);
+    else
+        rc = tn_launch_lds<convblock_bwd_lds<F, C, -1>>(ctx, nblk, CB_NT, lds, x, W, b, g, dx, partial, dbpartial, q, act, prm);
+    if (rc) return rc;
     TN_LAUNCH_CHECK();
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nslab, q.K, C, F);
 }

@@ -22,9 +22,6 @@
 // into registers while the current one is computed.  HBM traffic: x, g read once, dx written once.
 #include "common.h"
 
-int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
-                         float* db, int nblk, int K, int C, int f);
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define CM_XR 12        // prefetch registers per lane for x (C*H*W <= 64*CM_XR) and for g (K*Hp*Wp)
@@ -76,17 +73,6 @@ __device__ __forceinline__ float cm_bit_and(int m, float v) {
 // n / d for 0 <= n < 2^16 given rd = 1/d to 1 ulp (exact: (n + .5) / d stays >= .5/d away from
 // the next integer, far more than the rounding of the product)
 __device__ __forceinline__ int cm_div(int n, float rd) { return __float2int_rz(((float)n + .5f) * rd); }
-
-template <int ACT>
-__device__ __forceinline__ float cm_act(float z, int act, float prm) {
-    if (ACT == TN_ACT_LEAKY) return fmaxf(0.f, z) + fminf(0.f, z) * prm;
-    return tn_act_fwd(z, act, prm);
-}
-template <int ACT>
-__device__ __forceinline__ float cm_actg(float a, int act, float prm) {
-    if (ACT == TN_ACT_LEAKY) return a > 0.f ? 1.f : (a < 0.f ? prm : (prm > 0.f ? 1.f + prm : 0.f));
-    return tn_act_grad_from_out(a, act, prm);
-}
 
 template <int C, int KS2, int ACT>      // KS2 = ceil(K / 4): reduction steps of the dgrad product
 __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
@@ -278,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
                 float m = -INFINITY;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    a[r] = cm_act<ACT>(z[kt][r] + bk[kt], act, prm);
+                    a[r] = cb_act<ACT>(z[kt][r] + bk[kt], act, prm);
                     m = (e2 >> r & 1) ? fmaxf(m, a[r]) : m;
                 }
 #pragma unroll
@@ -810,7 +796,11 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
 #undef CM_STAMP
 }
 
-static void cm_geometry(CmGeom& q, int C, int K) {
+// the one builder of a launch's geometry (N, pad and dbg do not enter the derived fields: cm_supported passes zeros)
+static CmGeom cm_geometry(int N, int C, int H, int Wd, int K, int pad, int Ho, int Wo, int Hp, int Wp, int dbg) {
+    CmGeom q;
+    q.N = N; q.H = H; q.Wd = Wd; q.K = K; q.pad = pad; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp;
+    q.dbg = dbg;
     q.Wx = q.Wo + 3;
     q.xplane = (q.Ho + 3) * q.Wx;
     q.xf = ((C * q.xplane + 3) & ~3) + 4;
@@ -822,6 +812,7 @@ static void cm_geometry(CmGeom& q, int C, int K) {
     if (red < 2 * ((K + 3) / 4) * 4 * 64) red = 2 * ((K + 3) / 4) * 4 * 64;      // (W44: main + remainder accumulators)
     q.wavef = 2 * q.xf + q.dzf + 4;          // + one zero float4 behind the dz tile
     if (q.wavef < red) q.wavef = red;
+    return q;
 }
 
 static size_t cm_lds_bytes(const CmGeom& q) { return ((size_t)q.tabf + 4 * (size_t)q.wavef) * sizeof(float); }
@@ -834,9 +825,7 @@ static int cm_supported(int C, int K, int f, int stride, int p, int H, int Wd, i
     if (H + 2 * pad_lo > Ho + 2 || Wd + 2 * pad_lo > Wo + 2) return 0;     // the padded image is the tile
     if (Wo + 2 > 16) return 0;                   // a dz row (+ its 2-pixel spill) is one 16-lane DPP row
     if (Hp != (Ho + 1) / 2 || Wp != (Wo + 1) / 2) return 0;
-    CmGeom q;
-    q.H = H; q.Wd = Wd; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp; q.dbg = 0;
-    cm_geometry(q, C, K);
+    const CmGeom q = cm_geometry(0, C, H, Wd, K, 0, Ho, Wo, Hp, Wp, 0);
     if (recompute && K * Hp * Wp > q.xf) return 0;   // the g tile borrows the dx tile
     return cm_lds_bytes(q) <= 78 * 1024;         // two blocks per CU
 }
@@ -846,36 +835,26 @@ int tn_convblock_mfma_supported(int C, int K, int f, int stride, int p, int H, i
     return cm_supported(C, K, f, stride, p, H, Wd, pad_lo, Ho, Wo, Hp, Wp, true);
 }
 
+// one block per four images, at most two per CU; a weight-gradient slab per block
+static int cm_blocks(tn_ctx* ctx, int N) {
+    const int nblk = 2 * ctx->num_cus;
+    return nblk > cdiv(N, 4) ? cdiv(N, 4) : nblk;
+}
+
 template <int C, int KS2>
 static int launch_cm(tn_ctx* ctx, const float* x, const float* W, const float* b, const float* g,
                      float* dx, float* dW, float* db, CmGeom q, int act, float prm) {
     const size_t lds = cm_lds_bytes(q);
-    int nblk = 2 * ctx->num_cus;
-    if (nblk > cdiv(q.N, 4)) nblk = cdiv(q.N, 4);
-    const size_t KCFF = (size_t)q.K * C * 9;
-    float* partial;
-    int rc = tn_scratch_get(ctx, (size_t)nblk * (KCFF + q.K) * sizeof(float), &partial);
+    const int nblk = cm_blocks(ctx, q.N);
+    float *partial, *dbpartial;
+    int rc = conv_slabs(ctx, nblk, (size_t)q.K * C * 9, q.K, &partial, &dbpartial);
     if (rc) return rc;
-    float* dbpartial = partial + (size_t)nblk * KCFF;
-    if (act == TN_ACT_LEAKY) {
-        auto kern = convblock_bwd_mfma<C, KS2, TN_ACT_LEAKY>;
-        static size_t set_for = 0;      // the attribute call is not a stream op: do it once per size
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, 256, lds, ctx->stream>>>(x, W, b, g, dx, partial, dbpartial, q, act, prm,
-                                              (q.dbg & 16) ? db : nullptr);
-    } else {
-        auto kern = convblock_bwd_mfma<C, KS2, -1>;
-        static size_t set_for = 0;
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, 256, lds, ctx->stream>>>(x, W, b, g, dx, partial, dbpartial, q, act, prm,
-                                              (q.dbg & 16) ? db : nullptr);
-    }
+    float* tdbg = (q.dbg & 16) ? db : nullptr;
+#define CM_L(ACT_) \
+    tn_launch_lds<convblock_bwd_mfma<C, KS2, ACT_>>(ctx, nblk, 256, lds, x, W, b, g, dx, partial, dbpartial, q, act, prm, tdbg)
+    rc = act == TN_ACT_LEAKY ? CM_L(TN_ACT_LEAKY) : CM_L(-1);
+#undef CM_L
+    if (rc) return rc;
     TN_LAUNCH_CHECK();
     if (q.dbg & 16) return TN_OK;     // timing run: db holds the cycle stamps of block 0
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, q.K, C, 3);
@@ -886,43 +865,39 @@ static int launch_cm_mask(tn_ctx* ctx, const float* x, const float* W, const flo
                           const uint8_t* mask, float* dx, float* dW, float* db, CmGeom q, int act,
                           float prm) {
     const size_t lds = cm_lds_bytes(q);
-    int nblk = 2 * ctx->num_cus;
-    if (nblk > cdiv(q.N, 4)) nblk = cdiv(q.N, 4);
-    const size_t KCFF = (size_t)q.K * C * 9;
-    float* partial;
-    int rc = tn_scratch_get(ctx, (size_t)nblk * (KCFF + q.K) * sizeof(float), &partial);
+    const int nblk = cm_blocks(ctx, q.N);
+    float *partial, *dbpartial;
+    int rc = conv_slabs(ctx, nblk, (size_t)q.K * C * 9, q.K, &partial, &dbpartial);
     if (rc) return rc;
-    float* dbpartial = partial + (size_t)nblk * KCFF;
     float* tdbg = (q.dbg & 16) ? db : nullptr;
-    if (act == TN_ACT_LEAKY && tn_knob(TN_K_CB_W44)) {
-        auto kern = convblock_bwd_mask_mfma<C, KS2, TN_ACT_LEAKY, true>;
-        static size_t set_for = 0;
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, 256, lds, ctx->stream>>>(x, W, g, y, mask, dx, partial, dbpartial, q, act, prm, tdbg);
-    } else if (act == TN_ACT_LEAKY) {
-        auto kern = convblock_bwd_mask_mfma<C, KS2, TN_ACT_LEAKY, false>;
-        static size_t set_for = 0;
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, 256, lds, ctx->stream>>>(x, W, g, y, mask, dx, partial, dbpartial, q, act, prm, tdbg);
-    } else {
-        auto kern = convblock_bwd_mask_mfma<C, KS2, -1, false>;
-        static size_t set_for = 0;
-        if (set_for < lds) {
-            TN_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            set_for = lds;
-        }
-        kern<<<nblk, 256, lds, ctx->stream>>>(x, W, g, y, mask, dx, partial, dbpartial, q, act, prm, tdbg);
-    }
+#define CM_L(ACT_, W44_)                                                                                       \
+    tn_launch_lds<convblock_bwd_mask_mfma<C, KS2, ACT_, W44_>>(ctx, nblk, 256, lds, x, W, g, y, mask, dx, partial, \
+                                                               dbpartial, q, act, prm, tdbg)
+    if (act == TN_ACT_LEAKY && tn_knob(TN_K_CB_W44)) rc = CM_L(TN_ACT_LEAKY, true);
+    else if (act == TN_ACT_LEAKY) rc = CM_L(TN_ACT_LEAKY, false);
+    else rc = CM_L(-1, false);
+#undef CM_L
+    if (rc) return rc;
     TN_LAUNCH_CHECK();
     if (q.dbg & 16) return TN_OK;
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, q.K, C, 3);
 }
+
+// the C x ceil(K / 4) instantiation table of both launchers: LAUNCH_<C, KS2>(arguments)
+#define CM_KS(LAUNCH_, C_, S_, ...) case S_: return LAUNCH_<C_, S_>(__VA_ARGS__)
+#define CM_GO(LAUNCH_, C_, ...)                                                                                \
+    switch ((K + 3) / 4) {                                                                                     \
+        CM_KS(LAUNCH_, C_, 1, __VA_ARGS__); CM_KS(LAUNCH_, C_, 2, __VA_ARGS__); CM_KS(LAUNCH_, C_, 3, __VA_ARGS__); \
+        CM_KS(LAUNCH_, C_, 4, __VA_ARGS__); CM_KS(LAUNCH_, C_, 5, __VA_ARGS__); CM_KS(LAUNCH_, C_, 6, __VA_ARGS__); \
+        CM_KS(LAUNCH_, C_, 7, __VA_ARGS__); default: CM_KS(LAUNCH_, C_, 8, __VA_ARGS__);                       \
+    }
+#define CM_DISPATCH(LAUNCH_, ...)                                                                              \
+    switch (C) {                                                                                               \
+        case 1: CM_GO(LAUNCH_, 1, __VA_ARGS__);                                                                \
+        case 2: CM_GO(LAUNCH_, 2, __VA_ARGS__);                                                                \
+        case 3: CM_GO(LAUNCH_, 3, __VA_ARGS__);                                                                \
+        default: CM_GO(LAUNCH_, 4, __VA_ARGS__);                                                               \
+    }
 
 extern "C" int tn_convblock_mask_supported(int C, int K, int f, int stride, int p, int H, int Wd,
                                            int pad_lo, int Ho, int Wo, int Hp, int Wp) {
@@ -936,45 +911,13 @@ extern "C" int tn_convblock_bwd_mask(tn_ctx* ctx, const float* x, const float* W
     TN_REQUIRE(tn_convblock_mask_supported(C, K, f, 1, p, H, Wd, pad_lo, Ho, Wo, Hp, Wp),
                "tn_convblock_bwd_mask: unsupported C=%d K=%d f=%d p=%d %dx%d", C, K, f, p, H, Wd);
     TN_REQUIRE(x && W && g && y && mask && dW && db, "tn_convblock_bwd_mask: null argument");
-    CmGeom q;
-    q.N = N; q.H = H; q.Wd = Wd; q.K = K; q.pad = pad_lo; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp;
-    cm_geometry(q, C, K);
-    q.dbg = tn_knob(TN_K_CM_DBG);
-#define CM_KS(C_, S_) case S_: return launch_cm_mask<C_, S_>(ctx, x, W, g, y, mask, dx, dW, db, q, act, act_param)
-#define CM_GO(C_)                                                                                  \
-    switch ((K + 3) / 4) {                                                                         \
-        CM_KS(C_, 1); CM_KS(C_, 2); CM_KS(C_, 3); CM_KS(C_, 4);                                    \
-        CM_KS(C_, 5); CM_KS(C_, 6); CM_KS(C_, 7); default: CM_KS(C_, 8);                           \
-    }
-    switch (C) {
-        case 1: CM_GO(1);
-        case 2: CM_GO(2);
-        case 3: CM_GO(3);
-        default: CM_GO(4);
-    }
-#undef CM_GO
-#undef CM_KS
+    const CmGeom q = cm_geometry(N, C, H, Wd, K, pad_lo, Ho, Wo, Hp, Wp, tn_knob(TN_K_CM_DBG));
+    CM_DISPATCH(launch_cm_mask, ctx, x, W, g, y, mask, dx, dW, db, q, act, act_param)
 }
 
 int tn_convblock_mfma_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b, const float* g,
                           float* dx, float* dW, float* db, int N, int C, int H, int Wd, int K,
                           int pad_lo, int Ho, int Wo, int Hp, int Wp, int act, float act_param) {
-    CmGeom q;
-    q.N = N; q.H = H; q.Wd = Wd; q.K = K; q.pad = pad_lo; q.Ho = Ho; q.Wo = Wo; q.Hp = Hp; q.Wp = Wp;
-    cm_geometry(q, C, K);
-    q.dbg = tn_knob(TN_K_CM_DBG);
-#define CM_KS(C_, S_) case S_: return launch_cm<C_, S_>(ctx, x, W, b, g, dx, dW, db, q, act, act_param)
-#define CM_GO(C_)                                                                                  \
-    switch ((K + 3) / 4) {                                                                         \
-        CM_KS(C_, 1); CM_KS(C_, 2); CM_KS(C_, 3); CM_KS(C_, 4);                                    \
-        CM_KS(C_, 5); CM_KS(C_, 6); CM_KS(C_, 7); default: CM_KS(C_, 8);                           \
-    }
-    switch (C) {
-        case 1: CM_GO(1);
-        case 2: CM_GO(2);
-        case 3: CM_GO(3);
-        default: CM_GO(4);
-    }
-#undef CM_GO
-#undef CM_KS
+    const CmGeom q = cm_geometry(N, C, H, Wd, K, pad_lo, Ho, Wo, Hp, Wp, tn_knob(TN_K_CM_DBG));
+    CM_DISPATCH(launch_cm, ctx, x, W, b, g, dx, dW, db, q, act, act_param)
 }

@@ -17,30 +17,6 @@
 // Semantics: theanet/layer/convpool.py:54-72 (true convolution, flipped W), :106-112 (pool).
 #include "common.h"
 
-// conv_tile.hip: the matrix-core kernels for wide 3x3 'same' blocks
-extern "C" int tn_convpool_tile_supported(int N, int C, int H, int Wd, int K, int f, int stride, int pad, int Ho,
-                                          int Wo, int p, int Hp, int Wp);
-extern "C" int tn_convpool_smallc_supported(int N, int C, int H, int Wd, int K, int f, int pad, int Ho,
-                                            int Wo, int p, int Hp, int Wp);
-int tn_conv_tile_smallc_bwd(tn_ctx* ctx, const float* x, const float* g_, const float* y, const uint8_t* mask,
-                            float* dW, float* db, int N, int C, int H, int Wd, int K, int act, float prm);
-int tn_conv_tile_pool_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* y,
-                          uint8_t* mask, int N, int C, int H, int Wd, int K, int act, float prm);
-int tn_conv_tile_pool_bwd(tn_ctx* ctx, const float* x, const float* W, const float* g_, const float* y,
-                          const uint8_t* mask, float* dx, float* dW, float* db, int N, int C, int H, int Wd,
-                          int K, int act, float prm, const float* prev_a, int prev_act, float prev_prm);
-
-template <int ACT>
-__device__ __forceinline__ float act_fwd_t(float z, int act, float prm) {
-    if (ACT == TN_ACT_LEAKY) return fmaxf(0.f, z) + fminf(0.f, z) * prm;
-    return tn_act_fwd(z, act, prm);
-}
-template <int ACT>
-__device__ __forceinline__ float act_grad_t(float a, int act, float prm) {
-    if (ACT == TN_ACT_LEAKY) return a > 0.f ? 1.f : (a < 0.f ? prm : (prm > 0.f ? 1.f + prm : 0.f));
-    return tn_act_grad_from_out(a, act, prm);
-}
-
 // Input window of S x S x C values held in registers.  Row / column offsets are clamped ONCE
 // (S + S integer ops), then all loads are issued back to back from base + roff + coff (hipcc
 // serialises "load; wait; select" chains, so the zero-padding selects -- needed only for
@@ -160,7 +136,7 @@ __global__ __launch_bounds__(256) void convpool_fwd_kernel(
         for (int di = 0; di < P; ++di)
 #pragma unroll
             for (int dj = 0; dj < P; ++dj) {
-                z[di][dj] = act_fwd_t<ACT>(z[di][dj], act, prm);
+                z[di][dj] = cb_act<ACT>(z[di][dj], act, prm);
                 m = valid[di][dj] ? fmaxf(m, z[di][dj]) : m;
             }
         yn[(size_t)k * HpWp] = m;
@@ -262,11 +238,11 @@ __global__ __launch_bounds__(256) void convpool_bwd_kernel(
 #pragma unroll
                         for (int v = 0; v < F; ++v)
                             z = fmaf(pt.v[c][u][v], Wk[(c * F + (F - 1 - u)) * F + (F - 1 - v)], z);
-                const float a = act_fwd_t<ACT>(z, act, prm);
+                const float a = cb_act<ACT>(z, act, prm);
                 float m = valid ? a : -INFINITY;
                 m = fmaxf(m, dpp_f<DPP_QUAD_XOR1>(m));
                 m = fmaxf(m, dpp_f<DPP_QUAD_XOR2>(m));
-                const float d = (valid && a == m) ? gk[kk] * act_grad_t<ACT>(a, act, prm) : 0.f;
+                const float d = (valid && a == m) ? gk[kk] * cb_actg<ACT>(a, act, prm) : 0.f;
                 if (dz_out && valid) dz_out[((size_t)n * K + k) * HoWo + i * Wo + j] = d;
                 accb[kk] += d;
 #pragma unroll
@@ -492,10 +468,6 @@ __global__ __launch_bounds__(256) void convpool_bwd_mask_kernel(
     }
 }
 
-// shared with conv.hip
-int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW,
-                         float* db, int nblk, int K, int C, int f);
-
 template <int F, int P, int C>
 static int launch_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* y,
                       uint8_t* mask, int N, int H, int Wd, int K, int pad, int Ho, int Wo, int Hp, int Wp, int act,
@@ -521,23 +493,19 @@ static int launch_fwd(tn_ctx* ctx, const float* x, const float* W, const float* 
     return TN_OK;
 }
 
-static int tn_tune_kt() { return 4; }          // filters per thread of the recomputing backward
-
-static int tn_tune_ppt() { return 8; }         // pixels per thread of the recomputing backward
+constexpr int CP_BWD_PPT = 8;         // pixels per thread of the recomputing backward
 
 template <int F, int C, int KT>
 static int launch_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b, const float* g,
                       float* dz, float* dW, float* db, int N, int H, int Wd, int K, int pad, int Ho,
                       int Wo, int Hp, int Wp, int act, float prm) {
     const long long total = (long long)N * Hp * Wp * 4;
-    int nblk = cdiv(total, 256 * tn_tune_ppt());
+    int nblk = cdiv(total, 256 * CP_BWD_PPT);
     if (nblk > 2048) nblk = 2048;
     if (nblk < 1) nblk = 1;
-    const size_t KCFF = (size_t)K * C * F * F;
-    float* partial;
-    int rc = tn_scratch_get(ctx, (size_t)nblk * (KCFF + K) * sizeof(float), &partial);
+    float *partial, *dbpartial;
+    int rc = conv_slabs(ctx, nblk, (size_t)K * C * F * F, K, &partial, &dbpartial);
     if (rc) return rc;
-    float* dbpartial = partial + (size_t)nblk * KCFF;
     TN_REQUIRE(total < (1ll << 31), "tn_convpool_bwd: too many outputs for 32-bit indexing");
     TN_REQUIRE((long long)N * C * H * Wd < (1ll << 30), "tn_convpool_bwd: input too large for 32-bit byte offsets");
     const dim3 grid(nblk, cdiv(K, KT));
@@ -562,7 +530,7 @@ constexpr int mask_mw_cap(int C, bool leaky, bool padded, bool pairs, bool dz) {
     return 2;                                              // 112 .. 139 VGPRs
 }
 
-static int tn_tune_mwin() { return 4; }        // windows per thread of the mask-driven backward (full batches)
+constexpr int CP_MASK_MWIN = 4;       // windows per thread of the mask-driven backward (full batches)
 
 template <int C, int KT>
 static int launch_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const float* y,
@@ -572,16 +540,14 @@ static int launch_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const fl
     TN_REQUIRE(total < (1ll << 31), "tn_convpool_bwd_mask: too many outputs for 32-bit indexing");
     TN_REQUIRE((long long)N * C * H * Wd < (1ll << 30), "tn_convpool_bwd_mask: input too large for 32-bit byte offsets");
     TN_REQUIRE((long long)K * Hp * Wp < (1ll << 23), "tn_convpool_bwd_mask: image too large for 32-bit byte offsets inside a wave");
-    int mwin = tn_tune_mwin();                          // windows per thread ...
+    int mwin = CP_MASK_MWIN;                            // windows per thread ...
     while (mwin > 1 && cdiv(total, 256 * mwin) < 2 * ctx->num_cus) mwin >>= 1;   // ... fewer for short batches (a 512-image shard: 85 blocks otherwise)
     int nblk = cdiv(total, 256 * mwin);
     if (nblk > 2048) nblk = 2048;
     if (nblk < 1) nblk = 1;
-    const size_t KCFF = (size_t)K * C * 9;
-    float* partial;
-    int rc = tn_scratch_get(ctx, (size_t)nblk * (KCFF + K) * sizeof(float), &partial);
+    float *partial, *dbpartial;
+    int rc = conv_slabs(ctx, nblk, (size_t)K * C * 9, K, &partial, &dbpartial);
     if (rc) return rc;
-    float* dbpartial = partial + (size_t)nblk * KCFF;
     const dim3 grid(nblk, cdiv(K, KT));
     // patch rows as 8-byte loads: unpadded, even pitch, aligned tensor, and no window column ever clamped
     const bool pairs = pad == 0 && Wd % 2 == 0 && 2 * Wp + 2 <= Wd && (reinterpret_cast<uintptr_t>(x) & 7) == 0;
@@ -614,6 +580,13 @@ static int launch_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const fl
     return tn_conv_wgrad_finish(ctx, partial, dbpartial, dW, db, nblk, K, C, 3);
 }
 
+// the backward kernels write dz window by window: rows / cols outside every window (ignore_border) are cleared first
+static int cp_clear_dz(tn_ctx* ctx, float* dz, int N, int K, int Ho, int Wo, int p, int Hp, int Wp) {
+    if (dz && (Hp * p < Ho || Wp * p < Wo))
+        TN_HIP(hipMemsetAsync(dz, 0, (size_t)N * K * Ho * Wo * sizeof(float), ctx->stream));
+    return TN_OK;
+}
+
 extern "C" {
 
 int tn_convpool_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const float* y,
@@ -625,8 +598,7 @@ int tn_convpool_bwd_mask(tn_ctx* ctx, const float* x, const float* g, const floa
     // weight gradients only (first layer), 'same' block with even maps: matrix-core kernel of conv_tile.hip
     if (!dz && tn_convpool_smallc_supported(N, C, H, Wd, K, f, pad_lo, Ho, Wo, p, Hp, Wp))
         return tn_conv_tile_smallc_bwd(ctx, x, g, y, mask, dW, db, N, C, H, Wd, K, act, act_param);
-    if (dz && (Hp * p < Ho || Wp * p < Wo))   // rows/cols outside every window (ignore_border)
-        TN_HIP(hipMemsetAsync(dz, 0, (size_t)N * K * Ho * Wo * sizeof(float), ctx->stream));
+    if (int rc = cp_clear_dz(ctx, dz, N, K, Ho, Wo, p, Hp, Wp)) return rc;
 #define CP_BWDM(C_, KT_)                                                                          \
     return launch_bwd_mask<C_, KT_>(ctx, x, g, y, mask, dz, dW, db, N, H, Wd, K, pad_lo, Ho, Wo, Hp, Wp, \
                                     act, act_param)
@@ -656,7 +628,7 @@ int tn_convpool_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b,
 int tn_convpool_fwd_mask(tn_ctx* ctx, const float* x, const float* W, const float* b, float* y,
                          uint8_t* mask, int N, int C, int H, int Wd, int K, int f, int pad_lo, int Ho,
                          int Wo, int p, int Hp, int Wp, int act, float act_param) {
-    TN_REQUIRE(!ctx->mm_f16, "tn_convpool_fwd_mask: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
+    TN_FP32_ONLY(ctx, "tn_convpool_fwd_mask");
     if (!tn_convpool_supported(C, f, 1, p) &&
         tn_convpool_tile_supported(N, C, H, Wd, K, f, 1, pad_lo, Ho, Wo, p, Hp, Wp))
         return tn_conv_tile_pool_fwd(ctx, x, W, b, y, mask, N, C, H, Wd, K, act, act_param);   // wide layers
@@ -683,7 +655,7 @@ int tn_convpool_bwd_mask_dx(tn_ctx* ctx, const float* x, const float* W, const f
                             int Wd, int K, int f, int pad_lo, int Ho, int Wo, int p, int Hp, int Wp, int act,
                             float act_param, const float* prev_a, int prev_act, float prev_act_param) {
     TN_REQUIRE(x && W && g && y && mask, "tn_convpool_bwd_mask_dx: null argument");
-    TN_REQUIRE(!ctx->mm_f16, "tn_convpool_bwd_mask_dx: fp32 tensors in a 16-bit DTYPE mode (the mode's entry points are tn_c8_*)");
+    TN_FP32_ONLY(ctx, "tn_convpool_bwd_mask_dx");
     TN_REQUIRE(tn_convpool_tile_supported(N, C, H, Wd, K, f, 1, pad_lo, Ho, Wo, p, Hp, Wp),
                "tn_convpool_bwd_mask_dx: unsupported block (C=%d K=%d %dx%d f=%d p=%d)", C, K, H, Wd, f, p);
     return tn_conv_tile_pool_bwd(ctx, x, W, g, y, mask, dx, dW, db, N, C, H, Wd, K, act, act_param, prev_a,
@@ -694,8 +666,7 @@ int tn_convpool_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b,
                     float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K, int f,
                     int pad_lo, int Ho, int Wo, int p, int Hp, int Wp, int act, float act_param) {
     TN_REQUIRE(tn_convpool_supported(C, f, 1, p), "tn_convpool_bwd: unsupported C=%d f=%d p=%d", C, f, p);
-    if (dz && (Hp * p < Ho || Wp * p < Wo))   // rows/cols outside every window (ignore_border)
-        TN_HIP(hipMemsetAsync(dz, 0, (size_t)N * K * Ho * Wo * sizeof(float), ctx->stream));
+    if (int rc = cp_clear_dz(ctx, dz, N, K, Ho, Wo, p, Hp, Wp)) return rc;
 #define CP_BWD(F_, C_, KT_)                                                                       \
     return launch_bwd<F_, C_, KT_>(ctx, x, W, b, g, dz, dW, db, N, H, Wd, K, pad_lo, Ho, Wo, Hp, Wp, \
                                    act, act_param)
@@ -704,9 +675,7 @@ int tn_convpool_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b,
             case 1: CP_BWD(3, 1, 4);
             case 2: CP_BWD(3, 2, 4);
             case 3: CP_BWD(3, 3, 4);
-            default:
-                if (tn_tune_kt() == 2) CP_BWD(3, 4, 2);
-                CP_BWD(3, 4, 4);
+            default: CP_BWD(3, 4, 4);
         }
     } else {
         if (C == 1) CP_BWD(5, 1, 4);

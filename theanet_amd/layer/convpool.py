@@ -3,6 +3,7 @@ Same constructor arguments, shape rules and ``representation`` strings; the
 compute is enqueued on the HIP backend (include/theanet_hip.h)."""
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -10,6 +11,24 @@ from ..device import C8_DTYPES, C8Array, c8_pitch, is_c8
 from .c8 import DenseDetour, conv_family
 from .layer import Layer, activation_by_name, below_info
 from .weights import init_wb
+
+
+def pool_mask_enabled():
+    """TN_POOL_MASK (default on; "0": off): the training forward of a fused fp32 3x3 conv + 2x2 pool block records where
+    every pooled value came from, and the backward runs from that mask instead of recomputing the conv outputs.  Read
+    where a block is fused (ConvLayer.fuse); NeuralNet puts the same answer into the ranks' agreement."""
+    return os.environ.get("TN_POOL_MASK", "1") != "0"
+
+
+# A fused fp32 conv + act + pool block.  family: whose kernels run it -- "convpool" (the register-resident kernels of
+# convpool.hip, few input channels) or "tile" (the LDS-tile matrix-core kernels, wide 3x3 'same' layers); mask: its
+# training forward records the pooling mask.  (A 16-bit block -- ConvLayer.c8_fam -- carries None.)
+ConvBlock = namedtuple("ConvBlock", "family mask")
+# ... its backward, decided when it first runs (ConvLayer._block_route): the entry point, whether that writes the
+# gradient w.r.t. the block's input itself (else it leaves dz for tn_conv2d_dgrad), and what the decision was made from
+BlockBwd = namedtuple("BlockBwd", "entry writes_dx inputs")
+# ... and the geometry arguments every tn_convpool_* / tn_convblock_* entry point ends with
+FusedGeom = namedtuple("FusedGeom", "N C H W K f pad Ho Wo p Hp Wp act prm")
 
 
 class ConvLayer(Layer):
@@ -93,9 +112,9 @@ class ConvLayer(Layer):
             self.c8_1x1, self.c8_fam = False, None
             self.output = self.ctx.empty((batch_sz, num_maps, self.out_sz, self.out_sz))
         self.gin = None
-        self.fused_pool = None     # set by NeuralNet: conv+act+pool run as ONE kernel
-        self._tile_pool = False    # ... on the LDS-tile matrix-core kernels (wide layers)
-        self._mask_block = None
+        self.fused_pool = None     # set by fuse(): conv+act+pool run as ONE kernel
+        self.block = None          # ... fp32: the ConvBlock it is
+        self._bwd_route = None     # ... and the BlockBwd its backward takes
         self.dz = None
 
         self.params = [self.W, self.b]
@@ -127,35 +146,39 @@ class ConvLayer(Layer):
                 self.filter_sz, self.stride, self.pad_lo, self.out_sz, self.out_sz)
 
     def can_fuse_with(self, pool):
-        """conv -> act -> 2x2 max-pool on small channel counts runs as one fused kernel pair
-        (tn_convpool_fwd / tn_convpool_bwd): the conv activation never reaches HBM."""
+        """conv -> act -> 2x2 max-pool as one fused kernel pair -- the conv activation never reaches HBM.  Returns the
+        family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused."""
         if self.f16:
             return True                  # (the only way a PoolLayer runs on the 16-bit stack: c8.check_follows)
-        if self.stride == 1 and self.ctx.lib.tn_convpool_supported(
-                self.num_prev_maps, self.filter_sz, self.stride, pool.pool_sz):
-            return True
+        if self.stride == 1 and self.ctx.lib.tn_convpool_supported(self.num_prev_maps, self.filter_sz, self.stride, pool.pool_sz):
+            return "convpool"            # small channel counts (tn_convpool_fwd / tn_convpool_bwd)
         # wide 3x3 'same' layers: the LDS-tile matrix-core kernels pool in their epilogue and run the
         # backward from the pooling mask (tn_convpool_fwd_mask / tn_convpool_bwd_mask_dx)
-        self._tile_pool = bool(self.ctx.lib.tn_convpool_tile_supported(
-            self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps, self.filter_sz,
-            self.stride, self.pad_lo, self.out_sz, self.out_sz, pool.pool_sz, pool.out_sz, pool.out_sz))
-        return self._tile_pool
+        if self.ctx.lib.tn_convpool_tile_supported(
+                self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps, self.filter_sz,
+                self.stride, self.pad_lo, self.out_sz, self.out_sz, pool.pool_sz, pool.out_sz, pool.out_sz):
+            return "tile"
+        return None
 
-    def mask_backward_supported(self, pool):
-        """True if the fused block's whole backward (dW, db and the input gradient) can run as
-        the one-kernel matrix-core variant tn_convblock_bwd_mask."""
-        if self._mask_block is None:
-            self._mask_block = bool(self.stride == 1 and self.ctx.lib.tn_convblock_mask_supported(
-                self.num_prev_maps, self.num_maps, self.filter_sz, self.stride, pool.pool_sz,
-                self.in_sz, self.in_sz, self.pad_lo, self.out_sz, self.out_sz, pool.out_sz,
-                pool.out_sz))
-        return self._mask_block
+    def fuse(self, pool, family):
+        """Make this layer and ``pool`` one block of ``family`` (what can_fuse_with answered)."""
+        self.fused_pool, pool.fused_conv = pool, self
+        if not self.f16:
+            # the mask kernels are the 3x3 / 2x2 ones; a tile block has no backward without its mask
+            self.block = ConvBlock(family, self.filter_sz == 3 and pool.pool_sz == 2 and
+                                   (family == "tile" or pool_mask_enabled()))
+
+    def unfuse(self):
+        """Back to two layers with a conv map between them (NeuralNet.get_data_test_model reads it)."""
+        assert not self.f16, "DTYPE {}: the conv map of a fused conv + pool block is never materialised".format(self.c8_dtype)
+        self.fused_pool.fused_conv = None
+        self.fused_pool = self.block = self._bwd_route = None
 
     def _fused_geom(self):
         pool = self.fused_pool
-        return (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps,
-                self.filter_sz, self.pad_lo, self.out_sz, self.out_sz, pool.pool_sz,
-                pool.out_sz, pool.out_sz, self.act.kind, self.act.prm)
+        return FusedGeom(self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps,
+                         self.filter_sz, self.pad_lo, self.out_sz, self.out_sz, pool.pool_sz,
+                         pool.out_sz, pool.out_sz, self.act.kind, self.act.prm)
 
     # -- the 16-bit stack: the 16-bit-resident kernels (include/theanet_hip.h, tn_c8_*) ---------------------------
     _c8_prefilled = False
@@ -225,72 +248,62 @@ class ConvLayer(Layer):
         self.ctx.call("tn_conv2d_fwd", self.inpt.ptr, self.W.ptr, self.b.ptr, self.output.ptr,
                       *self._geom(), self.act.kind, self.act.prm)
 
+    def _block_route(self, need_gin, below):
+        """Which backward the fused fp32 block takes.  Decided once, from whether the layer below wants a gradient and an
+        activation gradient on it, whether the forward records the pooling mask, and the library's capability queries."""
+        pool, lib, g = self.fused_pool, self.ctx.lib, self._fused_geom()
+        has_mask = pool.mask is not None
+        below_act = need_gin and below_info(below)[0] is not None     # act' of the layer below rides on dx
+        inputs = (need_gin, below_act, has_mask)
+        if self._bwd_route is not None:
+            assert self._bwd_route.inputs == inputs, (self._bwd_route, inputs)
+            return self._bwd_route
+        if self.block.family == "tile":
+            assert has_mask
+            route = ("tn_convpool_bwd_mask_dx", True)    # wide block: dW, db and dx from the pooled gradient + mask
+        elif has_mask:
+            # the forward recorded where every pooled value came from: no conv recompute.  Small maps: weight and input
+            # gradients as matrix-core products over an LDS-resident dz, one kernel; else dW, db and dz
+            one = self.stride == 1 and lib.tn_convblock_mask_supported(g.C, g.K, g.f, self.stride, g.p, g.H, g.W, g.pad,
+                                                                       g.Ho, g.Wo, g.Hp, g.Wp) and not below_act
+            route = ("tn_convblock_bwd_mask", True) if one else ("tn_convpool_bwd_mask", False)
+        elif lib.tn_convblock_supported(g.C, g.K, g.f, self.stride, g.p, g.Ho, g.Wo) and not below_act:
+            route = ("tn_convblock_bwd", True)       # LDS-resident recompute: dW, db AND dx in one kernel
+        else:
+            route = ("tn_convpool_bwd", False)       # recompute; dz only when the layer below needs a gradient
+        self._bwd_route = BlockBwd(*route, inputs)
+        return self._bwd_route
+
     def _backward_fused(self, gpool, need_gin, below):
-        """gpool = d cost / d (pooled output).  One kernel recomputes the windows, routes the
-        gradient through max-pool and activation and reduces dW/db; dz is only materialised
-        when the layer below needs a gradient."""
-        pool = self.fused_pool
-        if self._tile_pool:
-            # wide block: dW, db and the input gradient straight from the pooled gradient + mask
-            assert pool.mask is not None
-            b_ptr, b_act, b_prm, b_mask = below_info(below if need_gin else None)
-            assert b_mask is None
-            if need_gin and self.gin is None:
-                self.gin = self.ctx.empty(self.inpt.shape)
-            upd = self.has_updates()
-            self.ctx.call("tn_convpool_bwd_mask_dx", self.inpt.ptr, self.W.ptr, gpool.ptr, pool.output.ptr,
-                          pool.mask.ptr, self.gin.ptr if need_gin else None,
-                          self.grads[0].ptr if upd else None, self.grads[1].ptr if upd else None,
-                          *self._fused_geom(), b_ptr, b_act, b_prm)
-            self._gin_done = True
-            return self.gin if need_gin else None
-        if pool.mask is not None:
-            # the forward recorded where every pooled value came from: no conv recompute
-            if self.mask_backward_supported(pool) and not (need_gin and below_info(below)[0] is not None):
-                # small maps: weight and input gradients as matrix-core products over an
-                # LDS-resident dz, one kernel
-                if need_gin and self.gin is None:
-                    self.gin = self.ctx.empty(self.inpt.shape)
-                self.ctx.call("tn_convblock_bwd_mask", self.inpt.ptr, self.W.ptr, gpool.ptr,
-                              pool.output.ptr, pool.mask.ptr, self.gin.ptr if need_gin else None,
-                              self.grads[0].ptr, self.grads[1].ptr, *self._fused_geom())
-                self._gin_done = True
-                return self.gin if need_gin else None
-            self._gin_done = False
-            if need_gin and self.dz is None:
-                self.dz = self.ctx.empty(self.output.shape)
-            self.ctx.call("tn_convpool_bwd_mask", self.inpt.ptr, gpool.ptr, pool.output.ptr,
-                          pool.mask.ptr, self.dz.ptr if need_gin else None, self.grads[0].ptr,
-                          self.grads[1].ptr, *self._fused_geom())
-            return self.dz if need_gin else None
-        if self.ctx.lib.tn_convblock_supported(self.num_prev_maps, self.num_maps, self.filter_sz,
-                                               self.stride, pool.pool_sz, self.out_sz, self.out_sz):
-            # LDS-resident variant: dW/db AND the gradient w.r.t. the input in one kernel
-            if not (need_gin and below_info(below)[0] is not None):
-                if need_gin and self.gin is None:
-                    self.gin = self.ctx.empty(self.inpt.shape)
-                self.ctx.call("tn_convblock_bwd", self.inpt.ptr, self.W.ptr, self.b.ptr, gpool.ptr,
-                              self.gin.ptr if need_gin else None, self.grads[0].ptr,
-                              self.grads[1].ptr, *self._fused_geom())
-                self._gin_done = True
-                return self.gin if need_gin else None
-        self._gin_done = False
-        if need_gin and self.dz is None:
+        """gpool = d cost / d (pooled output).  One kernel routes the gradient through max-pool and activation (from
+        the pooling mask, or recomputing the windows) and reduces dW/db.  Returns the route and what it wrote: the
+        gradient w.r.t. the block's input (route.writes_dx) or dz, None when the layer below needs no gradient."""
+        pool, route = self.fused_pool, self._block_route(need_gin, below)
+        if need_gin and route.writes_dx and self.gin is None:
+            self.gin = self.ctx.empty(self.inpt.shape)
+        if need_gin and not route.writes_dx and self.dz is None:
             self.dz = self.ctx.empty(self.output.shape)
-        self.ctx.call("tn_convpool_bwd", self.inpt.ptr, self.W.ptr, self.b.ptr, gpool.ptr,
-                      self.dz.ptr if need_gin else None, self.grads[0].ptr, self.grads[1].ptr,
-                      *self._fused_geom())
-        return self.dz if need_gin else None
+        out = (self.gin if route.writes_dx else self.dz) if need_gin else None
+        x, W, b, g, y = self.inpt.ptr, self.W.ptr, self.b.ptr, gpool.ptr, pool.output.ptr
+        mask = pool.mask.ptr if pool.mask is not None else None
+        tile = route.entry == "tn_convpool_bwd_mask_dx"
+        head = {"tn_convpool_bwd_mask_dx": (x, W, g, y, mask), "tn_convblock_bwd_mask": (x, W, g, y, mask),
+                "tn_convpool_bwd_mask": (x, g, y, mask), "tn_convblock_bwd": (x, W, b, g), "tn_convpool_bwd": (x, W, b, g)}
+        # (only the tile block's entry point takes a block without updates -- no dW, db -- and applies act' of the layer below)
+        dW, db = (None, None) if tile and not self.has_updates() else (self.grads[0].ptr, self.grads[1].ptr)
+        b_ptr, b_act, b_prm, b_mask = below_info(below if need_gin else None)
+        assert b_mask is None or not tile
+        self.ctx.call(route.entry, *head[route.entry], out.ptr if need_gin else None, dW, db, *self._fused_geom(),
+                      *((b_ptr, b_act, b_prm) if tile else ()))
+        return route, out
 
     def backward(self, gout, need_gin, below):
         """gout = d cost / d z of this layer (activation gradient already fused in)."""
         if self.f16:
             return self._c8_backward(gout, need_gin, below)
         if self.fused_pool is not None:
-            gout = self._backward_fused(gout, need_gin, below)
-            if not need_gin:
-                return None
-            if self._gin_done:
+            route, gout = self._backward_fused(gout, need_gin, below)
+            if not need_gin or route.writes_dx:
                 return gout
         elif self.has_updates():
             self.ctx.call("tn_conv2d_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr,
@@ -358,19 +371,16 @@ class PoolLayer(Layer):
                 self.mask = self.ctx.empty(self.output.shape, np.uint8)
             return conv._c8_forward(self.output, self.mask if train else None)
         if conv is not None:
-            if train and self.mask is None and conv.filter_sz == 3 and self.pool_sz == 2 and \
-                    (conv._tile_pool or os.environ.get("TN_POOL_MASK", "1") != "0"):
+            if train and self.mask is None and conv.block.mask:
                 self.mask = self.ctx.empty(self.output.shape, np.uint8)
             el = self.fused_elastic
             if el is not None and train and el._apply_args is not None:
                 # ElasticLayer -> conv -> act -> pool in one launch (the resampled image is still
                 # written to el.output for the backward pass)
-                a = el._apply_args
-                g = conv._fused_geom()          # (N, C, H, W, K, f, pad, Ho, Wo, p, Hp, Wp, act, prm)
-                self.ctx.call("tn_elastic_convpool_fwd_mask", a[0], a[1], a[2], a[3], a[4], a[6], a[7],
-                              *a[8:], conv.W.ptr, conv.b.ptr, self.output.ptr,
-                              self.mask.ptr if self.mask is not None else None, g[4], g[5], g[6], g[7],
-                              g[8], g[9], g[10], g[11], g[12], g[13])
+                a, g = el._apply_args, conv._fused_geom()      # (single channel: the entry point takes no C)
+                self.ctx.call("tn_elastic_convpool_fwd_mask", *a.source(), a.N, *a.sample(), conv.W.ptr, conv.b.ptr,
+                              self.output.ptr, self.mask.ptr if self.mask is not None else None, g.K, g.f, g.pad, g.Ho,
+                              g.Wo, g.p, g.Hp, g.Wp, g.act, g.prm)
                 return
             self.ctx.call("tn_convpool_fwd_mask", conv.inpt.ptr, conv.W.ptr, conv.b.ptr,
                           self.output.ptr, self.mask.ptr if (train and self.mask is not None) else None,

@@ -10,9 +10,25 @@ random draws which either comes from the on-device Philox generator or is
 injected by a parity test (``inject``).  The test version is identity + invert
 (:157-163).
 """
+from collections import namedtuple
+
 import numpy as np
 
 from .layer import Layer, below_info
+
+# The arguments of the resampling, in the order tn_elastic_apply takes them (include/theanet_hip.h).  Its relatives take
+# a part of them: source() + N + C (tn_elastic_convpool_fwd_mask: no C) + sample(); tn_elastic_apply_bwd only sample().
+_ELASTIC_SAMPLE = "h w invert nearest map_idx map_fy map_fx pflip flipmask seed step d_step row_global0"
+
+
+class ElasticApply(namedtuple("ElasticApply", "x x_row0 d_row0 out N C " + _ELASTIC_SAMPLE)):
+    def source(self, out=None):
+        """Where the images come from and where the resampled ones go (``out``: elsewhere)."""
+        return self.x, self.x_row0, self.d_row0, self.out if out is None else out
+
+    def sample(self):
+        """The image size and what says which pixel goes where: the sample map, the inversion, the flip noise."""
+        return tuple(getattr(self, f) for f in _ELASTIC_SAMPLE.split())
 
 
 class InputSlot:
@@ -250,19 +266,19 @@ class ElasticLayer(Layer):
                     self._field(self._maps[self._cur])
             self._pre_valid = False
         # arguments of the resampling (tn_elastic_apply / the conv block it may be fused into)
-        self._apply_args = (x_ptr, row0, d_row0_ptr, self.output.ptr, self.batch_sz, self.num_maps, h, w,
-                            int(self.invert), int(self.nearest),
-                            self.map_idx.ptr if self.has_field else None,
-                            self.map_fy.ptr, self.map_fx.ptr,
-                            float(self.pflip) if self._inj_flip is None else 0.0,
-                            self._inj_flip.ptr if self._inj_flip is not None else None,
-                            self.seed, 0, d_step_ptr, rg0)
+        self._apply_args = ElasticApply(
+            x=x_ptr, x_row0=row0, d_row0=d_row0_ptr, out=self.output.ptr, N=self.batch_sz, C=self.num_maps, h=h, w=w,
+            invert=int(self.invert), nearest=int(self.nearest),
+            map_idx=self.map_idx.ptr if self.has_field else None, map_fy=self.map_fy.ptr, map_fx=self.map_fx.ptr,
+            pflip=float(self.pflip) if self._inj_flip is None else 0.0,
+            flipmask=self._inj_flip.ptr if self._inj_flip is not None else None,
+            seed=self.seed, step=0, d_step=d_step_ptr, row_global0=rg0)
         if self.fused_conv is not None and train:
             return                      # the conv block's forward resamples while it loads (PoolLayer)
         if self._c8_consumer is not None:
             # 16-bit stack: straight into the c8 tensor of the first conv layer (same values, rounded when stored)
             a = self._apply_args
-            self.ctx.call("tn_c8_elastic_apply", *(a[:3] + (self._c8_consumer.x16.ptr,) + a[4:]))
+            self.ctx.call("tn_c8_elastic_apply", *a.source(out=self._c8_consumer.x16.ptr), a.N, a.C, *a.sample())
             return
         self.ctx.call("tn_elastic_apply", *self._apply_args)
 
@@ -278,9 +294,8 @@ class ElasticLayer(Layer):
             self.gin = self.ctx.empty(self.inpt.shape)
         h = w = self.img_sz
         if self.active:
-            a = self._apply_args
-            self.ctx.call("tn_elastic_apply_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps, h, w,
-                          a[8], a[9], a[10], a[11], a[12], a[13], a[14], a[15], a[16], a[17], a[18], b_ptr, b_act, b_prm)
+            self.ctx.call("tn_elastic_apply_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps,
+                          *self._apply_args.sample(), b_ptr, b_act, b_prm)
         else:
             self.ctx.call("tn_elastic_apply_bwd", gout.ptr, self.gin.ptr, self.batch_sz, self.num_maps, h, w,
                           int(self.invert), 1, None, None, None, 0.0, None, 0, 0, None, 0, b_ptr, b_act, b_prm)

@@ -26,6 +26,7 @@ from .dpsched import DpSchedule
 from .plan import StepPlan
 from .device import DeviceArray, get_context, is_c8, share
 from .layer.c8 import OperandTiles, check_follows
+from .layer.convpool import pool_mask_enabled
 from .layer import (AuxConcatLayer, SoftAuxLayer, CenteredOutLayer, ColorLayer, ConvLayer, DropOutLayer, ElasticLayer, ExpLossLayer, HiddenLayer,
                     HingeLayer, InputLayer, InputSlot, MeanLayer, OutputLayer, PoolLayer, SoftmaxLayer)
 
@@ -360,9 +361,9 @@ class NeuralNet():
         """Pair every ConvLayer that is directly followed by a 2x2 PoolLayer (and is small
         enough for the register-resident kernel) into one fused conv+act+pool launch."""
         for conv, pool in zip(lyrs[:-1], lyrs[1:]):
-            if isinstance(conv, ConvLayer) and isinstance(pool, PoolLayer) \
-                    and conv.can_fuse_with(pool):
-                conv.fused_pool, pool.fused_conv = pool, conv
+            family = conv.can_fuse_with(pool) if isinstance(conv, ConvLayer) and isinstance(pool, PoolLayer) else None
+            if family:
+                conv.fuse(pool, family)
         # 16-bit stack: the first conv layer packs its c8 input straight from the dataset window
         if len(lyrs) >= 2 and isinstance(lyrs[0], InputLayer) and isinstance(lyrs[1], ConvLayer) and lyrs[1].f16:
             lyrs[1]._pack_from, lyrs[0]._packed_by_conv = lyrs[0].inpt, True
@@ -461,7 +462,7 @@ class NeuralNet():
                 # every rank (a rank with another TN_C8_WSLAB_DIV or another device would round differently, silently)
                 import zlib
                 sig = "|".join("%s=%s" % kv for kv in self.ctx.knobs().items())
-                sig += "".join("|%s=%s" % (k, os.environ.get(k, "")) for k in ("TN_POOL_MASK", "TN_MN_FUSED"))
+                sig += "|TN_POOL_MASK=%d|TN_MN_FUSED=%s" % (pool_mask_enabled(), os.environ.get("TN_MN_FUSED", ""))
                 sig += "|cus=%s" % self.ctx.info()[1]
                 comm.agree(float(zlib.crc32(sig.encode())), "the kernel tunables / CU count (%s)" % sig)
         self.dp.prepare(slots, host)
@@ -858,9 +859,7 @@ class NeuralNet():
         for index in get_output_of_layers:          # a requested conv map must be materialised
             lyr = self.te_layers[index]
             if isinstance(lyr, ConvLayer) and lyr.fused_pool is not None:
-                assert not lyr.f16, "DTYPE {}: the conv map of a fused conv + pool block is never materialised".format(
-                    lyr.c8_dtype)
-                lyr.fused_pool.fused_conv, lyr.fused_pool = None, None
+                lyr.unfuse()
 
         def fn(x, aux=None):
             with self._at_avg_wts(averaged):
