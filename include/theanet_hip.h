@@ -420,6 +420,14 @@ int tn_convblock_bwd_mask(tn_ctx* ctx, const float* x, const float* W, const flo
                           const float* y, const uint8_t* mask, float* dx, float* dW, float* db,
                           int N, int C, int H, int Wd, int K, int f, int pad_lo, int Ho, int Wo,
                           int p, int Hp, int Wp, int act, float act_param);
+/* The kernel's lane set-up (tile offsets, window table, the filter operand's sources and validity)
+ * depends on the geometry alone and comes from a device table the context owns, one per geometry,
+ * freed with the context.  tn_convblock_table builds the table of a supported geometry unless the
+ * context has it, and returns when it is complete in device memory (a blocking copy, no stream
+ * work).  tn_convblock_bwd_mask entered cold does the same; a caller that captures a graph or runs
+ * two steps side by side calls this first (ConvLayer._block_route does, when it picks the route). */
+int tn_convblock_table(tn_ctx* ctx, int C, int H, int Wd, int K, int f, int pad_lo, int Ho, int Wo,
+                       int p, int Hp, int Wp);
 
 /* ---- pool / mean (replaces pool.pool_2d + MaxPoolGrad, tt.mean; convpool.py:106-107,131) ----
  * max over p x p, stride p, no padding; Ho = ceil(H/p) unless ignore_border (floor).   */

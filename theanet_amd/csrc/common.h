@@ -36,6 +36,15 @@ struct tn_red_rec {
     uint32_t n, S, stride, flip;
 };
 
+// one geometry's lane table of the matrix-core conv-block backwards (convblock_mfma.hip: cm_table builds, looks up and
+// frees them).  The context owns the list; a table lives as long as the context, because a captured graph may hold its
+// address.
+struct tn_cm_tab {
+    int key[9];                            // C, H, Wd, K, pad, Ho, Wo, Hp, Wp
+    int* dev;
+    tn_cm_tab* next;
+};
+
 struct tn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream ops are currently issued on
@@ -85,6 +94,7 @@ struct tn_ctx {
     // sums and, at wc_part[k][-4 .. -1] (a 16-byte block of its own at the allocation's start), the finishing ticket
     float* wc_part[2] = {nullptr, nullptr};
     size_t wc_cap[2] = {0, 0};             // partials the array holds
+    tn_cm_tab* cm_tabs = nullptr;          // lane tables of the conv-block backwards, one per geometry seen (newest first)
     // a light independent job waiting for a heavy launch to ride in (tn_rider_elastic_field)
     bool rider_valid = false;
     ElField rider;
@@ -220,6 +230,7 @@ int tn_convblock_mfma_supported(int C, int K, int f, int stride, int p, int H, i
 int tn_convblock_mfma_bwd(tn_ctx* ctx, const float* x, const float* W, const float* b, const float* g, float* dx, float* dW,
                           float* db, int N, int C, int H, int Wd, int K, int pad_lo, int Ho, int Wo, int Hp, int Wp, int act,
                           float act_param);
+void tn_cm_tables_free(tn_ctx* ctx);       // tn_ctx_destroy: the context's lane tables
 int tn_red_flush(tn_ctx* ctx);
 int tn_red_flush_inc(tn_ctx* ctx, uint32_t* inc);
 

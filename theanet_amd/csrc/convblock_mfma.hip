@@ -22,6 +22,8 @@
 // into registers while the current one is computed.  HBM traffic: x, g read once, dx written once.
 #include "common.h"
 
+#include <algorithm>
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define CM_XR 12        // prefetch registers per lane for x (C*H*W <= 64*CM_XR) and for g (K*Hp*Wp)
@@ -70,15 +72,72 @@ __device__ __forceinline__ float cm_bit_and(int m, float v) {
     return __int_as_float(s & __float_as_int(v));
 }
 
-// n / d for 0 <= n < 2^16 given rd = 1/d to 1 ulp (exact: (n + .5) / d stays >= .5/d away from
-// the next integer, far more than the rounding of the product)
-__device__ __forceinline__ int cm_div(int n, float rd) { return __float2int_rz(((float)n + .5f) * rd); }
+// ---- the lane table of a geometry -------------------------------------------------------------------------------------
+// What a wave's set-up needs beyond its own wave number is a function of (lane, C, H, Wd, K, pad, Ho, Wo, Hp, Wp) alone:
+// the same in every wave, launch and step of a net.  cm_table (below, host) computes it once per geometry into device
+// memory the context owns; the kernels' set-up is coalesced loads of it ([entry][lane]).  Ints:
+//   TABR [CM_XR][64]  image element lane + 64 j -> its cell of the x / dx tile (elements beyond C*H*W: the last one's)
+//   DZO  [CM_XR][64]  pooled element lane + 64 j = (k, window) -> its 4 dz cells (beyond K*Hp*Wp: the last one's)
+//   AOFF [CM_AW][64]  dgrad A operand Aw2[mt][s] (entry mt * KS2 + s): byte offset in W of the flipped, clamped source
+//   AMSK [64]         ... and bit e set where entry e's filter / channel / tap exists (clear: the operand is +0.0); one
+//                     word per lane, because CM_AW masks held beside the operands cost the widest forms registers
+//   WTAB [3][tabf]    window -> x tile offset of its top-left: in floats, in bytes (W44), and the recompute kernel's
+//                     (offset << 4) | valid bits
+// Only the VALUES of W change from step to step; they are gathered through AOFF in every launch.
+#define CM_AW 24         // filter-operand entries per lane: 3 dgrad row tiles x ceil(K / 4) <= 8 reduction steps
+#define CM_TB_TABR 0
+#define CM_TB_DZO (64 * CM_XR)
+#define CM_TB_AOFF (128 * CM_XR)
+#define CM_TB_AMSK (CM_TB_AOFF + 64 * CM_AW)
+#define CM_TB_WTAB (CM_TB_AMSK + 64)
+#define CM_WT_FLOATS 0
+#define CM_WT_BYTES 1
+#define CM_WT_VALID 2
+
+// The set-up's first loads go out ahead of the first image's prefetch (CM_TAB_FENCE between the two), and that prefetch
+// is unconditional: the vector-memory counter retires in order and the compiler counts along one path, so the waits in
+// front of the window table's store and of the filter gathers name these loads alone and leave the image in flight.
+// They are the lane's filter-operand sources and the thread's window-table entry; tabr / dzo, which only the staging
+// needs, follow the gathers (CM_TAB_LANE), so that no more than the counter's 64 loads are ever wanted in flight.
+#define CM_TAB_HEAD(FORM_)                                                                          \
+    unsigned tlb = 4 * lane;                                                                        \
+    asm volatile("" : "+v"(tlb));      /* one lane offset (bytes) on the scalar base, the entries are immediates */ \
+    unsigned awo[NTD * KS2];   /* (unsigned: a scalar base plus a 32-bit lane offset, no 64-bit address per gather) */ \
+    _Pragma("unroll") for (int e = 0; e < NTD * KS2; ++e) awo[e] = CM_TL(CM_TB_AOFF + 64 * e);        \
+    const int awm = CM_TL(CM_TB_AMSK);                                                              \
+    const int* const wsrc = tab + CM_TB_WTAB + (FORM_) * q.tabf;                                    \
+    const int wt0 = wsrc[min((int)threadIdx.x, 4 * q.PT - 1)];
+#define CM_TL(E_) (*reinterpret_cast<const int*>(reinterpret_cast<const char*>(tab) + (size_t)tlb + 4 * (E_)))
+#define CM_TAB_FENCE() __builtin_amdgcn_sched_barrier(0)
+// ... the window table's way into LDS (before the block's first barrier; the second line: more than 256 windows) ...
+#define CM_TAB_WTAB()                                                                               \
+    wtab[min((int)threadIdx.x, 4 * q.PT - 1)] = wt0;       /* (every thread: a test would take the load with it) */ \
+    _Pragma("unroll 1") for (int i = threadIdx.x + 256; i < 4 * q.PT; i += 256) wtab[i] = wsrc[i];
+// ... the 15-odd filter gathers, back to back ...
+#define CM_TAB_GATHER()                                                                             \
+    float Aw2[NTD][KS2];       /* dgrad product A operand: Wf[k = 4s+qd][c = lo>>2][ab = 4mt + (lo&3)] */ \
+    _Pragma("unroll") for (int mt = 0; mt < NTD; ++mt)                                              \
+        _Pragma("unroll") for (int s = 0; s < KS2; ++s)                                             \
+            Aw2[mt][s] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(W) + awo[mt * KS2 + s]); \
+    CM_TAB_FENCE();
+// ... the lane's staging offsets behind them ...
+#define CM_TAB_LANE(DST_, SEC_)                                                                     \
+    _Pragma("unroll") for (int j = 0; j < CM_XR; ++j) DST_[j] = CM_TL((SEC_) + 64 * j);
+// ... and, behind the set-up's one wait, the operand: bits(W value) & (0 / -1 from the entry's bit), +0.0 where the bit
+// is clear; pinned
+#define CM_TAB_OPERAND()                                                                            \
+    _Pragma("unroll") for (int mt = 0; mt < NTD; ++mt)                                              \
+        _Pragma("unroll") for (int s = 0; s < KS2; ++s) {                                           \
+            Aw2[mt][s] = __int_as_float(__float_as_int(Aw2[mt][s]) & ((awm << (31 - (mt * KS2 + s))) >> 31)); \
+            asm volatile("" : "+v"(Aw2[mt][s]));                                                    \
+        }
 
 template <int C, int KS2, int ACT>      // KS2 = ceil(K / 4): reduction steps of the dgrad product
 __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
     const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ b,
     const float* __restrict__ g, float* __restrict__ dx, float* __restrict__ partial,
-    float* __restrict__ dbpartial, CmGeom q, int act, float prm, float* __restrict__ tdbg) {
+    float* __restrict__ dbpartial, const int* __restrict__ tab, CmGeom q, int act, float prm,
+    float* __restrict__ tdbg) {
     constexpr int F = 3, FF = 9, CKK = C * FF;
     constexpr int KS1 = (CKK + 3) / 4;        // reduction steps of the conv product
     constexpr int NT = (CKK + 16) / 16;       // 16-wide ckk tiles incl. the bias column ckk == CKK
@@ -92,7 +151,9 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
 #define CM_STAMP() if (tdbg && blockIdx.x == (q.dbg >> 8) && threadIdx.x == 0 && ts_ < 20) tdbg[ts_++] = (float)(__builtin_readcyclecounter() - t0_)
     const int K = q.K, HW = q.H * q.Wd, CHW = C * HW, HpWp = q.Hp * q.Wp, KHW = K * HpWp;
 
-    // the first image starts travelling before anything else
+    CM_TAB_HEAD(CM_WT_VALID);
+    CM_TAB_FENCE();
+    // the first image starts travelling right behind them (a wave without one fetches the last image: see CM_TAB_HEAD)
     const int gw = blockIdx.x * 4 + wv, nw = gridDim.x * 4;
     float xr[CM_XR], gr[CM_XR];
     // the image index is wave-uniform: scalar base + per-lane 32-bit offset addressing
@@ -106,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
         }                                                                                   \
     }
     int n = __builtin_amdgcn_readfirstlane(gw);
-    if (n < q.N) CM_PREFETCH(n);
+    CM_PREFETCH(min(n, q.N - 1));
 
     int* wtab = reinterpret_cast<int*>(sm);           // [4*PT] window -> (tile offset << 4) | valid bits
     float* wbase = sm + q.tabf + wv * q.wavef;
@@ -117,15 +178,7 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
     const int ZERO = q.xf - 4, ONE = q.xf - 3;        // constant cells behind the x tile
     const int DUMMY = q.xf - 2;                       // write-only cell for out-of-range lanes
 
-    for (int i = threadIdx.x; i < 4 * q.PT; i += 256) {
-        int e = 0;
-        if (i < HpWp) {
-            const int wy = i / q.Wp, wx = i - wy * q.Wp;
-            const bool vx = 2 * wx + 1 < q.Wo, vy = 2 * wy + 1 < q.Ho;
-            e = ((2 * wy * q.Wx + 2 * wx) << 4) | 1 | (vx ? 2 : 0) | (vy ? 4 : 0) | (vx && vy ? 8 : 0);
-        }
-        wtab[i] = e;
-    }
+    CM_TAB_WTAB();
     // x tile: the pads stay zero for the whole kernel.  dz tile: phase 1 rewrites every pixel cell of
     // the rows < K for each image; the 4 pad cells of each row and the rows K..4*KS2-1 stay zero.
     for (int i = lane * 4; i < q.xf; i += 256) *reinterpret_cast<float4*>(sx + i) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -162,37 +215,29 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mfma(
         off3[nt] = ckk < CKK ? ckk_off(ckk) : (ckk == CKK ? ONE : ZERO);
         msk3[nt] = ckk < CKK ? -1 : 0;
     }
-    float Aw2[NTD][KS2];       // dgrad product A operand: Wf[k = 4s+qd][c = lo>>2][ab = 4mt + (lo&3)]
-#pragma unroll
-    for (int mt = 0; mt < NTD; ++mt)
-#pragma unroll
-        for (int s = 0; s < KS2; ++s) Aw2[mt][s] = wf(4 * s + qd, lo >> 2, 4 * mt + (lo & 3));
+    CM_TAB_GATHER();
+    int tabr[CM_XR];           // image element lane+64j -> offset in the x / dx tile
+    CM_TAB_LANE(tabr, CM_TB_TABR);
     float bk[NKT];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) bk[kt] = b[min(16 * kt + lo, K - 1)];
-    int tabr[CM_XR];           // image element lane+64j -> offset in the x / dx tile
-    const float rHW = __builtin_amdgcn_rcpf((float)HW), rWd = __builtin_amdgcn_rcpf((float)q.Wd);
-#pragma unroll
-    for (int j = 0; j < CM_XR; ++j) {
-        const int i = min(lane + 64 * j, CHW - 1);
-        const int c = cm_div(i, rHW), r = i - c * HW, y = cm_div(r, rWd), xx = r - y * q.Wd;
-        tabr[j] = (lane + 64 * j < CHW) ? c * q.xplane + (y + q.pad) * q.Wx + xx + q.pad : DUMMY;
-    }
     // Pin the operands: they are complete here, so the tile loops never wait on the vector-memory
     // counter and the image prefetch below stays in flight across them.
     CM_STAMP();
+    CM_TAB_FENCE();                         // (everything that needs no load is done before it)
     __builtin_amdgcn_s_waitcnt(0x0f70);     // vmcnt(0)
     CM_STAMP();
 #pragma unroll
     for (int s = 0; s < KS1; ++s)
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) asm volatile("" : "+v"(Bw1[kt][s]));
-#pragma unroll
-    for (int mt = 0; mt < NTD; ++mt)
-#pragma unroll
-        for (int s = 0; s < KS2; ++s) asm volatile("" : "+v"(Aw2[mt][s]));
+    CM_TAB_OPERAND();
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) asm volatile("" : "+v"(bk[kt]));
+    // (the table's entry of an element beyond the image is the last element's cell: this kernel parks those lanes'
+    // copies in a write-only cell, its copy-out tests the element)
+#pragma unroll
+    for (int j = 0; j < CM_XR; ++j) tabr[j] = lane + 64 * j < CHW ? tabr[j] : DUMMY;
 
     f32x4 accW[NKT][NT];
 #pragma unroll
@@ -395,8 +440,8 @@ template <int C, int KS2, int ACT, bool W44>
 __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ g,
     const float* __restrict__ y, const uint8_t* __restrict__ mask, float* __restrict__ dx,
-    float* __restrict__ partial, float* __restrict__ dbpartial, CmGeom q, int act, float prm,
-    float* __restrict__ tdbg) {
+    float* __restrict__ partial, float* __restrict__ dbpartial, const int* __restrict__ tab, CmGeom q, int act,
+    float prm, float* __restrict__ tdbg) {
     constexpr int F = 3, FF = 9, CKK = C * FF;
     constexpr int NKT = (KS2 + 3) / 4;        // 16-wide filter tiles
     constexpr int NT = (CKK + 16) / 16;       // 16-wide ckk tiles incl. the bias column ckk == CKK
@@ -409,6 +454,8 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
 #define CM_STAMP() if (tdbg && blockIdx.x == (q.dbg >> 8) && threadIdx.x == 0 && ts_ < 20) tdbg[ts_++] = (float)(__builtin_readcyclecounter() - t0_)
     const int K = q.K, HW = q.H * q.Wd, CHW = C * HW, HpWp = q.Hp * q.Wp, KHW = K * HpWp;
 
+    CM_TAB_HEAD(W44 ? CM_WT_BYTES : CM_WT_FLOATS);
+    CM_TAB_FENCE();
     const int gw = blockIdx.x * 4 + wv, nw = gridDim.x * 4;
     float xr[CM_XR], gr[CM_XR], yr[CM_XR];
     int mr[CM_XR];
@@ -426,9 +473,9 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
         }                                                                                   \
     }
     int n = __builtin_amdgcn_readfirstlane(gw);
-    if (n < q.N) CM_PREFETCH(n);
+    CM_PREFETCH(min(n, q.N - 1));     // (a wave without an image fetches the last one: see CM_TAB_HEAD)
 
-    int* wtab = reinterpret_cast<int*>(sm);           // [4*PT] window -> x tile offset of its top-left
+    int* wtab = reinterpret_cast<int*>(sm);           // [4*PT] window -> x tile offset of its top-left (W44: in bytes)
     float* wbase = sm + q.tabf + wv * q.wavef;
     float* sx = wbase;                                // x tile (zero padded)
     float* sdx = sx + q.xf;                           // dx tile
@@ -436,15 +483,17 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     const int ZERO = q.xf - 4, ONE = q.xf - 2;        // constant cells behind the x tile, two of each: a lane that reads a
                                                       // constant shares the live lanes' +1 offsets
 
-    for (int i = threadIdx.x; i < 4 * q.PT; i += 256) {
-        const int w = min(i, HpWp - 1);
-        const int wy = w / q.Wp, wx = w - wy * q.Wp;
-        wtab[i] = (2 * wy * q.Wx + 2 * wx) * (W44 ? 4 : 1);          // (W44: in bytes)
-    }
+    CM_TAB_WTAB();
     // x tile: the pads stay zero for the whole kernel.  dz tile: the staging rewrites the cells of
     // the K x Hp*Wp windows for each image; everything else (tile padding, rows >= K) stays zero.
     for (int i = lane * 4; i < q.xf; i += 256) *reinterpret_cast<float4*>(sx + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = lane * 4; i < q.dzf + 4; i += 256) *reinterpret_cast<float4*>(sdz + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    CM_TAB_GATHER();
+    int tabr[CM_XR];           // image element lane+64j -> offset in the x / dx tile (the prefetch clamps alike: the
+                               // lanes beyond the image hold, and stage, the last element once more)
+    int dzo[CM_XR];            // pooled element lane+64j = (k, window) -> its 4 dz cells
+    CM_TAB_LANE(tabr, CM_TB_TABR);
+    CM_TAB_LANE(dzo, CM_TB_DZO);
     __syncthreads();
     if (lane < 2) sx[ONE + lane] = 1.f;
 
@@ -504,35 +553,10 @@ __global__ __launch_bounds__(256, 2) void convblock_bwd_mask_mfma(
     f32x4 accM[KS2], accR[KS2];
 #pragma unroll
     for (int a_ = 0; a_ < KS2; ++a_) accM[a_] = accR[a_] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float Aw2[NTD][KS2];       // dgrad product A operand: Wf[k = 4s+qd][c = lo>>2][ab = 4mt + (lo&3)]
-#pragma unroll
-    for (int mt = 0; mt < NTD; ++mt)
-#pragma unroll
-        for (int s = 0; s < KS2; ++s) {
-            const int k = 4 * s + qd, c = lo >> 2, ab = 4 * mt + (lo & 3);
-            const float v = W[((size_t)min(k, K - 1) * C + min(c, C - 1)) * FF + (FF - 1 - min(ab, FF - 1))];
-            Aw2[mt][s] = (k < K && c < C && ab < FF) ? v : 0.f;
-        }
-    int tabr[CM_XR];           // image element lane+64j -> offset in the x / dx tile (the prefetch clamps alike: the
-                               // lanes beyond the image hold, and stage, the last element once more)
-    int dzo[CM_XR];            // pooled element lane+64j = (k, window) -> its 4 dz cells
-    const float rHW = __builtin_amdgcn_rcpf((float)HW), rWd = __builtin_amdgcn_rcpf((float)q.Wd);
-    const float rHpWp = __builtin_amdgcn_rcpf((float)HpWp);
-#pragma unroll
-    for (int j = 0; j < CM_XR; ++j) {
-        const int i = min(lane + 64 * j, CHW - 1);
-        const int c = cm_div(i, rHW), r = i - c * HW, yy = cm_div(r, rWd), xx = r - yy * q.Wd;
-        tabr[j] = c * q.xplane + (yy + q.pad) * q.Wx + xx + q.pad;      // lanes beyond C*H*W: the last element's cell
-        const int e = min(lane + 64 * j, KHW - 1);
-        const int k = cm_div(e, rHpWp), w = e - k * HpWp;
-        dzo[j] = k * q.npixp + 4 * w;       // lanes beyond K*Hp*Wp rewrite the last element's cells
-    }
-    // Pin the operands: complete here, so the loops below never wait on the vector-memory counter
+    // The set-up's one wait.  Pin the operands: complete here, so the loops below never wait on the vector-memory counter
+    CM_TAB_FENCE();                         // (everything that needs no load is done before it)
     __builtin_amdgcn_s_waitcnt(0x0f70);     // vmcnt(0)
-#pragma unroll
-    for (int mt = 0; mt < NTD; ++mt)
-#pragma unroll
-        for (int s = 0; s < KS2; ++s) asm volatile("" : "+v"(Aw2[mt][s]));
+    CM_TAB_OPERAND();
 
     f32x4 accW[NKT][NT];
 #pragma unroll
@@ -835,6 +859,77 @@ int tn_convblock_mfma_supported(int C, int K, int f, int stride, int p, int H, i
     return cm_supported(C, K, f, stride, p, H, Wd, pad_lo, Ho, Wo, Hp, Wp, true);
 }
 
+// The lane table of a geometry (layout: above the kernels), in the integer expressions the kernels' set-up used to
+// evaluate per wave.  A hit is a walk over the context's few tables; a miss builds one and returns only when it is
+// complete in device memory (a blocking copy), so that both streams of the two-step schedule and a later graph capture
+// only ever read a finished table.  Tables are never evicted: a launch in flight or a captured graph may read any of them,
+// a net has a few such blocks, and one is about 13 KB.  A miss during a stream capture fails (allocation and copy are not
+// stream work): whoever captures calls tn_convblock_table first.
+static int cm_table(tn_ctx* ctx, int C, const CmGeom& q, const int** out) {
+    const int key[9] = {C, q.H, q.Wd, q.K, q.pad, q.Ho, q.Wo, q.Hp, q.Wp};
+    for (const tn_cm_tab* t = ctx->cm_tabs; t; t = t->next)
+        if (!memcmp(t->key, key, sizeof(key))) {
+            *out = t->dev;
+            return TN_OK;
+        }
+    const int K = q.K, HW = q.H * q.Wd, CHW = C * HW, HpWp = q.Hp * q.Wp, KHW = K * HpWp;
+    const size_t n = CM_TB_WTAB + 3 * (size_t)q.tabf;
+    int* h = new int[n]();
+    for (int j = 0; j < CM_XR; ++j)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int i = std::min(lane + 64 * j, CHW - 1);
+            const int c = i / HW, r = i - c * HW, yy = r / q.Wd, xx = r - yy * q.Wd;
+            h[CM_TB_TABR + 64 * j + lane] = c * q.xplane + (yy + q.pad) * q.Wx + xx + q.pad;
+            const int e = std::min(lane + 64 * j, KHW - 1);
+            const int k = e / HpWp, w = e - k * HpWp;
+            h[CM_TB_DZO + 64 * j + lane] = k * q.npixp + 4 * w;
+        }
+    const int KS2 = (K + 3) / 4;
+    for (int mt = 0; mt < 3; ++mt)
+        for (int s = 0; s < KS2; ++s)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int lo = lane & 15, qd = lane >> 4;
+                const int k = 4 * s + qd, c = lo >> 2, ab = 4 * mt + (lo & 3);
+                const int src = (std::min(k, K - 1) * C + std::min(c, C - 1)) * 9 + (8 - std::min(ab, 8));
+                h[CM_TB_AOFF + 64 * (mt * KS2 + s) + lane] = 4 * src;
+                if (k < K && c < C && ab < 9) h[CM_TB_AMSK + lane] |= 1 << (mt * KS2 + s);
+            }
+    for (int i = 0; i < 4 * q.PT; ++i) {
+        const int w = std::min(i, HpWp - 1);
+        const int wy = w / q.Wp, wx = w - wy * q.Wp, off = 2 * wy * q.Wx + 2 * wx;
+        const bool vx = 2 * wx + 1 < q.Wo, vy = 2 * wy + 1 < q.Ho;
+        h[CM_TB_WTAB + CM_WT_FLOATS * q.tabf + i] = off;
+        h[CM_TB_WTAB + CM_WT_BYTES * q.tabf + i] = 4 * off;
+        h[CM_TB_WTAB + CM_WT_VALID * q.tabf + i] =
+            i < HpWp ? (off << 4) | 1 | (vx ? 2 : 0) | (vy ? 4 : 0) | (vx && vy ? 8 : 0) : 0;
+    }
+    int* dev = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, n * sizeof(int));
+    if (e == hipSuccess) {
+        e = hipMemcpy(dev, h, n * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) hipFree(dev);
+    }
+    delete[] h;
+    if (e != hipSuccess)
+        return tn_fail(ctx, TN_E_HIP, "conv-block lane table (C=%d K=%d %dx%d): %s", C, K, q.H, q.Wd, hipGetErrorString(e));
+    tn_cm_tab* t = new tn_cm_tab;
+    memcpy(t->key, key, sizeof(key));
+    t->dev = dev;
+    t->next = ctx->cm_tabs;
+    ctx->cm_tabs = t;
+    *out = dev;
+    return TN_OK;
+}
+
+void tn_cm_tables_free(tn_ctx* ctx) {
+    while (ctx->cm_tabs) {
+        tn_cm_tab* t = ctx->cm_tabs;
+        ctx->cm_tabs = t->next;
+        hipFree(t->dev);
+        delete t;
+    }
+}
+
 // one block per four images, at most two per CU; a weight-gradient slab per block
 static int cm_blocks(tn_ctx* ctx, int N) {
     const int nblk = 2 * ctx->num_cus;
@@ -849,9 +944,12 @@ static int launch_cm(tn_ctx* ctx, const float* x, const float* W, const float* b
     float *partial, *dbpartial;
     int rc = conv_slabs(ctx, nblk, (size_t)q.K * C * 9, q.K, &partial, &dbpartial);
     if (rc) return rc;
+    const int* tab;
+    rc = cm_table(ctx, C, q, &tab);
+    if (rc) return rc;
     float* tdbg = (q.dbg & 16) ? db : nullptr;
 #define CM_L(ACT_) \
-    tn_launch_lds<convblock_bwd_mfma<C, KS2, ACT_>>(ctx, nblk, 256, lds, x, W, b, g, dx, partial, dbpartial, q, act, prm, tdbg)
+    tn_launch_lds<convblock_bwd_mfma<C, KS2, ACT_>>(ctx, nblk, 256, lds, x, W, b, g, dx, partial, dbpartial, tab, q, act, prm, tdbg)
     rc = act == TN_ACT_LEAKY ? CM_L(TN_ACT_LEAKY) : CM_L(-1);
 #undef CM_L
     if (rc) return rc;
@@ -869,10 +967,13 @@ static int launch_cm_mask(tn_ctx* ctx, const float* x, const float* W, const flo
     float *partial, *dbpartial;
     int rc = conv_slabs(ctx, nblk, (size_t)q.K * C * 9, q.K, &partial, &dbpartial);
     if (rc) return rc;
+    const int* tab;
+    rc = cm_table(ctx, C, q, &tab);
+    if (rc) return rc;
     float* tdbg = (q.dbg & 16) ? db : nullptr;
 #define CM_L(ACT_, W44_)                                                                                       \
     tn_launch_lds<convblock_bwd_mask_mfma<C, KS2, ACT_, W44_>>(ctx, nblk, 256, lds, x, W, g, y, mask, dx, partial, \
-                                                               dbpartial, q, act, prm, tdbg)
+                                                               dbpartial, tab, q, act, prm, tdbg)
     if (act == TN_ACT_LEAKY && tn_knob(TN_K_CB_W44)) rc = CM_L(TN_ACT_LEAKY, true);
     else if (act == TN_ACT_LEAKY) rc = CM_L(TN_ACT_LEAKY, false);
     else rc = CM_L(-1, false);
@@ -902,6 +1003,15 @@ static int launch_cm_mask(tn_ctx* ctx, const float* x, const float* W, const flo
 extern "C" int tn_convblock_mask_supported(int C, int K, int f, int stride, int p, int H, int Wd,
                                            int pad_lo, int Ho, int Wo, int Hp, int Wp) {
     return cm_supported(C, K, f, stride, p, H, Wd, pad_lo, Ho, Wo, Hp, Wp, false);
+}
+
+extern "C" int tn_convblock_table(tn_ctx* ctx, int C, int H, int Wd, int K, int f, int pad_lo, int Ho, int Wo, int p,
+                                  int Hp, int Wp) {
+    TN_REQUIRE(ctx, "tn_convblock_table: null context");
+    TN_REQUIRE(tn_convblock_mask_supported(C, K, f, 1, p, H, Wd, pad_lo, Ho, Wo, Hp, Wp),
+               "tn_convblock_table: unsupported C=%d K=%d f=%d p=%d %dx%d", C, K, f, p, H, Wd);
+    const int* tab;
+    return cm_table(ctx, C, cm_geometry(0, C, H, Wd, K, pad_lo, Ho, Wo, Hp, Wp, 0), &tab);
 }
 
 extern "C" int tn_convblock_bwd_mask(tn_ctx* ctx, const float* x, const float* W, const float* g,

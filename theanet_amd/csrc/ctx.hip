@@ -60,6 +60,7 @@ int tn_ctx_destroy(tn_ctx* ctx) {
     hipStreamSynchronize(ctx->streams[0]);
     hipStreamSynchronize(ctx->streams[1]);
     if (ctx->scratch) hipFree(ctx->scratch);
+    tn_cm_tables_free(ctx);
     for (int i = 0; i < 2; ++i) {
         if (ctx->scratch_slot[i]) hipFree(ctx->scratch_slot[i]);
         if (ctx->tmp[i]) hipFree(ctx->tmp[i]);

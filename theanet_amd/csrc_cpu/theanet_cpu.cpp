@@ -436,6 +436,7 @@ int tn_convblock_bwd_mask(tn_ctx* ctx, const float*, const float*, const float*,
                           float*, float*, int, int, int, int, int, int, int, int, int, int, int, int, int, float) {
     NOT_HERE("tn_convblock_bwd_mask");
 }
+int tn_convblock_table(tn_ctx* ctx, int, int, int, int, int, int, int, int, int, int, int) { NOT_HERE("tn_convblock_table"); }
 int tn_elastic_convpool_supported(int, int, int, int, int, int, int, int, int, int) { return 0; }
 int tn_elastic_convpool_fwd_mask(tn_ctx* ctx, const float*, int64_t, const int64_t*, float*, int, int, int, int, int,
                                  const int32_t*, const float*, const float*, float, const uint8_t*, uint64_t, uint32_t,

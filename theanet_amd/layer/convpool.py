@@ -7,6 +7,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from .. import _lib
 from ..device import C8_DTYPES, C8Array, c8_pitch, is_c8
 from .c8 import DenseDetour, conv_family
 from .layer import Layer, activation_by_name, below_info
@@ -267,6 +268,11 @@ class ConvLayer(Layer):
             one = self.stride == 1 and lib.tn_convblock_mask_supported(g.C, g.K, g.f, self.stride, g.p, g.H, g.W, g.pad,
                                                                        g.Ho, g.Wo, g.Hp, g.Wp) and not below_act
             route = ("tn_convblock_bwd_mask", True) if one else ("tn_convpool_bwd_mask", False)
+            if one:
+                # its lane table, complete before the first launch (two steps in flight, a graph capture) reads it.  Host
+                # work like an allocation on first use, not a call of the step's schedule: not through ctx.call
+                _lib.check(self.ctx.h, lib.tn_convblock_table(self.ctx.h, g.C, g.H, g.W, g.K, g.f, g.pad, g.Ho, g.Wo, g.p,
+                                                             g.Hp, g.Wp), "tn_convblock_table")
         elif lib.tn_convblock_supported(g.C, g.K, g.f, self.stride, g.p, g.Ho, g.Wo) and not below_act:
             route = ("tn_convblock_bwd", True)       # LDS-resident recompute: dW, db AND dx in one kernel
         else:
