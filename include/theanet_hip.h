@@ -314,6 +314,29 @@ int tn_c8_dropout_fwd(tn_ctx* ctx, const void* x, void* y, uint8_t* mask8, int N
                       uint64_t seed, uint32_t step, const uint32_t* d_step, uint64_t elem0, int draw);
 int tn_c8_dropout_bwd(tn_ctx* ctx, const void* gout, const uint8_t* mask8, void* gin, int N, int C, int S, int P);
 int tn_c8_scale(tn_ctx* ctx, const void* x, void* y, int N, int C, int S, int P, float scale);
+/* A stand-alone PoolLayer on a c8 tensor (replaces pool_2d(inpt, (p, p), ignore_border) and its gradient, convpool.py:97-127,
+ * for every pool the fused conv + pool block does not take; theanet_amd/csrc/pool_c8.hip).  x, gin: N x C maps of S pixels
+ * a side at pitch P; y, gout: maps of So pixels at pitch Po; either element type (the ops compare by value through an
+ * ordered integer key that serves halfs and bf16 alike).  Window p x p, stride p, clipped at the map edge; So = S / p
+ * (ignore_border) or ceil(S / p).
+ * fwd: y = max over the clipped window of the STORED values -- a stored value, never rounded; the window is scanned
+ *   row-major and replaced on strict >, so of equal values the first one's pattern is kept.  Pad cells of y and channels
+ *   past C are written as 0: every cell of y is written.  Also the test version.  Inputs are NaN-free.
+ * bwd: gin[pos] = value(x[pos]) == value(y[window(pos)]) ? gout[window(pos)] : +0: every tied maximum receives the whole
+ *   gradient (tn_pool_bwd, Theano's MaxPoolGrad; -0 == +0 ties), copied bit for bit; positions no window covers (the
+ *   ignore_border remainder, pad cells, channels past C) get +0; every cell of gin is written.  The activation derivative
+ *   of the block below is NOT applied here (the producer of gout has applied act'(y): PoolLayer.act_info looks through).
+ * supported: 1 for 2 <= p <= 64, So one of the two sides above and >= 1, Po >= So, P and Po equal to their side or a power
+ *   of two above it, every tensor below 2^32 - 256 cells.  Anything else, or a NULL tensor: TN_E_ARG naming the arguments,
+ *   nothing launched.  No atomics: deterministic.
+ * plan (no device): op 0 (fwd) / 1 (bwd) -> PW (the window instantiation: 2, 3, or 0 = the run-time loop), SH (the pitch
+ *   the lanes are laid over -- fwd: Po, bwd: P -- is a power of two), blocks; returns how many values the plan has,
+ *   TN_E_ARG for a refused geometry (and always on the CPU backend).                                                  */
+int tn_c8_pool_supported(int N, int C, int S, int P, int p, int So, int Po);
+int tn_c8_pool_fwd(tn_ctx* ctx, const void* x, void* y, int N, int C, int S, int P, int p, int So, int Po);
+int tn_c8_pool_bwd(tn_ctx* ctx, const void* x, const void* y, const void* gout, void* gin, int N, int C, int S, int P,
+                   int p, int So, int Po);
+int tn_c8_pool_plan(int op, int N, int C, int S, int P, int p, int So, int Po, int* out, int nout);
 /* 1x1 stride-1 ConvLayers on c8 tensors (replace conv2d(inpt, W) + b, the activation and -- fused -- the 2x2 max-pool of
  * convpool.py:54-72, 106-107 with filter_sz 1, and their gradients, for a 1x1 layer on the 16-bit stack;
  * theanet_amd/csrc/conv1_c8.hip).  Tensors: N x C (x, dx) / N x K (y, dz) maps of S pixels a side stored at pitch P (P == S,

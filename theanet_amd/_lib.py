@@ -112,6 +112,10 @@ SIGNATURES = {
     "tn_c8_dropout_fwd": (c_int, [CTX, P, P, P] + [c_int] * 4 + [c_float, c_uint64, c_uint32, P, c_uint64, c_int]),
     "tn_c8_dropout_bwd": (c_int, [CTX, P, P, P] + [c_int] * 4),
     "tn_c8_scale": (c_int, [CTX, P, P] + [c_int] * 4 + [c_float]),
+    "tn_c8_pool_supported": (c_int, [c_int] * 7),
+    "tn_c8_pool_fwd": (c_int, [CTX, P, P] + [c_int] * 7),
+    "tn_c8_pool_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 7),
+    "tn_c8_pool_plan": (c_int, [c_int] * 8 + [POINTER(c_int), c_int]),
     "tn_c8_conv1_supported": (c_int, [c_int] * 5),
     "tn_c8_conv1_fwd": (c_int, [CTX, P, P, P, P, P] + [c_int] * 6 + [c_float, c_int]),
     "tn_c8_conv1_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 5 + [P, c_int, c_float, c_int, P]),

@@ -229,6 +229,12 @@ int tn_c8_dropout_fwd(tn_ctx* ctx, const void*, void*, uint8_t*, int, int, int, 
 }
 int tn_c8_dropout_bwd(tn_ctx* ctx, const void*, const uint8_t*, void*, int, int, int, int) { NOT_HERE("tn_c8_dropout_bwd"); }
 int tn_c8_scale(tn_ctx* ctx, const void*, void*, int, int, int, int, float) { NOT_HERE("tn_c8_scale"); }
+int tn_c8_pool_supported(int, int, int, int, int, int, int) { return 0; }
+int tn_c8_pool_fwd(tn_ctx* ctx, const void*, void*, int, int, int, int, int, int, int) { NOT_HERE("tn_c8_pool_fwd"); }
+int tn_c8_pool_bwd(tn_ctx* ctx, const void*, const void*, const void*, void*, int, int, int, int, int, int, int) {
+    NOT_HERE("tn_c8_pool_bwd");
+}
+int tn_c8_pool_plan(int, int, int, int, int, int, int, int, int*, int) { return TN_E_ARG; }
 int tn_c8_conv1_supported(int, int, int, int, int) { return 0; }
 int tn_c8_conv1_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, uint8_t*, int, int, int, int, int, int,
                     float, int) { NOT_HERE("tn_c8_conv1_fwd"); }

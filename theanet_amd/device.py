@@ -279,6 +279,12 @@ def c8_pitch(side):
     return p
 
 
+def c8_pool_pitch(side):
+    """The stored side of what a stand-alone PoolLayer of the 16-bit stack puts out: ``c8_pitch(side)`` up to 64 pixels, so
+    that a conv layer can follow it (4 x 4 maps are stored at pitch 8); dense above 64, where no conv layer runs."""
+    return c8_pitch(side) if side <= 64 else side
+
+
 class C8Array(DeviceArray):
     """A 16-bit-RESIDENT activation / gradient tensor (DTYPE 'float16' / 'bfloat16'): logical (N, C, H, W), stored
     [N][ceil(C/8)][P][P][8] halfs or bf16 -- one 16-byte cell = the 8 channels of an octet at one pixel, channels beyond

@@ -8,12 +8,24 @@ import numpy as np
 from ..device import C8Array
 
 
+def pool_stands_alone(pool_sz, fused=True):
+    """Which of its two forms a PoolLayer on the stack takes: a 2x2 one is the second half of the fused conv + pool block
+    of the ConvLayer below it while the net fuses (``fused``: NeuralNet.fuse_conv_pool); every other one -- and every one
+    of a net that does not fuse -- stands alone (tn_c8_pool_fwd / tn_c8_pool_bwd)."""
+    return not (fused and pool_sz == 2)
+
+
 def check_follows(dtype, below, kind, pool_sz=None, fused=True):
     """The stack's grammar, asserted before a layer of class ``kind`` (its name) is built on the stack tensor that layer
     ``below`` puts out: Conv / Pool / Mean / DropOut layers pass stack tensors on (a MeanLayer closes the stack with an
-    fp32 (N, C) output), a HiddenLayer consumes one; a PoolLayer exists only inside the fused block of the ConvLayer
-    directly below it, 2x2 on even maps."""
+    fp32 (N, C) output), a HiddenLayer consumes one.  A fused PoolLayer (pool_stands_alone) exists only inside the block
+    of the ConvLayer directly below it, 2x2 on even maps; a stand-alone one follows any layer that puts out a stack tensor
+    (its geometry is the constructor's to refuse: tn_c8_pool_supported)."""
     below_kind = type(below).__name__
+    if kind == "PoolLayer" and pool_stands_alone(pool_sz, fused):
+        assert below_kind in ("ConvLayer", "PoolLayer", "DropOutLayer"), \
+            "DTYPE {}: a stand-alone PoolLayer follows a Conv, Pool or DropOut layer (got {})".format(dtype, below_kind)
+        return
     if kind in ("ElasticLayer", "ColorLayer"):
         raise AssertionError("DTYPE {}: only Conv / Pool / Mean / DropOut layers take the conv stack's 16-bit-resident "
                              "tensors (got {})".format(dtype, kind))

@@ -8,7 +8,7 @@ from collections import namedtuple
 import numpy as np
 
 from .. import _lib
-from ..device import C8_DTYPES, C8Array, c8_pitch, is_c8
+from ..device import C8_DTYPES, C8Array, c8_pitch, c8_pool_pitch, is_c8
 from .c8 import DenseDetour, conv_family
 from .layer import Layer, activation_by_name, below_info
 from .weights import init_wb
@@ -150,7 +150,8 @@ class ConvLayer(Layer):
         """conv -> act -> 2x2 max-pool as one fused kernel pair -- the conv activation never reaches HBM.  Returns the
         family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused."""
         if self.f16:
-            return True                  # (the only way a PoolLayer runs on the 16-bit stack: c8.check_follows)
+            # what the fused block takes; any other PoolLayer of the stack stands alone (c8.check_follows)
+            return True if pool.pool_sz == 2 and self.out_sz % 2 == 0 and not pool.c8_alone else None
         if self.stride == 1 and self.ctx.lib.tn_convpool_supported(self.num_prev_maps, self.filter_sz, self.stride, pool.pool_sz):
             return "convpool"            # small channel counts (tn_convpool_fwd / tn_convpool_bwd)
         # wide 3x3 'same' layers: the LDS-tile matrix-core kernels pool in their epilogue and run the
@@ -325,9 +326,11 @@ class ConvLayer(Layer):
 
 
 class PoolLayer(Layer):
-    def __init__(self, inpt, num_maps, in_sz, pool_sz, ignore_border=False):
+    def __init__(self, inpt, num_maps, in_sz, pool_sz, ignore_border=False, c8_alone=False):
         """Max-pool, stride = window.  ignore_border=False keeps the partial last
-        window: (5,5) with pool 2 -> (3,3); True -> (2,2) (convpool.py:98-112)."""
+        window: (5,5) with pool 2 -> (3,3); True -> (2,2) (convpool.py:98-112).
+        ``c8_alone`` (16-bit stack, the net's to say: c8.pool_stands_alone): not the second half of a fused conv + pool
+        block but a layer of its own (tn_c8_pool_fwd / tn_c8_pool_bwd) -- any window on any map."""
         if ignore_border:
             self.out_sz = in_sz // pool_sz
         else:
@@ -339,11 +342,22 @@ class PoolLayer(Layer):
         self.num_maps = num_maps
         self.in_sz, self.pool_sz = in_sz, pool_sz
         self.ignore_border = ignore_border
-        self.args = (num_maps, in_sz, pool_sz, ignore_border)
+        self.args = (num_maps, in_sz, pool_sz, ignore_border, c8_alone)
         self.n_out = num_maps * self.out_sz ** 2
         self.batch_sz = inpt.shape[0]
-        self.f16 = is_c8(inpt)      # 16-bit stack: pooled c8 tensor (only as a fused block)
-        if self.f16:
+        self.f16 = is_c8(inpt)      # 16-bit stack: pooled c8 tensor (of a fused block, or this layer's own)
+        self.c8_alone = self.f16 and c8_alone
+        self.below = None           # (stand-alone) the layer below, set by the net: act_info() looks through to it
+        if self.c8_alone:
+            pitch = c8_pool_pitch(self.out_sz)
+            self.c8_geom = (self.batch_sz, num_maps, in_sz, inpt.pitch, pool_sz, self.out_sz, pitch)
+            assert self.ctx.lib.tn_c8_pool_supported(*self.c8_geom), (
+                "DTYPE {}: a stand-alone PoolLayer takes a window of 2 to 64 pixels that leaves at least one output pixel, "
+                "on tensors of fewer than 2^32 - 256 cells (got {} maps of {} pixels at pitch {}, window {}, {} border: "
+                "{} pixels at pitch {})".format(inpt.elem, num_maps, in_sz, inpt.pitch, pool_sz,
+                                                "ignored" if ignore_border else "kept", self.out_sz, pitch))
+            self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem, pitch=pitch)
+        elif self.f16:
             self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem,
                                   pitch=inpt.pitch // 2 if inpt.padded else None)
         else:
@@ -364,7 +378,13 @@ class PoolLayer(Layer):
     def act_info(self):
         """16-bit stack: the gradient a pooled block receives carries act'(pooled output) (applied by whichever kernel
         produces it, from the block's stored output); fp32 blocks take the derivative from the pooling mask's sign
-        bits inside their own backward kernels instead."""
+        bits inside their own backward kernels instead.  A stand-alone PoolLayer of the stack looks through, the way a
+        DropOutLayer does: its own output, with the activation of the block below -- every element its backward hands the
+        gradient to equals its window's maximum, so act' taken from the pooled output is act' of that element."""
+        if self.c8_alone and self.below is not None:
+            _, b_act, b_prm, b_mask = self.below.act_info()
+            assert b_mask is None
+            return self.output, b_act, b_prm, None
         if self.f16:
             act = self.fused_conv.act
             return self.output, act.kind, act.prm, None
@@ -372,6 +392,8 @@ class PoolLayer(Layer):
 
     def forward(self, train=True):
         conv = self.fused_conv
+        if self.c8_alone:
+            return self.ctx.call("tn_c8_pool_fwd", self.inpt.ptr, self.output.ptr, *self.c8_geom)
         if self.f16:
             if train and self.mask is None:
                 self.mask = self.ctx.empty(self.output.shape, np.uint8)
@@ -401,6 +423,12 @@ class PoolLayer(Layer):
             return None
         if self.fused_conv is not None:
             return gout               # the conv layer's fused backward consumes d cost / d y
+        if self.c8_alone:
+            # selection only: act' of the block below is already in gout (act_info)
+            if self.gin is None:
+                self.gin = C8Array.like(self.inpt)
+            self.ctx.call("tn_c8_pool_bwd", self.inpt.ptr, self.output.ptr, gout.ptr, self.gin.ptr, *self.c8_geom)
+            return self.gin
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
         _, b_act, b_prm, b_mask = below_info(below)

@@ -25,7 +25,7 @@ from . import _lib, comm, layer
 from .dpsched import DpSchedule
 from .plan import StepPlan
 from .device import DeviceArray, get_context, is_c8, share
-from .layer.c8 import OperandTiles, check_follows
+from .layer.c8 import OperandTiles, check_follows, pool_stands_alone
 from .layer.convpool import pool_mask_enabled
 from .layer import (AuxConcatLayer, SoftAuxLayer, CenteredOutLayer, ColorLayer, ConvLayer, DropOutLayer, ElasticLayer, ExpLossLayer, HiddenLayer,
                     HingeLayer, InputLayer, InputSlot, MeanLayer, OutputLayer, PoolLayer, SoftmaxLayer)
@@ -309,10 +309,16 @@ class NeuralNet():
                                    **layer_args)
 
         elif curr_layer_type in (PoolLayer, MeanLayer):
+            if curr_layer_type is PoolLayer and is_c8(tr_inpt):
+                # 16-bit stack: half of a fused conv + pool block, or a layer of its own that -- like a DropOutLayer --
+                # stands for the block below it (PoolLayer.act_info)
+                layer_args = dict(layer_args, c8_alone=pool_stands_alone(layer_args.get("pool_sz"), self.fuse_conv_pool))
             curr_layer = curr_layer_type(tr_inpt,
                                          num_maps=num_prev_maps,
                                          in_sz=prev_out_sz,
                                          **layer_args)
+            if curr_layer_type is PoolLayer:
+                curr_layer.below = prev_tr_layer
 
         elif curr_layer_type is DropOutLayer:
             curr_layer = DropOutLayer(tr_inpt,
