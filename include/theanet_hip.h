@@ -380,6 +380,44 @@ int tn_c8_conv_plan_pitch(int op, int N, int C, int S, int P, int K, int pool, i
 /* 1 if tn_conv2d_* run this shape on the implicit-im2col fp32-MFMA kernels (stride 1, reduction
  * C*f*f >= 32, >= 16 output maps); otherwise the direct VALU kernels are used.              */
 int tn_conv_mfma_supported(int C, int K, int f, int stride);
+/* Which kernel a tn_conv2d_* call of this shape launches in CONV mode 0 (fp32; CONV 'bfloat16' has kernels of its own) --
+ * the launchers' own selection (conv_route and the plan functions of theanet_amd/csrc/conv.hip, conv_mfma.hip and
+ * conv_tile.hip, which the entry points run), made without a context or a device.
+ *   prod     0 tn_conv2d_fwd, 1 tn_conv2d_wgrad, 2 tn_conv2d_dgrad; the geometry is the LAYER's, as the entry points take it
+ *   num_cus  the CU count the selection assumes; 0: the current device's, 256 where no GPU answers
+ *   flags    everything else the selection looks at; 0 is the common case
+ *            bit 0  the gathered operand(s) are NOT 16-byte aligned (forward x; weight gradient x and dz; input gradient dz)
+ *            bit 1  no prev_a (input gradient)
+ *            bit 2  out / prev_a NOT 16-byte aligned (forward a; input gradient dx, prev_a)
+ *            bit 3  W NOT 16-byte aligned (forward)
+ *   The knobs (TN_CONV_TILE*) are read as the library loaded them.
+ * One record of 16 ints:
+ *    0 route    1 LDS-tile kernels, 2 their few-channel weight gradient, 3 MFMA implicit GEMM, 4 conv_dgrad_lds, 5 direct
+ *               kernels, 6 generic weight gradient (ConvRoute; 0, CONV 'bfloat16', is never reported)
+ *    1 kernel   0 conv_fwd_direct, 1 conv_wgrad_direct, 2 conv_dgrad_direct, 3 conv_dgrad_lds, 4 conv_wgrad_generic (+
+ *               conv_bgrad_generic), 5 conv_mfma_fwd_kernel, 6 conv_mfma_wgrad_kernel, 7 conv_tile_kernel,
+ *               8 conv_tile_wgrad_kernel, 9 conv_tile_wgrad_smallc_kernel
+ *    2-5        the kernel's template arguments, in order, 0 beyond them: 0 <F, KT>; 1 <F, KT, CT>; 2 <F, CT>; 3 <F>; 4 none;
+ *               5 <PADDED, DGRAD>; 6 <PADDED>; 7 <FT, DGRAD, NCP> (POOL = false); 8 <NFT> (POOL = false); 9 none (POOL = false)
+ *    6-15       launch geometry, 0 beyond what the kernel has:
+ *               0  pixel blocks of 256 (grid x), filter groups of KT (grid y)
+ *               1  slabs nblk (grid x; the slab sum follows), filter groups of KT, channel groups of CT
+ *               2  pixel blocks of 256, channel groups of CT, prev_a given
+ *               3  G images per block, image groups, channel groups of 4, bytes of LDS, prev_a given
+ *               4  blocks (K*C*f*f)
+ *               5  KT row tiles of 64, MT pixel tiles of 64, Kd reduction depth, M pixels, a_vec (A rows loaded 16 bytes
+ *                  at a time), prev_a given
+ *               6  KT filter tiles of 64, MT tiles of 64 over Kd, Kd, M pixels, S pixel slabs, mchunk pixels per slab
+ *               7  KT filter tiles of 32 FT, MT pixel tiles, RT row tiles per image, NI images per tile, TH rows per tile,
+ *                  chunks of 8 gathered channels, vec_out (16-byte epilogue), the kernel's padding (input gradient:
+ *                  2 - pad_lo), prev_a given
+ *               8  KG filter groups of 32 NFT, CG channel groups of 32, S image slabs, ipb images per slab, NI images per
+ *                  tile, RT row tiles per image, NT tiles per slab
+ *               9  KG filter groups of 32, S image slabs, ipb, NI, RT, NT as for 8
+ * Writes up to nout ints to out and returns the record's length; TN_E_ARG where the call would refuse the shape (and
+ * always on the CPU backend).                                                                                       */
+int tn_conv_plan(int prod, int N, int C, int H, int W, int K, int f, int stride, int pad_lo, int Ho, int Wo, int num_cus,
+                 unsigned flags, int* out, int nout);
 
 /* ---- fused conv + bias + act + max-pool for small feature maps (same reference call sites as
  * tn_conv2d_* followed by tn_pool_*: convpool.py:54-72 then :106-107).  The conv activation

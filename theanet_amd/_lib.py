@@ -177,6 +177,7 @@ SIGNATURES = {
     "tn_softmax_nll_cost": (c_int, [CTX, P, P, c_int64, P, P, P, P, P, P, c_int, c_int, c_float,
                                     c_float, P, P]),
     "tn_conv_mfma_supported": (c_int, [c_int] * 4),
+    "tn_conv_plan": (c_int, [c_int] * 12 + [c_uint32, POINTER(c_int), c_int]),
     "tn_convpool_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "tn_convpool_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 12 + [c_int, c_float]),
     "tn_convpool_fwd_mask": (c_int, [CTX, P, P, P, P, P] + [c_int] * 12 + [c_int, c_float]),

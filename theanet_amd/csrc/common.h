@@ -191,6 +191,42 @@ int tn_cb_conv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, fl
                      int f, int stride, int pad, int Ho, int Wo);
 // The fp32 conv family: what one of its files calls in another.  conv_route (conv.hip) decides which of these a tn_conv2d_*
 // product runs; the fused blocks' entry points (convpool.hip, convblock*.hip) test their own *_supported functions.
+enum ConvProduct { CONV_FWD, CONV_WGRAD, CONV_DGRAD };
+enum ConvRoute {
+    CONV_BF16,         // CONV 'bfloat16' (conv_bf16.hip): every geometry while the mode is in force
+    CONV_TILE,         // LDS-resident-tile matrix-core kernels, 3x3 (conv_tile.hip)
+    CONV_TILE_SMALLC,  // ... their weight gradient for few input channels, C*9 <= 32 (first layers)
+    CONV_MFMA,         // MFMA implicit GEMM (conv_mfma.hip)
+    CONV_LDS_DGRAD,    // conv_dgrad_lds: 3x3 input gradient over an LDS-resident dz
+    CONV_DIRECT,       // conv_*_direct
+    CONV_GENERIC       // conv_wgrad_generic + conv_bgrad_generic: filter sizes without a direct weight gradient
+};
+// What one tn_conv2d_* product launches.  Every choice a launcher of the family makes beyond the route -- template arguments,
+// grids, slabs, the 16-byte forms -- is made by a plain host function of (shape, alignment bits, CU count) that fills this
+// (conv_direct_plan in conv.hip, tn_conv_mfma_plan, tn_conv_tile_*plan); the launchers switch on what those functions
+// chose, and tn_conv_plan (include/theanet_hip.h, which documents t[] and v[] per kernel) reports it.
+enum ConvKernel {
+    CVK_FWD_DIRECT, CVK_WGRAD_DIRECT, CVK_DGRAD_DIRECT, CVK_DGRAD_LDS, CVK_WGRAD_GENERIC,      // conv.hip
+    CVK_MFMA, CVK_MFMA_WGRAD,                                                                  // conv_mfma.hip
+    CVK_TILE, CVK_TILE_WGRAD, CVK_TILE_SMALLC                                                  // conv_tile.hip
+};
+// the alignment bits of a product (tn_conv_plan's flags): what the selection reads of the operand pointers
+enum {
+    CONV_UNAL_GATHER = 1,      // the gathered operand(s) -- forward x, weight gradient x and dz, input gradient dz
+    CONV_BARE = 2,             // input gradient without prev_a
+    CONV_UNAL_OUT = 4,         // out / prev_a
+    CONV_UNAL_W = 8            // W
+};
+struct ConvPlan {
+    int route, kernel;
+    int t[4];                  // the kernel's template arguments
+    int v[10];                 // launch geometry
+};
+#define CONV_PLAN_INTS 16
+static inline unsigned conv_unal(const void* p, const void* q = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & 15) != 0;
+}
+int tn_current_cus();          // gemm.hip: the current device's CU count, 256 where no GPU answers (the plan queries' num_cus 0)
 // conv.hip: the end of the family's split weight gradients (slabs in correlation layout: the sum flips every f x f block)
 int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbpartial, float* dW, float* db, int nblk, int K,
                          int C, int f);
@@ -201,19 +237,26 @@ int tn_conv_mfma_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, 
                        int pad, int Ho, int Wo, const float* prev_a, int act, float prm);
 int tn_conv_mfma_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K,
                        int f, int pad, int Ho, int Wo);
+// the *_plan functions take the LAYER's geometry and fill p as the product's launcher would choose; 0: the launcher refuses
+int tn_conv_mfma_plan(ConvProduct prod, int num_cus, unsigned al, int N, int C, int H, int Wd, int K, int f, int pad, int Ho,
+                      int Wo, ConvPlan* p);
 // conv_tile.hip: the LDS-resident-tile kernels for 3x3 windows ...
-int tn_conv_tile_ok(const float* x, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
+// (unal: the gathered operand(s) are not 16-byte aligned)
+int tn_conv_tile_ok(unsigned unal, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
 int tn_conv_tile_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K,
                      int pad, int Ho, int Wo, int act, float prm);
 int tn_conv_tile_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int pad,
                        int Ho, int Wo, const float* prev_a, int act, float prm);
-int tn_conv_tile_wgrad_ok(tn_ctx* ctx, const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad,
+int tn_conv_tile_plan(ConvProduct prod, unsigned al, int N, int C, int H, int Wd, int K, int pad, int Ho, int Wo, ConvPlan* p);
+int tn_conv_tile_wgrad_ok(int num_cus, unsigned unal, int N, int C, int H, int Wd, int K, int f, int pad,
                           int Ho, int Wo);
 int tn_conv_tile_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K);
+int tn_conv_tile_wgrad_plan(int num_cus, int N, int C, int H, int Wd, int K, ConvPlan* p);
 // ... their weight gradient for few input channels (first layers), from a plain dz or from a block's pooling mask ...
-int tn_conv_tile_smallc_ok(const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
+int tn_conv_tile_smallc_ok(unsigned unal, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo);
 int tn_conv_tile_smallc_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd,
                               int K);
+int tn_conv_tile_smallc_plan(int num_cus, int N, int C, int H, int Wd, int K, ConvPlan* p);
 extern "C" int tn_convpool_smallc_supported(int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo, int p, int Hp,
                                             int Wp);
 int tn_conv_tile_smallc_bwd(tn_ctx* ctx, const float* x, const float* g_, const float* y, const uint8_t* mask, float* dW,

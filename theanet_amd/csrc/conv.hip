@@ -367,17 +367,7 @@ int tn_conv_wgrad_finish(tn_ctx* ctx, const float* partial, const float* dbparti
                         db, (uint32_t)K, (uint32_t)nblk, (uint32_t)K, (uint32_t)(f * f));
 }
 
-// ---- which kernel a product of tn_conv2d_* gets: the whole ladder, in the order it is asked ------------------------
-enum ConvProduct { CONV_FWD, CONV_WGRAD, CONV_DGRAD };
-enum ConvRoute {
-    CONV_BF16,         // CONV 'bfloat16' (conv_bf16.hip): every geometry while the mode is in force
-    CONV_TILE,         // LDS-resident-tile matrix-core kernels, 3x3 (conv_tile.hip)
-    CONV_TILE_SMALLC,  // ... their weight gradient for few input channels, C*9 <= 32 (first layers)
-    CONV_MFMA,         // MFMA implicit GEMM (conv_mfma.hip)
-    CONV_LDS_DGRAD,    // conv_dgrad_lds: 3x3 input gradient over an LDS-resident dz
-    CONV_DIRECT,       // conv_*_direct
-    CONV_GENERIC       // conv_wgrad_generic + conv_bgrad_generic: filter sizes without a direct weight gradient
-};
+// ---- which kernel a product of tn_conv2d_* gets: the whole ladder, in the order it is asked (ConvRoute: common.h) ---------
 
 // images per block of conv_dgrad_lds (0: the filters and one haloed dz image do not fit its 60 KiB of LDS)
 static int dgrad_lds_group(int K, int Ho, int Wo, size_t* lds) {
@@ -390,44 +380,114 @@ static int dgrad_lds_group(int K, int Ho, int Wo, size_t* lds) {
     return G;
 }
 
-// p, q: the operands whose 16-byte alignment tn_conv_tile_*ok look at -- forward x, weight gradient x and dz, input
-// gradient dz.  The geometry is the LAYER's in every product.
-static ConvRoute conv_route(tn_ctx* ctx, ConvProduct prod, const float* p, const float* q, int N, int C, int H, int Wd,
+// unal: the operands whose 16-byte alignment tn_conv_tile_*ok look at -- forward x, weight gradient x and dz, input
+// gradient dz -- are not all aligned.  The geometry is the LAYER's in every product.
+static ConvRoute conv_route(int conv_bf16, int num_cus, ConvProduct prod, unsigned unal, int N, int C, int H, int Wd,
                             int K, int f, int stride, int pad, int Ho, int Wo) {
-    if (ctx->conv_bf16) return CONV_BF16;      // the mode, not the shape: asked before the entry points' shape checks,
+    if (conv_bf16) return CONV_BF16;           // the mode, not the shape: asked before the entry points' shape checks,
     if (N <= 0 || C <= 0 || K <= 0 || f <= 0 || stride <= 0 || (prod == CONV_FWD && (Ho <= 0 || Wo <= 0)))
         return CONV_DIRECT;                    // which refuse these: nothing to ask the geometry functions
     size_t lds;
     switch (prod) {
         case CONV_FWD:
             if (tn_conv_mfma_supported(C, K, f, stride))
-                return tn_conv_tile_ok(p, N, C, H, Wd, K, f, pad, Ho, Wo) ? CONV_TILE : CONV_MFMA;
+                return tn_conv_tile_ok(unal, N, C, H, Wd, K, f, pad, Ho, Wo) ? CONV_TILE : CONV_MFMA;
             // few input channels (first layers): still worth the matrix core when the LDS-tile kernel applies
-            if (stride == 1 && K >= 16 && tn_conv_tile_ok(p, N, C, H, Wd, K, f, pad, Ho, Wo)) return CONV_TILE;
+            if (stride == 1 && K >= 16 && tn_conv_tile_ok(unal, N, C, H, Wd, K, f, pad, Ho, Wo)) return CONV_TILE;
             return CONV_DIRECT;
         case CONV_WGRAD:
-            // (tn_conv_tile_wgrad_ok cuts its slabs for ctx->num_cus, the fused block's tn_convpool_tile_supported
-            // for 256 CUs whatever the chip: possibly unintended, kept as it is)
+            // (tn_conv_tile_wgrad_ok cuts its slabs for the context's CU count, the fused block's
+            // tn_convpool_tile_supported for 256 CUs whatever the chip: possibly unintended, kept as it is)
             if (tn_conv_mfma_supported(C, K, f, stride))
-                return tn_conv_tile_wgrad_ok(ctx, p, q, N, C, H, Wd, K, f, pad, Ho, Wo) ? CONV_TILE : CONV_MFMA;
-            if (stride == 1 && tn_conv_tile_smallc_ok(p, q, N, C, H, Wd, K, f, pad, Ho, Wo)) return CONV_TILE_SMALLC;
+                return tn_conv_tile_wgrad_ok(num_cus, unal, N, C, H, Wd, K, f, pad, Ho, Wo) ? CONV_TILE : CONV_MFMA;
+            if (stride == 1 && tn_conv_tile_smallc_ok(unal, N, C, H, Wd, K, f, pad, Ho, Wo)) return CONV_TILE_SMALLC;
             return (f == 3 || f == 5 || f == 1 || f == 2) ? CONV_DIRECT : CONV_GENERIC;
         default:
             // dx = conv_fwd(dz, Wt) with padding f-1-pad: the roles swap -- reduction K*f*f, rows = C input maps,
             // gathered tensor = dz (N,K,Ho,Wo)
             if (tn_conv_mfma_supported(K, C, f, stride))
-                return tn_conv_tile_ok(p, N, K, Ho, Wo, C, f, f - 1 - pad, H, Wd) ? CONV_TILE : CONV_MFMA;
+                return tn_conv_tile_ok(unal, N, K, Ho, Wo, C, f, f - 1 - pad, H, Wd) ? CONV_TILE : CONV_MFMA;
             if (f == 3 && stride == 1 && dgrad_lds_group(K, Ho, Wo, &lds)) return CONV_LDS_DGRAD;
             return CONV_DIRECT;
     }
 }
 
+// What the kernels of this file launch for a product that conv_route sent here (CONV_DIRECT, CONV_LDS_DGRAD,
+// CONV_GENERIC): template arguments and grid.  v[] per kernel: include/theanet_hip.h (tn_conv_plan).
+static ConvPlan conv_direct_plan(ConvRoute route, ConvProduct prod, unsigned al, int N, int C, int H, int Wd, int K, int f,
+                                 int Ho, int Wo) {
+    ConvPlan p{};
+    p.route = route;
+    const int prev = prod == CONV_DGRAD && !(al & CONV_BARE);
+    if (route == CONV_GENERIC) {
+        p.kernel = CVK_WGRAD_GENERIC;
+        p.v[0] = K * C * f * f;
+    } else if (route == CONV_LDS_DGRAD) {
+        size_t lds = 0;
+        const int G = dgrad_lds_group(K, Ho, Wo, &lds);
+        p.kernel = CVK_DGRAD_LDS;
+        p.t[0] = 3;
+        p.v[0] = G; p.v[1] = cdiv(N, G); p.v[2] = cdiv(C, 4); p.v[3] = (int)lds; p.v[4] = prev;
+    } else if (prod == CONV_FWD) {
+        p.kernel = CVK_FWD_DIRECT;
+        p.t[0] = (f == 3 || f == 5) ? f : 0;
+        p.t[1] = ((K % 8 == 0) || K > 32) ? 8 : 4;
+        p.v[0] = cdiv((long long)N * Ho * Wo, 256); p.v[1] = cdiv(K, p.t[1]);
+    } else if (prod == CONV_WGRAD) {
+        p.kernel = CVK_WGRAD_DIRECT;
+        p.t[0] = f;
+        if (f == 3) { p.t[1] = 4; p.t[2] = C >= 4 ? 4 : C >= 2 ? 2 : 1; }
+        else if (f == 5) { p.t[1] = C >= 2 ? 2 : 4; p.t[2] = C >= 2 ? 2 : 1; }
+        else if (f == 2) { p.t[1] = 4; p.t[2] = C >= 4 ? 4 : 1; }
+        else { p.t[0] = 1; p.t[1] = 8; p.t[2] = C >= 4 ? 4 : 1; }
+        int nblk = cdiv((long long)N * Ho * Wo, 256 * 16);
+        if (nblk > 1024) nblk = 1024;
+        if (nblk < 1) nblk = 1;
+        p.v[0] = nblk; p.v[1] = cdiv(K, p.t[1]); p.v[2] = cdiv(C, p.t[2]);
+    } else {
+        p.kernel = CVK_DGRAD_DIRECT;
+        p.t[0] = f == 3 ? 3 : 0;
+        p.t[1] = C >= 8 ? 8 : 4;
+        p.v[0] = cdiv((long long)N * H * Wd, 256); p.v[1] = cdiv(C, p.t[1]); p.v[2] = prev;
+    }
+    return p;
+}
+
 extern "C" {
+
+// What a tn_conv2d_* call of this shape launches in CONV mode 0: conv_route, then the plan function of the route's
+// launcher -- the functions the entry points below and their launchers run.  Layout and flags: include/theanet_hip.h.
+int tn_conv_plan(int prod_, int N, int C, int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo, int num_cus,
+                 unsigned flags, int* out, int nout) {
+    if (prod_ < 0 || prod_ > 2 || num_cus < 0 || (nout > 0 && !out)) return TN_E_ARG;
+    if (N <= 0 || C <= 0 || K <= 0 || f <= 0 || stride <= 0 || (prod_ == CONV_FWD && (Ho <= 0 || Wo <= 0))) return TN_E_ARG;
+    if (H <= 0 || Wd <= 0 || Ho <= 0 || Wo <= 0) return TN_E_ARG;     // (nothing to launch: the entry points do not ask)
+    if (num_cus == 0) num_cus = tn_current_cus();
+    const ConvProduct prod = (ConvProduct)prod_;
+    const unsigned unal = flags & CONV_UNAL_GATHER;
+    const ConvRoute route = conv_route(0, num_cus, prod, unal, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    ConvPlan p{};
+    int ok = 1;
+    switch (route) {
+        case CONV_TILE:
+            ok = prod == CONV_WGRAD ? tn_conv_tile_wgrad_plan(num_cus, N, C, H, Wd, K, &p)
+                                    : tn_conv_tile_plan(prod, flags, N, C, H, Wd, K, pad_lo, Ho, Wo, &p);
+            break;
+        case CONV_TILE_SMALLC: ok = tn_conv_tile_smallc_plan(num_cus, N, C, H, Wd, K, &p); break;
+        case CONV_MFMA: ok = tn_conv_mfma_plan(prod, num_cus, flags, N, C, H, Wd, K, f, pad_lo, Ho, Wo, &p); break;
+        default: p = conv_direct_plan(route, prod, flags, N, C, H, Wd, K, f, Ho, Wo); break;
+    }
+    if (!ok) return TN_E_ARG;
+    const int* v = &p.route;
+    static_assert(sizeof(ConvPlan) == CONV_PLAN_INTS * sizeof(int), "ConvPlan is CONV_PLAN_INTS ints");
+    for (int k = 0; k < CONV_PLAN_INTS && k < nout; ++k) out[k] = v[k];
+    return CONV_PLAN_INTS;
+}
 
 int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N,
                   int C, int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo,
                   int act, float act_param) {
-    const ConvRoute route = conv_route(ctx, CONV_FWD, x, nullptr, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    const ConvRoute route = conv_route(ctx->conv_bf16, ctx->num_cus, CONV_FWD, conv_unal(x), N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
     if (route == CONV_BF16) return tn_cb_conv_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, act, act_param);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0 && Ho > 0 && Wo > 0, "tn_conv2d_fwd: bad shape");
     TN_FP32_ONLY(ctx, "tn_conv2d_fwd");
@@ -436,18 +496,15 @@ int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, f
         case CONV_MFMA: return tn_conv_mfma_fwd(ctx, x, W, b, a, N, C, H, Wd, K, f, pad_lo, Ho, Wo, act, act_param);
         default: break;      // CONV_DIRECT
     }
-    const long long M = (long long)N * Ho * Wo;
-    const int gx = cdiv(M, 256);
+    const ConvPlan p = conv_direct_plan(route, CONV_FWD, 0, N, C, H, Wd, K, f, Ho, Wo);
 #define LAUNCH_FWD(F_, KT_)                                                                     \
-    conv_fwd_direct<F_, KT_><<<dim3(gx, cdiv(K, KT_)), 256, 0, ctx->stream>>>(                   \
-        x, W, b, a, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, act, act_param)
-    const bool k8 = (K % 8 == 0) || K > 32;
-    if (f == 3) {
-        if (k8) LAUNCH_FWD(3, 8); else LAUNCH_FWD(3, 4);
-    } else if (f == 5) {
-        if (k8) LAUNCH_FWD(5, 8); else LAUNCH_FWD(5, 4);
-    } else {
-        if (k8) LAUNCH_FWD(0, 8); else LAUNCH_FWD(0, 4);
+    case F_ * 16 + KT_:                                                                         \
+        conv_fwd_direct<F_, KT_><<<dim3(p.v[0], p.v[1]), 256, 0, ctx->stream>>>(                 \
+            x, W, b, a, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, act, act_param);             \
+        break
+    switch (p.t[0] * 16 + p.t[1]) {
+        LAUNCH_FWD(3, 8); LAUNCH_FWD(3, 4); LAUNCH_FWD(5, 8); LAUNCH_FWD(5, 4); LAUNCH_FWD(0, 8); LAUNCH_FWD(0, 4);
+        default: return tn_fail(ctx, TN_E_ARG, "tn_conv2d_fwd: no conv_fwd_direct<%d,%d>", p.t[0], p.t[1]);
     }
 #undef LAUNCH_FWD
     TN_LAUNCH_CHECK();
@@ -456,7 +513,7 @@ int tn_conv2d_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, f
 
 int tn_conv2d_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C,
                     int H, int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo) {
-    const ConvRoute route = conv_route(ctx, CONV_WGRAD, x, dz, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    const ConvRoute route = conv_route(ctx->conv_bf16, ctx->num_cus, CONV_WGRAD, conv_unal(x, dz), N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
     if (route == CONV_BF16) return tn_cb_conv_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0, "tn_conv2d_wgrad: bad shape");
     TN_FP32_ONLY(ctx, "tn_conv2d_wgrad");
@@ -464,34 +521,31 @@ int tn_conv2d_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, flo
         case CONV_TILE: return tn_conv_tile_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K);
         case CONV_MFMA: return tn_conv_mfma_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K, f, pad_lo, Ho, Wo);
         case CONV_TILE_SMALLC: return tn_conv_tile_smallc_wgrad(ctx, x, dz, dW, db, N, C, H, Wd, K);
-        case CONV_GENERIC:
-            conv_wgrad_generic<<<K * C * f * f, 256, 0, ctx->stream>>>(x, dz, dW, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
-            TN_LAUNCH_CHECK();
-            conv_bgrad_generic<<<K, 256, 0, ctx->stream>>>(dz, db, N, K, Ho * Wo);
-            TN_LAUNCH_CHECK();
-            return TN_OK;
-        default: break;      // CONV_DIRECT
+        default: break;      // CONV_GENERIC, CONV_DIRECT
     }
-    const long long M = (long long)N * Ho * Wo;
-    int nblk = cdiv(M, 256 * 16);
-    if (nblk > 1024) nblk = 1024;
-    if (nblk < 1) nblk = 1;
+    const ConvPlan p = conv_direct_plan(route, CONV_WGRAD, 0, N, C, H, Wd, K, f, Ho, Wo);
+    if (p.kernel == CVK_WGRAD_GENERIC) {
+        conv_wgrad_generic<<<p.v[0], 256, 0, ctx->stream>>>(x, dz, dW, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+        TN_LAUNCH_CHECK();
+        conv_bgrad_generic<<<K, 256, 0, ctx->stream>>>(dz, db, N, K, Ho * Wo);
+        TN_LAUNCH_CHECK();
+        return TN_OK;
+    }
+    const int nblk = p.v[0];
     float *partial, *dbpartial;
     int rc = conv_slabs(ctx, nblk, (size_t)K * C * f * f, K, &partial, &dbpartial);
     if (rc) return rc;
 #define LAUNCH_WG(F_, KT_, CT_)                                                                  \
-    conv_wgrad_direct<F_, KT_, CT_><<<dim3(nblk, cdiv(K, KT_), cdiv(C, CT_)), 256, 0, ctx->stream>>>( \
-        x, dz, partial, dbpartial, N, C, H, Wd, K, stride, pad_lo, Ho, Wo)
-    if (f == 3) {
-        if (C >= 4) LAUNCH_WG(3, 4, 4);
-        else if (C >= 2) LAUNCH_WG(3, 4, 2);
-        else LAUNCH_WG(3, 4, 1);
-    } else if (f == 5) {
-        if (C >= 2) LAUNCH_WG(5, 2, 2); else LAUNCH_WG(5, 4, 1);
-    } else if (f == 2) {
-        if (C >= 4) LAUNCH_WG(2, 4, 4); else LAUNCH_WG(2, 4, 1);
-    } else {
-        if (C >= 4) LAUNCH_WG(1, 8, 4); else LAUNCH_WG(1, 8, 1);
+    case F_ * 256 + KT_ * 16 + CT_:                                                              \
+        conv_wgrad_direct<F_, KT_, CT_><<<dim3(nblk, p.v[1], p.v[2]), 256, 0, ctx->stream>>>(     \
+            x, dz, partial, dbpartial, N, C, H, Wd, K, stride, pad_lo, Ho, Wo);                  \
+        break
+    switch (p.t[0] * 256 + p.t[1] * 16 + p.t[2]) {
+        LAUNCH_WG(3, 4, 4); LAUNCH_WG(3, 4, 2); LAUNCH_WG(3, 4, 1);
+        LAUNCH_WG(5, 2, 2); LAUNCH_WG(5, 4, 1);
+        LAUNCH_WG(2, 4, 4); LAUNCH_WG(2, 4, 1);
+        LAUNCH_WG(1, 8, 4); LAUNCH_WG(1, 8, 1);
+        default: return tn_fail(ctx, TN_E_ARG, "tn_conv2d_wgrad: no conv_wgrad_direct<%d,%d,%d>", p.t[0], p.t[1], p.t[2]);
     }
 #undef LAUNCH_WG
     TN_LAUNCH_CHECK();
@@ -501,7 +555,7 @@ int tn_conv2d_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, flo
 int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H,
                     int Wd, int K, int f, int stride, int pad_lo, int Ho, int Wo, const float* prev_a,
                     int prev_act, float prev_act_param) {
-    const ConvRoute route = conv_route(ctx, CONV_DGRAD, dz, nullptr, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
+    const ConvRoute route = conv_route(ctx->conv_bf16, ctx->num_cus, CONV_DGRAD, conv_unal(dz), N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo);
     if (route == CONV_BF16)
         return tn_cb_conv_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
     TN_REQUIRE(N > 0 && C > 0 && K > 0 && f > 0 && stride > 0, "tn_conv2d_dgrad: bad shape");
@@ -509,25 +563,23 @@ int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int
     switch (route) {
         case CONV_TILE: return tn_conv_tile_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
         case CONV_MFMA: return tn_conv_mfma_dgrad(ctx, dz, W, dx, N, C, H, Wd, K, f, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param);
-        case CONV_LDS_DGRAD: {
-            size_t lds;
-            const int G = dgrad_lds_group(K, Ho, Wo, &lds);
-            conv_dgrad_lds<3><<<dim3(cdiv(N, G), cdiv(C, 4)), 256, lds, ctx->stream>>>(
-                dz, W, dx, N, C, H, Wd, K, pad_lo, Ho, Wo, G, prev_a, prev_act, prev_act_param);
-            TN_LAUNCH_CHECK();
-            return TN_OK;
-        }
-        default: break;      // CONV_DIRECT
+        default: break;      // CONV_LDS_DGRAD, CONV_DIRECT
     }
-    const long long M = (long long)N * H * Wd;
-    const int gx = cdiv(M, 256);
+    const ConvPlan p = conv_direct_plan(route, CONV_DGRAD, 0, N, C, H, Wd, K, f, Ho, Wo);
+    if (p.kernel == CVK_DGRAD_LDS) {
+        conv_dgrad_lds<3><<<dim3(p.v[1], p.v[2]), 256, (size_t)p.v[3], ctx->stream>>>(
+            dz, W, dx, N, C, H, Wd, K, pad_lo, Ho, Wo, p.v[0], prev_a, prev_act, prev_act_param);
+        TN_LAUNCH_CHECK();
+        return TN_OK;
+    }
 #define LAUNCH_DG(F_, CT_)                                                                       \
-    conv_dgrad_direct<F_, CT_><<<dim3(gx, cdiv(C, CT_)), 256, 0, ctx->stream>>>(                  \
-        dz, W, dx, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param)
-    if (f == 3) {
-        if (C >= 8) LAUNCH_DG(3, 8); else LAUNCH_DG(3, 4);
-    } else {
-        if (C >= 8) LAUNCH_DG(0, 8); else LAUNCH_DG(0, 4);
+    case F_ * 16 + CT_:                                                                          \
+        conv_dgrad_direct<F_, CT_><<<dim3(p.v[0], p.v[1]), 256, 0, ctx->stream>>>(                \
+            dz, W, dx, N, C, H, Wd, K, f, stride, pad_lo, Ho, Wo, prev_a, prev_act, prev_act_param); \
+        break
+    switch (p.t[0] * 16 + p.t[1]) {
+        LAUNCH_DG(3, 8); LAUNCH_DG(3, 4); LAUNCH_DG(0, 8); LAUNCH_DG(0, 4);
+        default: return tn_fail(ctx, TN_E_ARG, "tn_conv2d_dgrad: no conv_dgrad_direct<%d,%d>", p.t[0], p.t[1]);
     }
 #undef LAUNCH_DG
     TN_LAUNCH_CHECK();

@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256) void conv_mfma_wgrad_reduce(const float* __res
     }
 }
 
-static int vecA(const void* p, int kd) { return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (kd % 4 == 0) && kd >= 4; }
+static int vecA(bool unal, int kd) { return !unal && (kd % 4 == 0) && kd >= 4; }
 
 // 1 if the MFMA path applies (stride 1, deep enough reduction, enough filters).  The three launchers below are that path
 // only: conv_route (conv.hip) has already sent the shapes of the LDS-tile kernels to conv_tile.hip.
@@ -374,20 +374,66 @@ extern "C" int tn_conv_mfma_supported(int C, int K, int f, int stride) {
     return stride == 1 && C * f * f >= 32 && K >= 16;
 }
 
+// ---- what the launchers choose, from the shape, the alignment of the A rows and the CU count (tn_conv_mfma_plan reports
+// it): the geometry fields of ConvMG and the PADDED template argument ------------------------------------------------
+// forward kernel on the gathered tensor (N, C, H, Wd), K rows of A, window f, padding pad, pixels (Ho, Wo); 0: too large
+static int cm_fwd_geom(ConvMG& g, bool a_unal, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
+    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.f = f; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
+    g.Kd = C * f * f; g.M = N * Ho * Wo; g.a_vec = vecA(a_unal, g.Kd);
+    g.KT = cdiv(K, 64); g.MT = cdiv(g.M, 64);
+    return (long long)N * C * H * Wd < (1ll << 31) && (long long)N * K * Ho * Wo < (1ll << 31);
+}
+static bool cm_padded(int f, int pad, int H, int Wd, int Ho, int Wo) { return pad > 0 || Ho + f - 1 > H || Wo + f - 1 > Wd; }
+static int cm_grid(const ConvMG& g) { return 8 * cdiv(g.MT, 8) * g.KT; }
+// dx = conv_fwd(dz, Wt) with padding f-1-pad: gathered tensor = dz (N,K,Ho,Wo), rows = C maps; Wt is scratch (tn_scratch_get: 256-byte aligned)
+static int cm_dgrad_geom(ConvMG& g, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
+    return cm_fwd_geom(g, false, N, K, Ho, Wo, C, f, f - 1 - pad, H, Wd);
+}
+static int cm_wgrad_geom(ConvMG& g, int num_cus, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
+    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.f = f; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
+    g.Kd = C * f * f; g.M = N * Ho * Wo;
+    g.KT = cdiv(K, 64); g.MT = cdiv(g.Kd, 64);
+    // pixel slabs: a multiple of 8 (one or more per XCD), enough blocks to fill the chip
+    int S = 8;
+    while (S < 64 && (long long)S * g.KT * g.MT < 2 * num_cus && g.M / (2 * S) >= 8 * CM_BK) S *= 2;
+    g.S = S;
+    g.mchunk = cdiv(cdiv(g.M, S), CM_BK) * CM_BK;
+    return (long long)N * C * H * Wd < (1ll << 31) && (long long)N * K * Ho * Wo < (1ll << 31);
+}
+
+int tn_conv_mfma_plan(ConvProduct prod, int num_cus, unsigned al, int N, int C, int H, int Wd, int K, int f, int pad, int Ho,
+                      int Wo, ConvPlan* p) {
+    ConvMG g{};
+    p->route = CONV_MFMA;
+    if (prod == CONV_WGRAD) {
+        if (!cm_wgrad_geom(g, num_cus, N, C, H, Wd, K, f, pad, Ho, Wo)) return 0;
+        p->kernel = CVK_MFMA_WGRAD;
+        p->t[0] = cm_padded(f, pad, H, Wd, Ho, Wo);
+        const int v[6] = {g.KT, g.MT, g.Kd, g.M, g.S, g.mchunk};
+        memcpy(p->v, v, sizeof v);
+        return 1;
+    }
+    const bool dgrad = prod == CONV_DGRAD;
+    if (!(dgrad ? cm_dgrad_geom(g, N, C, H, Wd, K, f, pad, Ho, Wo)
+                : cm_fwd_geom(g, al & CONV_UNAL_W, N, C, H, Wd, K, f, pad, Ho, Wo))) return 0;
+    p->kernel = CVK_MFMA;
+    p->t[0] = dgrad || cm_padded(f, pad, H, Wd, Ho, Wo);
+    p->t[1] = dgrad;
+    const int v[6] = {g.KT, g.MT, g.Kd, g.M, g.a_vec, dgrad && !(al & CONV_BARE)};
+    memcpy(p->v, v, sizeof v);
+    return 1;
+}
+
 int tn_conv_mfma_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N,
                      int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo, int act, float prm) {
     ConvMG g{};
-    g.x = x; g.W = W; g.out = a; g.bias = b;
-    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.f = f; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
-    g.Kd = C * f * f; g.M = N * Ho * Wo; g.act = act; g.prm = prm; g.a_vec = vecA(W, g.Kd);
-    g.KT = cdiv(K, 64); g.MT = cdiv(g.M, 64);
-    TN_REQUIRE((long long)N * C * H * Wd < (1ll << 31) && (long long)N * K * Ho * Wo < (1ll << 31),
+    TN_REQUIRE(cm_fwd_geom(g, conv_unal(W), N, C, H, Wd, K, f, pad, Ho, Wo),
                "tn_conv_mfma_fwd: tensor too large for 32-bit offsets");
-    const int grid = 8 * cdiv(g.MT, 8) * g.KT;
-    if (pad > 0 || Ho + f - 1 > H || Wo + f - 1 > Wd)
-        conv_mfma_fwd_kernel<true, false><<<grid, 256, 0, ctx->stream>>>(g);
+    g.x = x; g.W = W; g.out = a; g.bias = b; g.act = act; g.prm = prm;
+    if (cm_padded(f, pad, H, Wd, Ho, Wo))
+        conv_mfma_fwd_kernel<true, false><<<cm_grid(g), 256, 0, ctx->stream>>>(g);
     else
-        conv_mfma_fwd_kernel<false, false><<<grid, 256, 0, ctx->stream>>>(g);
+        conv_mfma_fwd_kernel<false, false><<<cm_grid(g), 256, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
@@ -395,7 +441,6 @@ int tn_conv_mfma_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b
 int tn_conv_mfma_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H,
                        int Wd, int K, int f, int pad, int Ho, int Wo, const float* prev_a, int act,
                        float prm) {
-    // dx = conv_fwd(dz, Wt) with padding f-1-pad: gathered tensor = dz (N,K,Ho,Wo), rows = C maps
     const size_t wt_bytes = (size_t)K * C * f * f * sizeof(float);
     float* Wt;
     int rc = tn_scratch_get(ctx, wt_bytes, &Wt);
@@ -403,14 +448,9 @@ int tn_conv_mfma_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, 
     conv_wt_kernel<<<cdiv((long long)K * C * f * f, 256), 256, 0, ctx->stream>>>(W, Wt, K, C, f);
     TN_LAUNCH_CHECK();
     ConvMG g{};
-    g.x = dz; g.W = Wt; g.out = dx; g.prev_a = prev_a;
-    g.N = N; g.C = K; g.H = Ho; g.Wd = Wo; g.K = C; g.f = f; g.pad = f - 1 - pad; g.Ho = H; g.Wo = Wd;
-    g.Kd = K * f * f; g.M = N * H * Wd; g.act = act; g.prm = prm; g.a_vec = vecA(Wt, g.Kd);
-    g.KT = cdiv(C, 64); g.MT = cdiv(g.M, 64);
-    TN_REQUIRE((long long)N * C * H * Wd < (1ll << 31) && (long long)N * K * Ho * Wo < (1ll << 31),
-               "tn_conv_mfma_dgrad: tensor too large for 32-bit offsets");
-    const int grid = 8 * cdiv(g.MT, 8) * g.KT;
-    conv_mfma_fwd_kernel<true, true><<<grid, 256, 0, ctx->stream>>>(g);
+    TN_REQUIRE(cm_dgrad_geom(g, N, C, H, Wd, K, f, pad, Ho, Wo), "tn_conv_mfma_dgrad: tensor too large for 32-bit offsets");
+    g.x = dz; g.W = Wt; g.out = dx; g.prev_a = prev_a; g.act = act; g.prm = prm;
+    conv_mfma_fwd_kernel<true, true><<<cm_grid(g), 256, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
@@ -418,28 +458,21 @@ int tn_conv_mfma_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, 
 int tn_conv_mfma_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N,
                        int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
     ConvMG g{};
-    g.x = x; g.W = dz;
-    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.f = f; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
-    g.Kd = C * f * f; g.M = N * Ho * Wo;
-    g.KT = cdiv(K, 64); g.MT = cdiv(g.Kd, 64);
-    TN_REQUIRE((long long)N * C * H * Wd < (1ll << 31) && (long long)N * K * Ho * Wo < (1ll << 31),
+    TN_REQUIRE(cm_wgrad_geom(g, ctx->num_cus, N, C, H, Wd, K, f, pad, Ho, Wo),
                "tn_conv_mfma_wgrad: tensor too large for 32-bit offsets");
-    // pixel slabs: a multiple of 8 (one or more per XCD), enough blocks to fill the chip
-    int S = 8;
-    while (S < 64 && (long long)S * g.KT * g.MT < 2 * ctx->num_cus && g.M / (2 * S) >= 8 * CM_BK) S *= 2;
-    g.S = S;
-    g.mchunk = cdiv(cdiv(g.M, S), CM_BK) * CM_BK;
+    g.x = x; g.W = dz;
     const size_t n = (size_t)K * g.Kd;
-    int rc = tn_scratch_get(ctx, ((size_t)S * n + (size_t)S * K) * sizeof(float), &g.ws);
+    int rc = tn_scratch_get(ctx, ((size_t)g.S * n + (size_t)g.S * K) * sizeof(float), &g.ws);
     if (rc) return rc;
-    g.dbws = g.ws + (size_t)S * n;
-    const int grid = S * g.KT * g.MT;
-    if (pad > 0 || Ho + f - 1 > H || Wo + f - 1 > Wd)
+    g.dbws = g.ws + (size_t)g.S * n;
+    const int grid = g.S * g.KT * g.MT;
+    if (cm_padded(f, pad, H, Wd, Ho, Wo))
         conv_mfma_wgrad_kernel<true><<<grid, 256, 0, ctx->stream>>>(g);
     else
         conv_mfma_wgrad_kernel<false><<<grid, 256, 0, ctx->stream>>>(g);
     TN_LAUNCH_CHECK();
-    conv_mfma_wgrad_reduce<<<cdiv(n, 256), 256, 0, ctx->stream>>>(g.ws, dW, (int)n, S, g.dbws, db, K);
+    conv_mfma_wgrad_reduce<<<cdiv(n, 256), 256, 0, ctx->stream>>>(g.ws, dW, (int)n, g.S, g.dbws, db, K);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }
+

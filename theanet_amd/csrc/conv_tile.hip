@@ -239,9 +239,9 @@ static size_t ct_lds_bytes(const ConvTG& g, int FT) {
 static int ct_pick_ft(int K) { return K > 32 ? 2 : 1; }
 
 // 1 if conv_tile_kernel handles the (gathered tensor N,C,H,Wd; K filters; pad; output Ho,Wo) problem
-int tn_conv_tile_ok(const float* x, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
+int tn_conv_tile_ok(unsigned unal, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
     if (!tn_knob(TN_K_CONV_TILE) || f != 3 || pad < 0 || pad > 2) return 0;
-    if (reinterpret_cast<uintptr_t>(x) & 15) return 0;
+    if (unal) return 0;
     ConvTG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
     const int FT = ct_pick_ft(K);
@@ -278,11 +278,41 @@ static int ct_launch(tn_ctx* ctx, ConvTG& g) {
     return TN_OK;
 }
 
+// The kernel's template arguments, past POOL: FT from the filter count; NCP = 2 for first layers (forward, C <= 4: one
+// chunk, two channel pairs); and whether the epilogue stores 16 bytes (out_unal: out or prev_a is not 16-byte aligned)
+struct CtPick { int FT, NCP, vec_out; };
+static CtPick ct_pick(const ConvTG& g, bool dgrad, bool out_unal) {
+    return {ct_pick_ft(g.K), !dgrad && g.C <= 4 ? 2 : 4, (g.Wo % 4 == 0) && !out_unal};
+}
+// the kernel's problem from the LAYER's geometry: the forward as it stands; the input gradient dx (N,C,H,Wd) from dz
+// (N,K,Ho,Wo) is the forward kernel with (channels, filters) = (K, C), padding 2 - pad
+static ConvTG ct_problem(bool dgrad, int N, int C, int H, int Wd, int K, int pad, int Ho, int Wo) {
+    ConvTG g{};
+    if (dgrad) { g.N = N; g.C = K; g.H = Ho; g.Wd = Wo; g.K = C; g.pad = 2 - pad; g.Ho = H; g.Wo = Wd; }
+    else { g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.pad = pad; g.Ho = Ho; g.Wo = Wo; }
+    return g;
+}
+static bool ct_fits32(const ConvTG& g) {
+    return (long long)g.N * g.C * g.H * g.Wd < (1ll << 31) && (long long)g.N * g.K * g.Ho * g.Wo < (1ll << 31);
+}
+
+int tn_conv_tile_plan(ConvProduct prod, unsigned al, int N, int C, int H, int Wd, int K, int pad, int Ho, int Wo, ConvPlan* p) {
+    const bool dgrad = prod == CONV_DGRAD;
+    ConvTG g = ct_problem(dgrad, N, C, H, Wd, K, pad, Ho, Wo);
+    const CtPick c = ct_pick(g, dgrad, al & CONV_UNAL_OUT);
+    if (!ct_geometry(g, c.FT) || !ct_fits32(g)) return 0;
+    p->route = CONV_TILE; p->kernel = CVK_TILE;
+    p->t[0] = c.FT; p->t[1] = dgrad; p->t[2] = c.NCP;
+    const int v[9] = {g.KT, g.MT, g.RT, g.NI, g.TH, g.nchunk, c.vec_out, g.pad, dgrad && !(al & CONV_BARE)};
+    memcpy(p->v, v, sizeof v);
+    return 1;
+}
+
 static int ct_run(tn_ctx* ctx, ConvTG& g, const float* W, bool dgrad, bool pool = false) {
-    const int FT = ct_pick_ft(g.K);
+    const CtPick c = ct_pick(g, dgrad, conv_unal(g.out, g.prev_a));
+    const int FT = c.FT;
     TN_REQUIRE(ct_geometry(g, FT), "conv_tile: unsupported shape");
-    TN_REQUIRE((long long)g.N * g.C * g.H * g.Wd < (1ll << 31) && (long long)g.N * g.K * g.Ho * g.Wo < (1ll << 31),
-               "conv_tile: tensor too large for 32-bit offsets");
+    TN_REQUIRE(ct_fits32(g), "conv_tile: tensor too large for 32-bit offsets");
     const int KBF = 32 * FT, total = g.KT * g.nchunk * 4 * 9 * 2 * KBF;
     float* wt;
     int rc = tn_scratch_get(ctx, (size_t)total * sizeof(float), &wt);
@@ -291,8 +321,8 @@ static int ct_run(tn_ctx* ctx, ConvTG& g, const float* W, bool dgrad, bool pool 
                                                                   dgrad ? 1 : 0);
     TN_LAUNCH_CHECK();
     g.wt = wt;
-    g.vec_out = (g.Wo % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.out) | reinterpret_cast<uintptr_t>(g.prev_a)) & 15) == 0;
-    if (!dgrad && g.C <= 4) {        // first layers: one chunk, two channel pairs
+    g.vec_out = c.vec_out;
+    if (c.NCP == 2) {
         if (pool) return FT == 2 ? ct_launch<2, false, true, 2>(ctx, g) : ct_launch<1, false, true, 2>(ctx, g);
         return FT == 2 ? ct_launch<2, false, false, 2>(ctx, g) : ct_launch<1, false, false, 2>(ctx, g);
     }
@@ -306,19 +336,16 @@ static int ct_run(tn_ctx* ctx, ConvTG& g, const float* W, bool dgrad, bool pool 
 
 int tn_conv_tile_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C,
                      int H, int Wd, int K, int pad, int Ho, int Wo, int act, float prm) {
-    ConvTG g{};
+    ConvTG g = ct_problem(false, N, C, H, Wd, K, pad, Ho, Wo);
     g.x = x; g.out = a; g.bias = b;
-    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K; g.pad = pad; g.Ho = Ho; g.Wo = Wo;
     g.act = act; g.prm = prm;
     return ct_run(ctx, g, W, false);
 }
 
-// dx (N,C,H,Wd) from dz (N,K,Ho,Wo): the forward kernel with (channels, filters) = (K, C), padding 2 - pad
 int tn_conv_tile_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H,
                        int Wd, int K, int pad, int Ho, int Wo, const float* prev_a, int act, float prm) {
-    ConvTG g{};
+    ConvTG g = ct_problem(true, N, C, H, Wd, K, pad, Ho, Wo);
     g.x = dz; g.out = dx; g.prev_a = prev_a;
-    g.N = N; g.C = K; g.H = Ho; g.Wd = Wo; g.K = C; g.pad = 2 - pad; g.Ho = H; g.Wo = Wd;
     g.act = act; g.prm = prm;
     return ct_run(ctx, g, W, true);
 }
@@ -524,6 +551,8 @@ __global__ __launch_bounds__(256) void conv_tile_wgrad_kernel(ConvWG g) {
 
 static int cw_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
 
+static int cw_nft(int K) { return K > 32 ? 2 : 1; }      // filter tiles of a block: the kernel's NFT
+
 static int cw_geometry(ConvWG& g, int num_cus) {
     const int lgW = cw_log2(g.Wd);
     if (lgW < 3 || lgW > 6) return 0;                  // rows of 8..64 pixels
@@ -545,7 +574,7 @@ static int cw_geometry(ConvWG& g, int num_cus) {
     g.q4 = g.Wd / 4;
     g.nx4 = 32 * g.NI * g.THi * g.q4;
     if (g.nx4 > 8 * 256) return 0;
-    const int NFT = g.K > 32 ? 2 : 1;
+    const int NFT = cw_nft(g.K);
     g.KG = cdiv(g.K, 32 * NFT);
     g.CG = cdiv(g.C, 32);
     int S = num_cus / (g.KG * g.CG);
@@ -559,19 +588,33 @@ static int cw_geometry(ConvWG& g, int num_cus) {
 }
 
 static size_t cw_lds_bytes(const ConvWG& g) {
-    const int NFT = g.K > 32 ? 2 : 1;
+    const int NFT = cw_nft(g.K);
     return (size_t)2 * (32 * NFT * CW_DZS + 32 * g.plane) * sizeof(float);
 }
 
-int tn_conv_tile_wgrad_ok(tn_ctx* ctx, const float* x, const float* dz, int N, int C, int H, int Wd, int K,
-                          int f, int pad, int Ho, int Wo) {
+int tn_conv_tile_wgrad_ok(int num_cus, unsigned unal, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
     if (!tn_knob(TN_K_CONV_TILE) || f != 3 || pad != 1 || Ho != H || Wo != Wd) return 0;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) return 0;
+    if (unal) return 0;
     if (!tn_knob(TN_K_CONV_TILE_WGRAD)) return 0;
     ConvWG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
-    if (!cw_geometry(g, ctx->num_cus)) return 0;
+    if (!cw_geometry(g, num_cus)) return 0;
     return cw_lds_bytes(g) <= 160 * 1024;
+}
+
+static bool cw_fits32(const ConvWG& g) {
+    return (long long)g.N * g.C * g.H * g.Wd < (1ll << 31) && (long long)g.N * g.K * g.H * g.Wd < (1ll << 31);
+}
+
+int tn_conv_tile_wgrad_plan(int num_cus, int N, int C, int H, int Wd, int K, ConvPlan* p) {
+    ConvWG g{};
+    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
+    if (!cw_geometry(g, num_cus) || !cw_fits32(g)) return 0;
+    p->route = CONV_TILE; p->kernel = CVK_TILE_WGRAD;
+    p->t[0] = cw_nft(K);
+    const int v[7] = {g.KG, g.CG, g.S, g.ipb, g.NI, g.RT, g.NT};
+    memcpy(p->v, v, sizeof v);
+    return 1;
 }
 
 template <int NFT, bool POOL>
@@ -590,9 +633,8 @@ static int cw_launch(tn_ctx* ctx, ConvWG& g) {
 
 static int cw_run(tn_ctx* ctx, ConvWG& g, float* dW, float* db, bool pool) {
     TN_REQUIRE(cw_geometry(g, ctx->num_cus), "conv_tile_wgrad: unsupported shape");
-    TN_REQUIRE((long long)g.N * g.C * g.H * g.Wd < (1ll << 31) && (long long)g.N * g.K * g.H * g.Wd < (1ll << 31),
-               "conv_tile_wgrad: tensor too large for 32-bit offsets");
-    const int NFT = g.K > 32 ? 2 : 1, PS = 4 / NFT;
+    TN_REQUIRE(cw_fits32(g), "conv_tile_wgrad: tensor too large for 32-bit offsets");
+    const int NFT = cw_nft(g.K), PS = 4 / NFT;
     const size_t n = (size_t)g.K * g.C * 9;
     int rc = tn_scratch_get(ctx, ((size_t)g.S * PS * n + (size_t)g.S * g.K) * sizeof(float), &g.ws);
     if (rc) return rc;
@@ -843,9 +885,11 @@ extern "C" int tn_convpool_smallc_supported(int N, int C, int H, int Wd, int K, 
     return cs_geometry(g, 256);
 }
 
+static bool cs_fits32(const ConvSG& g) { return (long long)g.N * g.K * g.H * g.Wd < (1ll << 31); }
+
 static int cs_run(tn_ctx* ctx, ConvSG& g, float* dW, float* db, bool pool) {
     TN_REQUIRE(cs_geometry(g, ctx->num_cus), "conv_tile_smallc: unsupported shape");
-    TN_REQUIRE((long long)g.N * g.K * g.H * g.Wd < (1ll << 31), "conv_tile_smallc: tensor too large for 32-bit offsets");
+    TN_REQUIRE(cs_fits32(g), "conv_tile_smallc: tensor too large for 32-bit offsets");
     const size_t n = (size_t)g.K * g.C * 9;
     int rc = tn_scratch_get(ctx, ((size_t)g.S * 4 * n + (size_t)g.S * g.K) * sizeof(float), &g.ws);
     if (rc) return rc;
@@ -872,10 +916,9 @@ int tn_conv_tile_smallc_bwd(tn_ctx* ctx, const float* x, const float* g_, const 
 }
 
 // unfused first layers: dW, db from the plain dz tensor
-int tn_conv_tile_smallc_ok(const float* x, const float* dz, int N, int C, int H, int Wd, int K, int f, int pad,
-                           int Ho, int Wo) {
+int tn_conv_tile_smallc_ok(unsigned unal, int N, int C, int H, int Wd, int K, int f, int pad, int Ho, int Wo) {
     if (!tn_knob(TN_K_CONV_TILE) || f != 3 || pad != 1 || Ho != H || Wo != Wd || C * 9 > 32 || K < 16) return 0;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz)) & 15) return 0;
+    if (unal) return 0;
     if (!tn_knob(TN_K_CONV_TILE_SMALLC)) return 0;
     ConvSG g{};
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
@@ -888,4 +931,14 @@ int tn_conv_tile_smallc_wgrad(tn_ctx* ctx, const float* x, const float* dz, floa
     g.x = x; g.dz = dz;
     g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
     return cs_run(ctx, g, dW, db, false);
+}
+
+int tn_conv_tile_smallc_plan(int num_cus, int N, int C, int H, int Wd, int K, ConvPlan* p) {
+    ConvSG g{};
+    g.N = N; g.C = C; g.H = H; g.Wd = Wd; g.K = K;
+    if (!cs_geometry(g, num_cus) || !cs_fits32(g)) return 0;
+    p->route = CONV_TILE_SMALLC; p->kernel = CVK_TILE_SMALLC;
+    const int v[6] = {g.KG, g.S, g.ipb, g.NI, g.RT, g.NT};
+    memcpy(p->v, v, sizeof v);
+    return 1;
 }

@@ -1669,7 +1669,7 @@ static bool fc_head_train_skinny(int n_in, int n_out, const float* x, const floa
 }
 
 // the current device's CU count (what tn_ctx_create stores in ctx->num_cus), 256 = MI355X where no device answers
-static int fc_current_cus() {
+int tn_current_cus() {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
@@ -1685,7 +1685,7 @@ extern "C" {
 // are read for their alignment only).  Layout and flags: include/theanet_hip.h.
 int tn_fc_plan(int op, int B, int n_in, int n_out, int num_cus, unsigned flags, int* out, int nout) {
     if (B <= 0 || n_in <= 0 || n_out <= 0 || op < 0 || op > 6 || num_cus < 0 || (nout > 0 && !out)) return TN_E_ARG;
-    if (num_cus == 0) num_cus = fc_current_cus();
+    if (num_cus == 0) num_cus = tn_current_cus();
     const bool unal = flags & 1, bare = flags & 2, rider = flags & 4, elem_odd = flags & 8;
     float* const f = reinterpret_cast<float*>(static_cast<uintptr_t>(unal ? 0x1004 : 0x1000));
     uint8_t* const m = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(unal ? 0x1001 : 0x1000));

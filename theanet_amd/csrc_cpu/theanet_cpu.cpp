@@ -293,6 +293,7 @@ int tn_event_query(tn_ctx*, void*, int* done) { *done = 1; return TN_OK; }      
 
 // ================================== conv (im2col + SGEMM) ==================================
 int tn_conv_mfma_supported(int, int, int, int) { return 0; }
+int tn_conv_plan(int, int, int, int, int, int, int, int, int, int, int, int, unsigned, int*, int) { return TN_E_ARG; }
 
 // col[(c,u,v)][i*Wo+j] = xpad[c][i*s+u][j*s+v]
 static void im2col(const float* x, int C, int H, int Wd, int f, int s, int pad, int Ho, int Wo, float* col) {
