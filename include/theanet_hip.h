@@ -362,6 +362,42 @@ int tn_c8_conv1_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int
                       const void* prev_a, int prev_act, float prev_prm, int pooled, const uint8_t* mask);
 int tn_c8_conv1_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int K,
                       int pooled, const uint8_t* mask);
+/* ConvLayers of any filter, mode and stride on c8 tensors (replace conv2d(inpt, W, subsample=(stride, stride)) + b on the
+ * padded input and the activation of convpool.py:54-72, and their gradients, for every conv shape the two tiled families
+ * above refuse; the training param CONV_SHAPES 'any'; theanet_amd/csrc/convg_c8.hip).  Tensors: x / dx N x C maps of S
+ * pixels a side stored at pitch P, y / dz N x K maps of So pixels stored at pitch Po (a pitch is the side itself, any size,
+ * or a power of two above it: tn_c8_pool_supported's rule), either element type; W (K, C, f, f) fp32 master weights in
+ * tn_conv2d_*'s orientation (Theano's conv2d), b (K) fp32.  `pad` is the low padding as in tn_conv2d_*; the high padding
+ * follows from So, (So - 1) stride + f - pad - S (negative: the last window ends before the map does), so an even filter
+ * in 'same' mode works (f = 4: 2 low, 1 high, as ConvLayer computes it).  C and K need not be multiples of 8.
+ * Arithmetic: tn_c8_conv_fwd's -- x and dz as stored, W rounded to the 16-bit type (nearest even), exact products, fp32
+ * accumulation on the matrix core, bias / activation on the fp32 sums, one rounding on store.
+ * fwd: y = act(conv(x, W) + b).  dgrad: dx = R(conv^T(dz, W) * act'(prev_a)); prev_a: the stored output of the layer below
+ *   (dx's shape; NULL: no derivative).  EVERY cell of y / dx is written by the op (no tn_c8_pad_zero): pad cells, channels
+ *   past K / C and -- with a stride -- input pixels no window touches as exact +0.
+ * wgrad: dW (K, C, f, f), db (K) fp32, OVERWRITE, the gradient scale removed in the fp32 epilogue; db is summed from the
+ *   stored dz.  Slab sums in context scratch finished by the context's reduction: no atomics, a slab count that depends on
+ *   the geometry alone, one order, the same bits every run and on every device.
+ * supported: 1 for every N, C, K, f, stride >= 1 whose geometry is consistent -- pitches as above, pad <= f / 2,
+ *   -stride < high padding <= pad (So is the number of windows that fit, no more padding than a 'same' layer's) -- with
+ *   fewer than 2^32 cells per tensor, K C f f < 2^28 and f, stride < 2^15.  Anything else, and any NULL tensor:
+ *   TN_E_ARG naming the entry point, nothing launched.
+ * plan (no device; TN_E_ARG for a refused geometry and on the CPU backend): what call `op` (0 fwd, 1 dgrad, 2 wgrad) takes,
+ *   8 values: kernel (0 forward, 1 input gradient stride 1, 2 input gradient strided, 3 weight gradient), leaky-ReLU
+ *   epilogue, octets of the reduced maps (fwd: channels, dgrad: filters; wgrad: channels), reduction steps of 2 cells
+ *   (wgrad: tiles of 64 output pixels), ragged reduction tail (bit 0: half a step past the last (tap, octet) cell, bit 1: a
+ *   ragged octet; wgrad: a partial last pixel tile), 32-row tiles (wgrad: column groups x filter groups), blocks of 256
+ *   pixels (wgrad: slabs), ragged output (bit 0: a partial last pixel block -- wgrad: column group --, bit 1: a partial row
+ *   tile -- wgrad: filter group).  Returns 8.                                                                             */
+int tn_c8_convg_supported(int N, int C, int S, int P, int K, int f, int stride, int pad, int So, int Po);
+int tn_c8_convg_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, int N, int C, int S, int P, int K,
+                    int f, int stride, int pad, int So, int Po, int act, float prm);
+int tn_c8_convg_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int S, int P, int K, int f,
+                      int stride, int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);
+int tn_c8_convg_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int K,
+                      int f, int stride, int pad, int So, int Po);
+int tn_c8_convg_plan(int op, int N, int C, int S, int P, int K, int f, int stride, int pad, int So, int Po, int act,
+                     float prm, int* out, int nout);
 /* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
  * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
  * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on

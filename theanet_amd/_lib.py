@@ -120,6 +120,11 @@ SIGNATURES = {
     "tn_c8_conv1_fwd": (c_int, [CTX, P, P, P, P, P] + [c_int] * 6 + [c_float, c_int]),
     "tn_c8_conv1_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 5 + [P, c_int, c_float, c_int, P]),
     "tn_c8_conv1_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_int, P]),
+    "tn_c8_convg_supported": (c_int, [c_int] * 10),
+    "tn_c8_convg_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 11 + [c_float]),
+    "tn_c8_convg_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 10 + [P, c_int, c_float]),
+    "tn_c8_convg_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 10),
+    "tn_c8_convg_plan": (c_int, [c_int] * 12 + [c_float, POINTER(c_int), c_int]),
     "tn_c8_pack_pitch": (c_int, [CTX, P, c_int64, P] + [c_int] * 4 + [c_float]),
     "tn_c8_pad_zero": (c_int, [CTX, P] + [c_int] * 4),
     "tn_c8_crop": (c_int, [CTX, P, P] + [c_int] * 4),

@@ -242,6 +242,14 @@ int tn_c8_conv1_dgrad(tn_ctx* ctx, const void*, const float*, void*, int, int, i
                       const uint8_t*) { NOT_HERE("tn_c8_conv1_dgrad"); }
 int tn_c8_conv1_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, int, int, int, int, int, int,
                       const uint8_t*) { NOT_HERE("tn_c8_conv1_wgrad"); }
+int tn_c8_convg_supported(int, int, int, int, int, int, int, int, int, int) { return 0; }
+int tn_c8_convg_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int,
+                    int, int, float) { NOT_HERE("tn_c8_convg_fwd"); }
+int tn_c8_convg_dgrad(tn_ctx* ctx, const void*, const float*, void*, int, int, int, int, int, int, int, int, int, int,
+                      const void*, int, float) { NOT_HERE("tn_c8_convg_dgrad"); }
+int tn_c8_convg_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, int,
+                      int) { NOT_HERE("tn_c8_convg_wgrad"); }
+int tn_c8_convg_plan(int, int, int, int, int, int, int, int, int, int, int, int, float, int*, int) { return TN_E_ARG; }
 int tn_c8_pack_pitch(tn_ctx* ctx, const float*, int64_t, void*, int, int, int, int, float) { NOT_HERE("tn_c8_pack_pitch"); }
 int tn_c8_pad_zero(tn_ctx* ctx, void*, int, int, int, int) { NOT_HERE("tn_c8_pad_zero"); }
 int tn_c8_crop(tn_ctx* ctx, const void*, void*, int, int, int, int) { NOT_HERE("tn_c8_crop"); }

@@ -1,28 +1,35 @@
 """What the layers of the 16-bit-resident conv stack (DTYPE 'float16' / 'bfloat16': device.C8Array tensors, the tn_c8_*
-kernels) share on the host: the stack's grammar, the two conv families, the detour of a padded tensor through a dense
+kernels) share on the host: the stack's grammar, the conv families, the detour of a padded tensor through a dense
 copy, and the table of the conv weights arranged as MFMA operand tiles."""
 from collections import namedtuple
 
 import numpy as np
 
-from ..device import C8Array
+from ..device import C8Array, c8_pitch, c8_pool_pitch
 
 
-def pool_stands_alone(pool_sz, fused=True):
+def pool_stands_alone(pool_sz, fused=True, below=None, any_shapes=False):
     """Which of its two forms a PoolLayer on the stack takes: a 2x2 one is the second half of the fused conv + pool block
     of the ConvLayer below it while the net fuses (``fused``: NeuralNet.fuse_conv_pool); every other one -- and every one
-    of a net that does not fuse -- stands alone (tn_c8_pool_fwd / tn_c8_pool_bwd)."""
-    return not (fused and pool_sz == 2)
+    of a net that does not fuse -- stands alone (tn_c8_pool_fwd / tn_c8_pool_bwd).  ``any_shapes`` (the net's
+    CONV_SHAPES 'any') with the layer ``below``: a 2x2 one stands alone too where the block cannot take it -- above a
+    ConvLayer of the general family (ConvFamily.pools false: never fused) and on an odd map."""
+    if not (fused and pool_sz == 2):
+        return True
+    if any_shapes and type(below).__name__ == "ConvLayer":
+        fam = getattr(below, "c8_fam", None)
+        return (fam is not None and not fam.pools) or below.out_sz % 2 != 0
+    return False
 
 
-def check_follows(dtype, below, kind, pool_sz=None, fused=True):
+def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False):
     """The stack's grammar, asserted before a layer of class ``kind`` (its name) is built on the stack tensor that layer
     ``below`` puts out: Conv / Pool / Mean / DropOut layers pass stack tensors on (a MeanLayer closes the stack with an
     fp32 (N, C) output), a HiddenLayer consumes one.  A fused PoolLayer (pool_stands_alone) exists only inside the block
     of the ConvLayer directly below it, 2x2 on even maps; a stand-alone one follows any layer that puts out a stack tensor
     (its geometry is the constructor's to refuse: tn_c8_pool_supported)."""
     below_kind = type(below).__name__
-    if kind == "PoolLayer" and pool_stands_alone(pool_sz, fused):
+    if kind == "PoolLayer" and pool_stands_alone(pool_sz, fused, below, any_shapes):
         assert below_kind in ("ConvLayer", "PoolLayer", "DropOutLayer"), \
             "DTYPE {}: a stand-alone PoolLayer follows a Conv, Pool or DropOut layer (got {})".format(dtype, below_kind)
         return
@@ -39,18 +46,59 @@ def check_follows(dtype, below, kind, pool_sz=None, fused=True):
         assert pool_sz == 2 and below.out_sz % 2 == 0, "DTYPE {}: pooling layers are 2x2 on even maps".format(dtype)
 
 
-# The stack's two conv shapes differ in their ops, one entry of the geometry the ops take, whether fwd / dgrad take the
-# weights as arranged operand tiles (a trailing pointer; OperandTiles) and whether a product leaves the pad cells of a
-# padded output to be zeroed afterwards (tn_c8_pad_zero).
-ConvFamily = namedtuple("ConvFamily", "fwd wgrad dgrad geom tiles pad_zero")
+# The stack's conv families differ in their ops, the geometry the ops take, whether fwd / dgrad take the weights as
+# arranged operand tiles (a trailing pointer; OperandTiles), whether a product leaves the pad cells of a padded output
+# to be zeroed afterwards (tn_c8_pad_zero) and whether the ops can pool: take the arguments of a fused conv + 2x2 pool
+# block (forward: the mask to write and the pool flag; gradients: the pooled flag and the mask) -- a family that cannot
+# is never fused (pool_stands_alone).
+ConvFamily = namedtuple("ConvFamily", "fwd wgrad dgrad geom tiles pad_zero pools")
 
 
-def conv_family(one_by_one, n, c, side, pitch, k):
-    """3x3 stride-1 'same' (conv_c8.hip: runs on the pitch x pitch shape) or 1x1 stride-1 (conv1_c8.hip: rounds its
-    operand tiles per call, writes its output's pad cells itself)."""
+def conv_family(one_by_one, n, c, side, pitch, k, general=None):
+    """3x3 stride-1 'same' (conv_c8.hip: runs on the pitch x pitch shape), 1x1 stride-1 (conv1_c8.hip: rounds its
+    operand tiles per call, writes its output's pad cells itself) or -- ``general``: (filter, stride, low padding, output
+    side, output pitch) -- any shape (convg_c8.hip: like the 1x1 family, an output pitch of its own, no pooling)."""
+    if general is not None:
+        return ConvFamily("tn_c8_convg_fwd", "tn_c8_convg_wgrad", "tn_c8_convg_dgrad", (n, c, side, pitch, k) + tuple(general),
+                          False, False, False)
     if one_by_one:
-        return ConvFamily("tn_c8_conv1_fwd", "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad", (n, c, side, pitch, k), False, False)
-    return ConvFamily("tn_c8_conv_fwd", "tn_c8_conv_wgrad", "tn_c8_conv_dgrad", (n, c, pitch, pitch, k), True, True)
+        return ConvFamily("tn_c8_conv1_fwd", "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad", (n, c, side, pitch, k), False, False,
+                          True)
+    return ConvFamily("tn_c8_conv_fwd", "tn_c8_conv_wgrad", "tn_c8_conv_dgrad", (n, c, pitch, pitch, k), True, True, True)
+
+
+def choose_conv(lib, dtype, conv_shapes, n, c, side, in_pitch, k, f, stride, mode, pad_lo, out_side):
+    """The family that runs a ConvLayer of the stack and the pitches of its maps: (ConvFamily, 1x1 family?, input pitch,
+    output pitch), from the library's capability queries alone (no device).  Maps of S pixels a side are stored at a pitch
+    P: the input's (``in_pitch``), or -- first conv layer, None -- the smallest power of two >= max(S, 8); the tiled
+    kernels run on the P x P shape, S < P pads every plane with zero rows and columns (device.C8Array), which the 'same'
+    products read as their padding, and their output keeps the pitch.  Two tiled shapes run on the stack: 3x3 stride-1
+    'same' (conv_c8.hip) and 1x1 stride-1 (conv1_c8.hip: 'valid' and 'same' are the same layer, any number of filters).
+    ``conv_shapes`` (the net's CONV_SHAPES) 'any': a shape those two refuse takes the general family (convg_c8.hip: any
+    filter, mode and stride).  Its input pitch is the input's own or -- first conv layer -- c8_pool_pitch(S): a power of
+    two up to 64 pixels (tn_c8_pack_pitch), dense above (tn_c8_pack); its output pitch is c8_pool_pitch(out_side), so
+    that any layer of the stack can follow."""
+    P = in_pitch if in_pitch is not None else c8_pitch(side)
+    one_by_one = f == 1 and stride == 1 and mode in ('valid', 'same')
+    if one_by_one:
+        ok = bool(lib.tn_c8_conv1_supported(n, c, side, P, k))
+    else:
+        ok = bool((side == P or side <= 64) and P >= 8 and mode == 'same' and
+                  lib.tn_c8_conv_supported(n, c, P, P, k, f, stride, pad_lo) and lib.tn_c8_conv_wgrad_supported(n, c, P, P, k))
+    if not ok and conv_shapes == 'any':
+        P = in_pitch if in_pitch is not None else c8_pool_pitch(side)
+        Po = c8_pool_pitch(out_side)
+        general = (f, stride, pad_lo, out_side, Po)
+        assert lib.tn_c8_convg_supported(n, c, side, P, k, *general), (
+            "DTYPE {} with CONV_SHAPES 'any' takes conv layers whose tensors have fewer than 2^32 cells and whose weights "
+            "fewer than 2^28 elements (got {}->{} maps, {}x{} at pitch {}, {} filter {} stride {}: {}x{} at pitch {})".format(
+                dtype, c, k, side, side, P, mode, f, stride, out_side, out_side, Po))
+        return conv_family(False, n, c, side, P, k, general), False, P, Po
+    assert ok, (
+        "DTYPE {} needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of at most 64 "
+        "pixels a side, stored at a pitch of at least 8, or 1x1 stride-1 conv layers (got {}->{} maps, {}x{} at "
+        "pitch {}, {} filter {} stride {})".format(dtype, c, k, side, side, P, mode, f, stride))
+    return conv_family(one_by_one, n, c, side, P, k), one_by_one, P, P
 
 
 class DenseDetour:

@@ -8,8 +8,8 @@ from collections import namedtuple
 import numpy as np
 
 from .. import _lib
-from ..device import C8_DTYPES, C8Array, c8_pitch, c8_pool_pitch, is_c8
-from .c8 import DenseDetour, conv_family
+from ..device import C8_DTYPES, C8Array, c8_pool_pitch, is_c8
+from .c8 import DenseDetour, choose_conv
 from .layer import Layer, activation_by_name, below_info
 from .weights import init_wb
 
@@ -39,7 +39,8 @@ class ConvLayer(Layer):
                  mode='valid',
                  actvn='relu50',
                  reg=(),
-                 dtype='float32'):
+                 dtype='float32',
+                 conv_shapes='tiled'):
         assert (wts is not None or rand_gen is not None)
         assert mode in ("valid", "full", "same")
         if mode == "full":
@@ -81,29 +82,15 @@ class ConvLayer(Layer):
         self.filter_sz, self.stride = filter_sz, stride
         if self.f16:
             lib = self.ctx.lib
-            # maps of S pixels a side are stored at a pitch P: the input's, or -- first conv layer -- the smallest power of
-            # two >= max(S, 8).  The kernels run on the P x P shape; S < P pads every plane with zero rows and columns
-            # (device.C8Array), which the 'same' products read as their padding.
-            self.pitch = inpt.pitch if is_c8(inpt) else c8_pitch(in_sz)
-            P = self.pitch
-            # two shapes run on the stack: 3x3 stride-1 'same' (conv_c8.hip) and 1x1 stride-1 (conv1_c8.hip: 'valid' and
-            # 'same' are the same layer, any number of filters)
-            self.c8_1x1 = filter_sz == 1 and stride == 1 and mode in ('valid', 'same')
-            if self.c8_1x1:
-                ok = bool(lib.tn_c8_conv1_supported(batch_sz, num_prev_maps, in_sz, P, num_maps))
-            else:
-                ok = (in_sz == P or in_sz <= 64) and P >= 8 and mode == 'same' and \
-                    lib.tn_c8_conv_supported(batch_sz, num_prev_maps, P, P, num_maps, filter_sz, stride, self.pad_lo) and \
-                    lib.tn_c8_conv_wgrad_supported(batch_sz, num_prev_maps, P, P, num_maps)
-            assert ok, (
-                "DTYPE {} needs 3x3 stride-1 'same' conv layers with a multiple of 8 filters on maps of at most 64 "
-                "pixels a side, stored at a pitch of at least 8, or 1x1 stride-1 conv layers (got {}->{} maps, {}x{} at "
-                "pitch {}, {} filter {} stride {})".format(self.c8_dtype, num_prev_maps, num_maps, in_sz, in_sz, P, mode,
-                                                           filter_sz, stride))
+            # which of the stack's conv families runs the layer, at which pitches its maps are stored (c8.choose_conv:
+            # construction fails there for a shape the net's CONV_SHAPES does not let onto the stack)
+            self.c8_fam, self.c8_1x1, P, Po = choose_conv(
+                lib, dtype, conv_shapes, batch_sz, num_prev_maps, in_sz, inpt.pitch if is_c8(inpt) else None, num_maps,
+                filter_sz, stride, mode, self.pad_lo, self.out_sz)
+            self.pitch = P
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
             self.x16 = None if is_c8(inpt) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz, dtype, pitch=P)
-            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, dtype, pitch=P)
-            self.c8_fam = conv_family(self.c8_1x1, batch_sz, num_prev_maps, in_sz, P, num_maps)
+            self.output = C8Array(self.ctx, batch_sz, num_maps, self.out_sz, self.out_sz, dtype, pitch=Po)
             # the weights as MFMA operand tiles (forward / input gradient): the net arranges every layer's in one launch
             # per step (c8.OperandTiles) and marks them valid until the next update; otherwise the ops do it per call
             self.wt_fwd = self.ctx.empty((lib.tn_c8_wt_elems(num_maps, num_prev_maps, 0),), np.uint16) \
@@ -129,7 +116,7 @@ class ConvLayer(Layer):
         self.reg.update(reg)
 
         self.args = (batch_sz, num_prev_maps, in_sz, num_maps, filter_sz,
-                     stride, mode, actvn, reg, dtype)
+                     stride, mode, actvn, reg, dtype, conv_shapes)
         self.representation = (
             "Conv Maps:{:2d} Filter:{} Stride:{} Mode:{} Output:{:2d} "
             "Act:{}\n\t  L1:{L1} L2:{L2} Momentum:{momentum} Rate:{rate} Max Norm:{maxnorm}"
@@ -151,7 +138,7 @@ class ConvLayer(Layer):
         family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused."""
         if self.f16:
             # what the fused block takes; any other PoolLayer of the stack stands alone (c8.check_follows)
-            return True if pool.pool_sz == 2 and self.out_sz % 2 == 0 and not pool.c8_alone else None
+            return True if pool.pool_sz == 2 and self.out_sz % 2 == 0 and not pool.c8_alone and self.c8_fam.pools else None
         if self.stride == 1 and self.ctx.lib.tn_convpool_supported(self.num_prev_maps, self.filter_sz, self.stride, pool.pool_sz):
             return "convpool"            # small channel counts (tn_convpool_fwd / tn_convpool_bwd)
         # wide 3x3 'same' layers: the LDS-tile matrix-core kernels pool in their epilogue and run the
@@ -215,8 +202,11 @@ class ConvLayer(Layer):
 
     def _c8_forward(self, out, mask):
         x, fam = self._c8_input(), self.c8_fam
-        self.ctx.call(fam.fwd, x.ptr, self.W.ptr, self.b.ptr, out.ptr, mask.ptr if mask is not None else None, *fam.geom,
-                      self.act.kind, self.act.prm, 1 if out is not self.output else 0, *self._c8_tiles(self.wt_fwd))
+        pooled = out is not self.output
+        assert fam.pools or not pooled
+        self.ctx.call(fam.fwd, x.ptr, self.W.ptr, self.b.ptr, out.ptr, *((mask.ptr if mask is not None else None,) if fam.pools else ()),
+                      *fam.geom, self.act.kind, self.act.prm, *((1 if pooled else 0,) if fam.pools else ()),
+                      *self._c8_tiles(self.wt_fwd))
         if fam.pad_zero:
             self._c8_pad_zero(out)
 
@@ -225,10 +215,12 @@ class ConvLayer(Layer):
         gradient w.r.t. the POOLED output (act' already applied by its producer), dz being formed from it and the
         pooling mask inside the kernels."""
         pool, fam = self.fused_pool, self.c8_fam
-        pooled, mask = (1, pool.mask.ptr) if pool is not None else (0, None)
+        assert fam.pools or pool is None
+        # (a family that pools: whether gout is a pooled gradient, and the block's mask)
+        pooled = ((1, pool.mask.ptr) if pool is not None else (0, None)) if fam.pools else ()
         x = self.x16 if self.x16 is not None else self.inpt
         if self.has_updates():
-            self.ctx.call(fam.wgrad, x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *fam.geom, pooled, mask)
+            self.ctx.call(fam.wgrad, x.ptr, gout.ptr, self.grads[0].ptr, self.grads[1].ptr, *fam.geom, *pooled)
         if not need_gin:
             return None
         assert self.x16 is None, "DTYPE {}: no trainable layer below the first conv layer".format(self.c8_dtype)
@@ -236,7 +228,7 @@ class ConvLayer(Layer):
             self.gin = C8Array.like(self.inpt)
         b_ptr, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
-        self.ctx.call(fam.dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *fam.geom, b_ptr, b_act, b_prm, pooled, mask,
+        self.ctx.call(fam.dgrad, gout.ptr, self.W.ptr, self.gin.ptr, *fam.geom, b_ptr, b_act, b_prm, *pooled,
                       *self._c8_tiles(self.wt_bwd))
         if fam.pad_zero:
             self._c8_pad_zero(self.gin)

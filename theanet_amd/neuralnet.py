@@ -163,6 +163,12 @@ class NeuralNet():
         assert not (self.conv_mm == 'bfloat16' and self.dtype in ('float16', 'bfloat16')), (
             "CONV 'bfloat16' with DTYPE '{}': the 16-bit conv stack already runs 16-bit products on every conv layer it "
             "takes; CONV is for float32 nets".format(self.dtype))
+        # CONV_SHAPES: 'tiled' (default) -- under a 16-bit DTYPE a ConvLayer must be one of the two tiled shapes (3x3 stride-1
+        # 'same', 1x1 stride-1) or construction fails -- or 'any': every other filter, mode and stride runs on the general
+        # family (convg_c8.hip), unfused: a PoolLayer above such a layer, or a 2x2 one on an odd map, stands alone.  The
+        # tiled shapes keep their kernels and their bits.  No effect under DTYPE 'float32' (the fp32 kernels take every shape).
+        self.conv_shapes = training_params.get('CONV_SHAPES', 'tiled')
+        assert self.conv_shapes in ('tiled', 'any'), "CONV_SHAPES must be 'tiled' or 'any', not {!r}".format(self.conv_shapes)
         # WT_AVG: d, 0 < d < 1 -- an exponential moving average of the weights (Polyak averaging) that test functions and
         # checkpoints use: a_t = a_{t-1} + c (p_t - a_{t-1}), c = fl(1 - d), p_t = the weights after step t's update and
         # max-norm projection, a_0 = the weights the net starts from (include/theanet_hip.h, tn_avg_net).  Absent, None
@@ -271,7 +277,8 @@ class NeuralNet():
         curr_layer_type = getattr(layer, layer_type)
         if is_c8(tr_inpt):
             # 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to layer as they are
-            check_follows(self.dtype, prev_tr_layer, layer_type, layer_args.get("pool_sz"), self.fuse_conv_pool)
+            check_follows(self.dtype, prev_tr_layer, layer_type, layer_args.get("pool_sz"), self.fuse_conv_pool,
+                          self.conv_shapes == 'any')
 
         if curr_layer_type in (ElasticLayer, ColorLayer, ConvLayer, PoolLayer, MeanLayer):
             use_tr_layer, k = prev_tr_layer, self.num_layers - 1
@@ -306,13 +313,15 @@ class NeuralNet():
                                    num_prev_maps,
                                    prev_out_sz,
                                    dtype=self.dtype,
+                                   conv_shapes=self.conv_shapes,
                                    **layer_args)
 
         elif curr_layer_type in (PoolLayer, MeanLayer):
             if curr_layer_type is PoolLayer and is_c8(tr_inpt):
                 # 16-bit stack: half of a fused conv + pool block, or a layer of its own that -- like a DropOutLayer --
                 # stands for the block below it (PoolLayer.act_info)
-                layer_args = dict(layer_args, c8_alone=pool_stands_alone(layer_args.get("pool_sz"), self.fuse_conv_pool))
+                layer_args = dict(layer_args, c8_alone=pool_stands_alone(layer_args.get("pool_sz"), self.fuse_conv_pool,
+                                                                         prev_tr_layer, self.conv_shapes == 'any'))
             curr_layer = curr_layer_type(tr_inpt,
                                          num_maps=num_prev_maps,
                                          in_sz=prev_out_sz,
@@ -469,6 +478,7 @@ class NeuralNet():
                 import zlib
                 sig = "|".join("%s=%s" % kv for kv in self.ctx.knobs().items())
                 sig += "|TN_POOL_MASK=%d|TN_MN_FUSED=%s" % (pool_mask_enabled(), os.environ.get("TN_MN_FUSED", ""))
+                sig += "|CONV_SHAPES=%s" % self.conv_shapes
                 sig += "|cus=%s" % self.ctx.info()[1]
                 comm.agree(float(zlib.crc32(sig.encode())), "the kernel tunables / CU count (%s)" % sig)
         self.dp.prepare(slots, host)
