@@ -278,6 +278,34 @@ int tn_c8_fcg_fwd_dropout(tn_ctx* ctx, const void* x, const float* W, const floa
 int tn_c8_fcg_dgrad(tn_ctx* ctx, const float* dz, const float* W, void* dx, int B, int C, int HW, int n_out, const void* y,
                     int act, float act_param);
 int tn_c8_fcg_wgrad(tn_ctx* ctx, const void* x, const float* dz, float* dW, float* db, int B, int C, int HW, int n_out);
+/* An output head on the 16-bit stack (training param STACK_HEAD 'any'; theanet_amd/csrc/head_c8.hip): the affine map of a
+ * head with at most 16 outputs read straight from the c8 tensor, each op ONE launch (no slab scratch, no finishing kernel)
+ * -- the stack's counterpart of tn_fc_fwd / tn_fc_softmax_nll for <= 16 classes.  tn_c8_fcg_fwd's arithmetic, argument for
+ * argument: x the dense flattened c8 tensor as stored, (B, Kc) elements, Kc = ceil(C/8)*HW*8; W (C*HW, n_out) fp32 in NCHW
+ * row order, walked through the row map k -> (8 o + e) * HW + p and rounded nearest-even to the element type as it is
+ * loaded; exact products, fp32 accumulation on the 16x16x32 matrix core; bias and activation on the fp32 sum; z fp32.  Rows
+ * of W for channels past C are never read, nothing is read or written past an operand, no alignment of n_out is assumed.
+ * No atomics: the same call gives the same bits.
+ * head_fwd: z = act(x . W16 + b) (the heads' activations: linear, sigmoid, scaled_tanh; any TN_ACT_* code).
+ * head_softmax_nll: logits = x . W16 + b -- tn_c8_head_fwd's linear z bit for bit -- and tn_softmax_nll's statement on
+ *   them in the same launch: logprob, rowloss, pred (the first maximum), rowp, dz = (softmax - onehot) * inv_batch; labels
+ *   y[y_row0 + *d_row0 + row] (d_row0 NULL: 0); y, rowloss, rowp and dz may be NULL as in tn_fc_softmax_nll (without y
+ *   the other three must be).
+ * supported: 1 for 1 <= n_out <= 16 within tn_c8_fcg_supported's index limits (0 for every shape with TN_C8_HEAD=0 in the
+ *   environment: heads then take the dense families' forward and the row kernels).  Anything else, or a NULL x, W, b, z /
+ *   logits, logprob or pred: TN_E_ARG by name, nothing launched.
+ * plan (no device): op 0 (head_fwd) / 1 (head_softmax_nll) -> instantiation (= op), row tiles of 16 samples (blocks),
+ *   reduction steps of 4 cells, waves of a block (1 to 16, from the steps alone: they split the steps into contiguous runs
+ *   and meet in a fixed order), steps of the busiest wave, padding rows of the last tile, padding cells of the last step,
+ *   padding channels of the last octet, HW == 1; returns how many values the plan has, TN_E_ARG for a refused shape (and
+ *   always on the CPU backend).                                                                                       */
+int tn_c8_head_supported(int B, int C, int HW, int n_out);
+int tn_c8_head_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, float* z, int B, int C, int HW, int n_out,
+                   int act, float act_param);
+int tn_c8_head_softmax_nll(tn_ctx* ctx, const void* x, const float* W, const float* b, float* logits, int B, int C, int HW,
+                           int n_out, const int32_t* y, int64_t y_row0, const int64_t* d_row0, float* logprob,
+                           float* rowloss, int32_t* pred, float* rowp, float* dz, float inv_batch);
+int tn_c8_head_plan(int op, int B, int C, int HW, int n_out, int* out, int nout);
 /* NCHW fp32 (rows row0.. of a dataset) -> c8 fp16 and back; values are multiplied by scale                        */
 int tn_c8_pack(tn_ctx* ctx, const float* x, int64_t row0, void* out, int N, int C, int HW, float scale);
 /* tn_elastic_apply (below; inlayers.py:126-142) whose output is the c8 tensor the first conv layer consumes: the same

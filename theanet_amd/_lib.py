@@ -105,6 +105,10 @@ SIGNATURES = {
     "tn_c8_fcg_fwd_dropout": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_float, P, c_float, c_uint64, c_uint32, P, c_uint64]),
     "tn_c8_fcg_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 4 + [P, c_int, c_float]),
     "tn_c8_fcg_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 4),
+    "tn_c8_head_supported": (c_int, [c_int] * 4),
+    "tn_c8_head_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 5 + [c_float]),
+    "tn_c8_head_softmax_nll": (c_int, [CTX, P, P, P, P] + [c_int] * 4 + [P, c_int64, P, P, P, P, P, P, c_float]),
+    "tn_c8_head_plan": (c_int, [c_int] * 5 + [POINTER(c_int), c_int]),
     "tn_c8_pack": (c_int, [CTX, P, c_int64, P, c_int, c_int, c_int, c_float]),
     "tn_c8_unpack": (c_int, [CTX, P, P, c_int, c_int, c_int, c_float]),
     "tn_c8_mean_fwd": (c_int, [CTX, P, P] + [c_int] * 4),

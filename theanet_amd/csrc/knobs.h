@@ -1,7 +1,8 @@
 // The library's environment switches (TN_*), one row each: name, default, parse form, whether data-parallel ranks
 // must agree on it, what it does.  A switch that fixes a slab count or a kernel form fixes the order in which partial
 // sums are added, and replicas must stay bit-identical: tn_knobs (include/theanet_hip.h) exports the resolved values
-// of those rows and NeuralNet checks them across ranks.  Debug rows (cycle stamps, ablations) are not agreed.
+// of those rows and NeuralNet checks them across ranks.  Debug rows (cycle stamps, ablations) are not agreed; nor is a
+// switch whose effect the host sees in a capability query and puts into the ranks' agreement itself (C8_HEAD).
 // Plain C++, included by both backends (common.h, theanet_cpu.cpp).
 #pragma once
 #include <cstdio>
@@ -26,6 +27,8 @@ enum tn_knob_form { TN_KF_ATOI, TN_KF_POS, TN_KF_NOT0, TN_KF_SET };
     X(FC8_FIN, 1, ATOI, 1, "0: the finishing launch also for one K slab (A/B)")                                       \
     X(FC8_WSLABS, 2, ATOI, 1, "weight-gradient sample slabs: n half blocks per CU")                                   \
     X(FC8_DZ16, 1, ATOI, 1, "0: rounding dz to 16 bits stays a launch of its own (A/B)")                              \
+    /* head_c8.hip: an output head on the fp16 / bf16 conv stack */                                                   \
+    X(C8_HEAD, 1, ATOI, 0, "0: no head kernels (tn_c8_head_supported answers 0): heads take the dense families")      \
     /* conv_tile.hip: the fp32 tile conv kernels */                                                                   \
     X(CONV_TILE, 1, NOT0, 1, "0: none of the tile kernels")                                                           \
     X(CONV_TILE_WGRAD, 1, NOT0, 1, "0: no tile weight gradient")                                                      \

@@ -215,6 +215,15 @@ int tn_c8_fcg_dgrad(tn_ctx* ctx, const float*, const float*, void*, int, int, in
     NOT_HERE("tn_c8_fcg_dgrad");
 }
 int tn_c8_fcg_wgrad(tn_ctx* ctx, const void*, const float*, float*, float*, int, int, int, int) { NOT_HERE("tn_c8_fcg_wgrad"); }
+int tn_c8_head_supported(int, int, int, int) { return 0; }
+int tn_c8_head_fwd(tn_ctx* ctx, const void*, const float*, const float*, float*, int, int, int, int, int, float) {
+    NOT_HERE("tn_c8_head_fwd");
+}
+int tn_c8_head_softmax_nll(tn_ctx* ctx, const void*, const float*, const float*, float*, int, int, int, int, const int32_t*,
+                           int64_t, const int64_t*, float*, float*, int32_t*, float*, float*, float) {
+    NOT_HERE("tn_c8_head_softmax_nll");
+}
+int tn_c8_head_plan(int, int, int, int, int, int*, int) { return TN_E_ARG; }
 int tn_c8_pack(tn_ctx* ctx, const float*, int64_t, void*, int, int, int, float) { NOT_HERE("tn_c8_pack"); }
 int tn_c8_elastic_apply(tn_ctx* ctx, const float*, int64_t, const int64_t*, void*, int, int, int, int, int, int, const int32_t*,
                         const float*, const float*, float, const uint8_t*, uint64_t, uint32_t, const uint32_t*, int64_t) {

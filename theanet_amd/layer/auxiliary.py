@@ -178,8 +178,7 @@ class SoftAuxLayer(HiddenLayer, OutputLayer):
 
     def forward(self, train=True, y=None, y_row0=0, d_row0=None, cost_scale=None, below=None):
         c, B = self.ctx, self.batch_sz
-        c.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.logits.ptr, B, self.n_in, self.n_out,
-               _lib.TN_ACT_LINEAR, 0.0, None)
+        self.affine(_lib.TN_ACT_LINEAR, 0.0)
         self.aux.forward(train)
         c.call("tn_fc_fwd", self.aux.output.ptr, self.cross_w.ptr, self.cross_b.ptr, self._cross.ptr, B,
                self.n_aux[-1], self.n_out, _lib.TN_ACT_LINEAR, 0.0, None)

@@ -22,10 +22,17 @@ def pool_stands_alone(pool_sz, fused=True, below=None, any_shapes=False):
     return False
 
 
-def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False):
+# the output heads that can close the stack (STACK_HEAD 'any'): each is a HiddenLayer -- which consumes stack tensors --
+# plus a row kernel on its fp32 output.  (AuxConcatLayer is not one: it concatenates fp32 features.)
+STACK_HEADS = ("SoftmaxLayer", "SoftAuxLayer", "HingeLayer", "ExpLossLayer", "CenteredOutLayer")
+HEAD_HINT = "training param STACK_HEAD: 'any' lets an output head close the stack"
+
+
+def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False, stack_head=False):
     """The stack's grammar, asserted before a layer of class ``kind`` (its name) is built on the stack tensor that layer
     ``below`` puts out: Conv / Pool / Mean / DropOut layers pass stack tensors on (a MeanLayer closes the stack with an
-    fp32 (N, C) output), a HiddenLayer consumes one.  A fused PoolLayer (pool_stands_alone) exists only inside the block
+    fp32 (N, C) output), a HiddenLayer consumes one -- and so does, with ``stack_head`` (the net's STACK_HEAD 'any'), an
+    output head (STACK_HEADS).  A fused PoolLayer (pool_stands_alone) exists only inside the block
     of the ConvLayer directly below it, 2x2 on even maps; a stand-alone one follows any layer that puts out a stack tensor
     (its geometry is the constructor's to refuse: tn_c8_pool_supported)."""
     below_kind = type(below).__name__
@@ -36,8 +43,11 @@ def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False
     if kind in ("ElasticLayer", "ColorLayer"):
         raise AssertionError("DTYPE {}: only Conv / Pool / Mean / DropOut layers take the conv stack's 16-bit-resident "
                              "tensors (got {})".format(dtype, kind))
-    if kind in ("AuxConcatLayer", "SoftmaxLayer", "SoftAuxLayer", "HingeLayer", "ExpLossLayer"):
-        raise AssertionError("DTYPE {}: a HiddenLayer must follow the conv stack (got {})".format(dtype, kind))
+    if stack_head and kind in STACK_HEADS:
+        return
+    if kind == "AuxConcatLayer" or kind in STACK_HEADS:
+        raise AssertionError("DTYPE {}: a HiddenLayer must follow the conv stack (got {}){}".format(
+            dtype, kind, "; " + HEAD_HINT if kind in STACK_HEADS else ""))
     if kind == "PoolLayer":
         assert below_kind != "DropOutLayer", \
             "DTYPE {}: a DropOutLayer between a ConvLayer and its PoolLayer breaks the fused conv + pool block " \

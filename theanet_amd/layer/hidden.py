@@ -37,6 +37,7 @@ class HiddenLayer(Layer):
         # 16-bit stack: the layer above the conv stack consumes the c8 tensor as it is stored (tn_c8_fc_* / tn_c8_fcg_*:
         # 16-bit operands through the NCHW row map, fp32 output); further dense layers are fp32 like the reference
         self.c8 = inpt.c8 if is_c8(inpt) else None
+        self.c8_head = False
         if self.c8 is not None:
             c, h, wd = self.c8
             assert c * h * wd == n_in, (self.c8, n_in)
@@ -49,6 +50,9 @@ class HiddenLayer(Layer):
                 "DTYPE {}: a dense layer of {} samples on {} maps of {}x{} with {} outputs is beyond what the 16-bit dense "
                 "products index (tn_c8_fcg_supported: fewer than 2^31 input, output and weight elements)".format(
                     inpt.elem, inpt.shape[0], c, h, wd, n_out))
+            # an output head (OutputLayer.is_head) of at most 16 outputs: the affine map on the head kernels (head_c8.hip;
+            # TN_C8_HEAD 0: never).  A plain HiddenLayer never takes them; the gradients are the family's above either way
+            self.c8_head = bool(getattr(self, "is_head", False) and lib.tn_c8_head_supported(*shape))
             # a padded stack tensor (maps stored at a pitch > their side): the products read a dense copy, cropped in
             # front of them; the input gradient is embedded back into the padded layout
             self.detour = DenseDetour(inpt)
@@ -112,6 +116,22 @@ class HiddenLayer(Layer):
         if self.test_scale != 1.0:
             self.ctx.call("tn_scale_mask", self.output.ptr, None, float(self.test_scale),
                           self.output.ptr, self.output.size, None, _lib.TN_ACT_LINEAR, 0.0)
+
+    def affine(self, act_kind, act_prm):
+        """output = act(x . W + b) for an output head built on this layer (its row kernel follows): tn_fc_fwd on an fp32
+        input; on a stack tensor the layer's 16-bit product -- the head kernel (``c8_head``) or the dense family's forward
+        -- in front of which a padded tensor is cropped."""
+        if self.c8 is None:
+            self.ctx.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr,
+                          self.batch_sz, self.n_in, self.n_out, act_kind, act_prm, None)
+            return
+        self.detour.crop()
+        if self.c8_head:
+            self.ctx.call("tn_c8_head_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, *self._fc[1],
+                          act_kind, act_prm)
+        else:
+            self.ctx.call(self.c8_fc + "_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr, *self._fc[1],
+                          act_kind, act_prm, None)
 
     def backward(self, gout, need_gin, below):
         """gout = d cost / d z (activation gradient and dropout mask already applied)."""

@@ -5,7 +5,7 @@ argmax (first maximum); cost('nll') = -mean(logprob[n, y_n]) (:50-51); error sta
 fused HIP kernel produces logprob, the per-row loss, argmax, P(label) and d cost / d logits (and, in
 training, the layer's whole backward).  The other losses of SoftmaxLayer ('nllsq', 'nllNN', 'hinge',
 'exp'; :12-64) and the other heads (ExpLossLayer :105-126, HingeLayer :129-147, CenteredOutLayer
-:153-224) run the affine map (tn_fc_fwd, with the head's activation) followed by one row kernel
+:153-224) run the affine map (HiddenLayer.affine, with the head's activation) followed by one row kernel
 (tn_head_rows: log-probabilities, predictions, second error statistic, per-row loss and d cost / d z).
 """
 import numpy as np
@@ -44,6 +44,8 @@ def loss_code(loss):
 
 
 class OutputLayer(object):
+    is_head = True          # (HiddenLayer: on a stack tensor, a head of at most 16 outputs takes the head kernels)
+
     def cost(self, y):
         """Validates the loss name like outlayers.py:12-36; the value itself is
         produced on the device by ``forward``."""
@@ -137,12 +139,26 @@ class SoftmaxLayer(HiddenLayer, OutputLayer):
         self._bwd_done = False
         if self.loss not in (None, "nll"):
             # the other losses on the softmax head (:38-64): affine map, then the generic row kernel
-            self.ctx.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.logits.ptr,
-                          self.batch_sz, self.n_in, self.n_out, _lib.TN_ACT_LINEAR, 0.0, None)
+            self.affine(_lib.TN_ACT_LINEAR, 0.0)
             self._head_rows(HEAD_SOFTMAX, getattr(self, "_loss", None) or loss_code(self.loss), self.logits, train,
                             y, y_row0, d_row0)
             return
-        if have_y and train and below is not None and cost_scale is None and self.has_updates():
+        in_launch_cost = have_y and train and cost_scale is not None and self.d_cost is not None
+        if self.c8 is not None and not in_launch_cost:
+            # on the 16-bit stack (STACK_HEAD 'any'): no fused training op -- ``below`` is ignored, the backward is
+            # HiddenLayer.backward's stack route on dlogits.  At most 16 classes: ONE op; else the dense family + the rows
+            outs = (y.ptr if have_y else None, int(y_row0), d_row0.ptr if d_row0 is not None else None, self.logprob.ptr,
+                    self.rowloss.ptr if have_y else None, self.y_preds.ptr, self.rowp.ptr if have_y else None,
+                    self.dlogits.ptr if (have_y and train) else None)
+            if self.c8_head:
+                self.detour.crop()
+                self.ctx.call("tn_c8_head_softmax_nll", self.inpt.ptr, self.w.ptr, self.b.ptr, self.logits.ptr,
+                              *self._fc[1], *outs, float(self.inv_batch))
+            else:
+                self.affine(_lib.TN_ACT_LINEAR, 0.0)
+                self.ctx.call("tn_softmax_nll", self.logits.ptr, *outs, self.batch_sz, self.n_out, float(self.inv_batch))
+            return
+        if self.c8 is None and have_y and train and below is not None and cost_scale is None and self.has_updates():
             if self.wgrad_ws is None:
                 nbytes = self.ctx.lib.tn_fc_wgrad_ws_bytes(self.batch_sz, self.n_in, self.n_out)
                 self.wgrad_ws = self.ctx.empty((nbytes + 3) // 4)
@@ -158,7 +174,7 @@ class SoftmaxLayer(HiddenLayer, OutputLayer):
                           b_mask.ptr if b_mask is not None else None)
             self._bwd_done = True
             return
-        if not (have_y and train and cost_scale is not None and self.d_cost is not None):
+        if not in_launch_cost:
             # affine map + softmax / NLL rows as ONE op (one launch for <= 16 classes)
             self.ctx.call("tn_fc_softmax_nll", self.inpt.ptr, self.w.ptr, self.b.ptr, self.logits.ptr,
                           self.batch_sz, self.n_in, self.n_out, y.ptr if have_y else None, int(y_row0),
@@ -169,8 +185,7 @@ class SoftmaxLayer(HiddenLayer, OutputLayer):
             return
         # explicit in-launch cost reduction (kept for callers that ask for it; the training step
         # lets the cost ride in the update launch instead)
-        self.ctx.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.logits.ptr,
-                      self.batch_sz, self.n_in, self.n_out, _lib.TN_ACT_LINEAR, 0.0, None)
+        self.affine(_lib.TN_ACT_LINEAR, 0.0)
         if self.cost_ws is None:
             n = self.ctx.lib.tn_softmax_cost_ws_bytes(self.batch_sz)
             self.cost_ws = self.ctx.zeros(((n + 3) // 4,))
@@ -202,8 +217,7 @@ class _LinearHead(HiddenLayer, OutputLayer):
         return None, _lib.TN_ACT_LINEAR, 0.0, None
 
     def forward(self, train=True, y=None, y_row0=0, d_row0=None, cost_scale=None, below=None):
-        self.ctx.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr,
-                      self.batch_sz, self.n_in, self.n_out, _lib.TN_ACT_LINEAR, 0.0, None)
+        self.affine(_lib.TN_ACT_LINEAR, 0.0)
         self._head_rows(self.HEAD, self._loss, self.output, train, y, y_row0, d_row0, feat=self._feat)
 
 
@@ -288,8 +302,7 @@ class CenteredOutLayer(HiddenLayer, OutputLayer):
         return None, _lib.TN_ACT_LINEAR, 0.0, None
 
     def forward(self, train=True, y=None, y_row0=0, d_row0=None, cost_scale=None, below=None):
-        self.ctx.call("tn_fc_fwd", self.inpt.ptr, self.w.ptr, self.b.ptr, self.output.ptr,
-                      self.batch_sz, self.n_in, self.n_out, self.act.kind, self.act.prm, None)
+        self.affine(self.act.kind, self.act.prm)
         dcent = None
         if self.learn_centers and train and y is not None and self.grads is not None:
             dcent = self.grads[2]

@@ -169,6 +169,11 @@ class NeuralNet():
         # tiled shapes keep their kernels and their bits.  No effect under DTYPE 'float32' (the fp32 kernels take every shape).
         self.conv_shapes = training_params.get('CONV_SHAPES', 'tiled')
         assert self.conv_shapes in ('tiled', 'any'), "CONV_SHAPES must be 'tiled' or 'any', not {!r}".format(self.conv_shapes)
+        # STACK_HEAD: 'dense' (default) -- under a 16-bit DTYPE a HiddenLayer must follow the conv stack -- or 'any': an output
+        # head (Softmax, ExpLoss, Hinge, CenteredOut, SoftAux layer) may sit on a stack tensor; it reads the 16-bit tensor as a
+        # HiddenLayer does, a head of at most 16 outputs on kernels of its own (head_c8.hip).  No effect under DTYPE 'float32'.
+        self.stack_head = training_params.get('STACK_HEAD', 'dense')
+        assert self.stack_head in ('dense', 'any'), "STACK_HEAD must be 'dense' or 'any', not {!r}".format(self.stack_head)
         # WT_AVG: d, 0 < d < 1 -- an exponential moving average of the weights (Polyak averaging) that test functions and
         # checkpoints use: a_t = a_{t-1} + c (p_t - a_{t-1}), c = fl(1 - d), p_t = the weights after step t's update and
         # max-norm projection, a_0 = the weights the net starts from (include/theanet_hip.h, tn_avg_net).  Absent, None
@@ -278,7 +283,7 @@ class NeuralNet():
         if is_c8(tr_inpt):
             # 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to layer as they are
             check_follows(self.dtype, prev_tr_layer, layer_type, layer_args.get("pool_sz"), self.fuse_conv_pool,
-                          self.conv_shapes == 'any')
+                          self.conv_shapes == 'any', stack_head=self.stack_head == 'any')
 
         if curr_layer_type in (ElasticLayer, ColorLayer, ConvLayer, PoolLayer, MeanLayer):
             use_tr_layer, k = prev_tr_layer, self.num_layers - 1
@@ -343,8 +348,9 @@ class NeuralNet():
             if wts:
                 centers = wts[2] if len(wts) > 2 else None
                 wts = wts[:2]
-            te_inpt = te_inpt.flatten(2)
-            curr_layer = CenteredOutLayer(tr_inpt.flatten(2),
+            if not is_c8(tr_inpt):          # (STACK_HEAD 'any': a head takes the stack tensor as it is, like a HiddenLayer)
+                tr_inpt, te_inpt = tr_inpt.flatten(2), te_inpt.flatten(2)
+            curr_layer = CenteredOutLayer(tr_inpt,
                                           wts, centers,
                                           self.rand_gen,
                                           prev_tr_layer.n_out,
@@ -356,8 +362,9 @@ class NeuralNet():
             curr_layer = HiddenLayer(tr_inpt, wts, self.rand_gen, prev_tr_layer.n_out, **layer_args)
 
         elif curr_layer_type in (AuxConcatLayer, HiddenLayer, SoftmaxLayer, SoftAuxLayer, HingeLayer, ExpLossLayer):
-            te_inpt = te_inpt.flatten(2)
-            curr_layer = curr_layer_type(tr_inpt.flatten(2),
+            if not is_c8(tr_inpt):          # (STACK_HEAD 'any': a head takes the stack tensor as it is, like a HiddenLayer)
+                tr_inpt, te_inpt = tr_inpt.flatten(2), te_inpt.flatten(2)
+            curr_layer = curr_layer_type(tr_inpt,
                                          wts,
                                          self.rand_gen,
                                          prev_tr_layer.n_out,
@@ -478,7 +485,9 @@ class NeuralNet():
                 import zlib
                 sig = "|".join("%s=%s" % kv for kv in self.ctx.knobs().items())
                 sig += "|TN_POOL_MASK=%d|TN_MN_FUSED=%s" % (pool_mask_enabled(), os.environ.get("TN_MN_FUSED", ""))
-                sig += "|CONV_SHAPES=%s" % self.conv_shapes
+                # (the head's route -- TN_C8_HEAD, seen through tn_c8_head_supported -- fixes the order of its sums)
+                sig += "|CONV_SHAPES=%s|STACK_HEAD=%s|C8_HEAD=%d" % (self.conv_shapes, self.stack_head,
+                                                                    any(getattr(l, "c8_head", False) for l in self.tr_layers))
                 sig += "|cus=%s" % self.ctx.info()[1]
                 comm.agree(float(zlib.crc32(sig.encode())), "the kernel tunables / CU count (%s)" % sig)
         self.dp.prepare(slots, host)
