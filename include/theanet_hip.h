@@ -365,6 +365,30 @@ int tn_c8_pool_fwd(tn_ctx* ctx, const void* x, void* y, int N, int C, int S, int
 int tn_c8_pool_bwd(tn_ctx* ctx, const void* x, const void* y, const void* gout, void* gin, int N, int C, int S, int P,
                    int p, int So, int Po);
 int tn_c8_pool_plan(int op, int N, int C, int S, int P, int p, int So, int Po, int* out, int nout);
+/* A stand-alone PoolLayer with a stride of its own on a c8 tensor (Theano's pool_2d(inpt, (p, p), ignore_border, st=(st, st))
+ * and its gradient MaxPoolGrad: overlapping, st < p, or gapped, st > p, max-pooling; theanet_amd/csrc/pools_c8.hip).
+ * Tensors as in tn_c8_pool_*.  Window (i, j) covers rows i * st .. min(S, i * st + p) - 1 and the same columns: clipped at
+ * the map edge, never padded.  So = (S - p) / st + 1 (ignore_border; needs S >= p), else (S - 1) / st + 1 for st >= p and
+ * max(0, (S - 1 - p + st) / st) + 1 for st < p (Theano's Pool.out_shape); st = p gives tn_c8_pool_*'s sides and bits.
+ * fwd: tn_c8_pool_fwd's on those windows -- the maximum of the STORED values through the ordered integer key, row-major
+ *   scan, replaced on strict >, a stored pattern, never rounded; pad cells of y and channels past C written as 0, every cell
+ *   of y written.  Also the test version.  Inputs are NaN-free.
+ * bwd: gin[pos] = the sum of gout[i, j] over the windows that cover pos and whose maximum equals x[pos] by value (-0 == +0
+ *   ties; every tied element gets the whole gradient).  The windows covering row h are i = max(0, ceil((h - p + 1) / st)) ..
+ *   min(So - 1, h / st), columns likewise; terms are added in fp32 in row-major window order starting from the first term
+ *   (a single term is copied bit for bit), and the sum is rounded once, to nearest even, to the context's 16-bit type.  No
+ *   term (uncovered or untied positions, pad cells, channels past C): +0; every cell of gin is written.  A gather: a lane
+ *   per input cell, no atomics, deterministic.  The activation derivative of the block below is NOT applied (as tn_c8_pool_bwd).
+ * supported: 1 for 2 <= p <= 64, 1 <= st <= 64, So one of the two sides above and >= 1, and the pitch and cell-count rules of
+ *   tn_c8_pool_supported.  Anything else, or a NULL tensor: TN_E_ARG naming the arguments, nothing launched.
+ * plan (no device): op 0 (fwd) / 1 (bwd) -> PW, ST (the compile-time window and stride: (3, 2), (2, 1), or (0, 0) = the
+ *   run-time loops), SH (the pitch the lanes are laid over -- fwd: Po, bwd: P -- is a power of two), blocks; returns how
+ *   many values the plan has, TN_E_ARG for a refused geometry (and always on the CPU backend).                        */
+int tn_c8_pool_st_supported(int N, int C, int S, int P, int p, int st, int So, int Po);
+int tn_c8_pool_st_fwd(tn_ctx* ctx, const void* x, void* y, int N, int C, int S, int P, int p, int st, int So, int Po);
+int tn_c8_pool_st_bwd(tn_ctx* ctx, const void* x, const void* y, const void* gout, void* gin, int N, int C, int S, int P,
+                      int p, int st, int So, int Po);
+int tn_c8_pool_st_plan(int op, int N, int C, int S, int P, int p, int st, int So, int Po, int* out, int nout);
 /* 1x1 stride-1 ConvLayers on c8 tensors (replace conv2d(inpt, W) + b, the activation and -- fused -- the 2x2 max-pool of
  * convpool.py:54-72, 106-107 with filter_sz 1, and their gradients, for a 1x1 layer on the 16-bit stack;
  * theanet_amd/csrc/conv1_c8.hip).  Tensors: N x C (x, dx) / N x K (y, dz) maps of S pixels a side stored at pitch P (P == S,
@@ -563,6 +587,16 @@ int tn_pool_fwd(tn_ctx* ctx, const float* x, float* y, int NC, int H, int Wd, in
  * (x IS that layer's output).  prev_act = TN_ACT_LINEAR disables it.                    */
 int tn_pool_bwd(tn_ctx* ctx, const float* x, const float* y, const float* dy, float* dx,
                 int NC, int H, int Wd, int p, int Ho, int Wo, int prev_act, float prev_act_param);
+/* The same with a stride st of its own (pool_2d's st=): window (i, j) covers rows i*st .. min(H, i*st + p) - 1, columns
+ * likewise, clipped and never padded; Ho, Wo by Theano's Pool.out_shape (tn_c8_pool_st_supported), the ops validate
+ * (Ho - 1) * st < H and (Wo - 1) * st < Wd.  fwd: fmaxf over the window.  bwd: dx = the sum of dy over the covering
+ * windows whose maximum the element equals, in fp32, row-major window order, starting from the first term (+0 where there
+ * is none), then the producing layer's activation gradient as in tn_pool_bwd.  A gather, no atomics.  st = p: the bits of
+ * tn_pool_fwd / tn_pool_bwd.  Bad geometry or a NULL tensor: TN_E_ARG, nothing launched.                              */
+int tn_pool_st_fwd(tn_ctx* ctx, const float* x, float* y, int NC, int H, int Wd, int p, int st,
+                   int Ho, int Wo);
+int tn_pool_st_bwd(tn_ctx* ctx, const float* x, const float* y, const float* dy, float* dx,
+                   int NC, int H, int Wd, int p, int st, int Ho, int Wo, int prev_act, float prev_act_param);
 int tn_mean_fwd(tn_ctx* ctx, const float* x, float* y, int NC, int HW);
 int tn_mean_bwd(tn_ctx* ctx, const float* dy, float* dx, int NC, int HW,
                 const float* prev_a, int prev_act, float prev_act_param);

@@ -120,6 +120,10 @@ SIGNATURES = {
     "tn_c8_pool_fwd": (c_int, [CTX, P, P] + [c_int] * 7),
     "tn_c8_pool_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 7),
     "tn_c8_pool_plan": (c_int, [c_int] * 8 + [POINTER(c_int), c_int]),
+    "tn_c8_pool_st_supported": (c_int, [c_int] * 8),
+    "tn_c8_pool_st_fwd": (c_int, [CTX, P, P] + [c_int] * 8),
+    "tn_c8_pool_st_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 8),
+    "tn_c8_pool_st_plan": (c_int, [c_int] * 9 + [POINTER(c_int), c_int]),
     "tn_c8_conv1_supported": (c_int, [c_int] * 5),
     "tn_c8_conv1_fwd": (c_int, [CTX, P, P, P, P, P] + [c_int] * 6 + [c_float, c_int]),
     "tn_c8_conv1_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 5 + [P, c_int, c_float, c_int, P]),
@@ -136,6 +140,8 @@ SIGNATURES = {
     "tn_c8_conv_plan_pitch": (c_int, [c_int] * 8 + [c_float, POINTER(c_int), c_int]),
     "tn_pool_fwd": (c_int, [CTX, P, P] + [c_int] * 6),
     "tn_pool_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 6 + [c_int, c_float]),
+    "tn_pool_st_fwd": (c_int, [CTX, P, P] + [c_int] * 7),
+    "tn_pool_st_bwd": (c_int, [CTX, P, P, P, P] + [c_int] * 7 + [c_int, c_float]),
     "tn_mean_fwd": (c_int, [CTX, P, P, c_int, c_int]),
     "tn_mean_bwd": (c_int, [CTX, P, P, c_int, c_int, P, c_int, c_float]),
     "tn_fc_fwd": (c_int, [CTX, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),

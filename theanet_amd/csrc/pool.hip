@@ -45,6 +45,58 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
     dx[t] = r;
 }
 
+// A stride of its own (Theano's pool_2d(..., st=)): window (i, j) covers rows i*st .. min(H, i*st + p) - 1 and columns
+// likewise, clipped and never padded.  The same two forms: a thread per output, a thread per input.
+__global__ __launch_bounds__(256) void pool_st_fwd_kernel(const float* __restrict__ x,
+                                                         float* __restrict__ y, long long total,
+                                                         int H, int Wd, int p, int st, int Ho, int Wo) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int HoWo = Ho * Wo;
+    const long long nc = t / HoWo;
+    const int q = (int)(t - nc * HoWo);
+    const int i = q / Wo, j = q - i * Wo;
+    const float* xc = x + nc * (long long)H * Wd;
+    const int y1 = min(H, i * st + p), x1 = min(Wd, j * st + p);
+    float m = -INFINITY;
+    for (int yy = i * st; yy < y1; ++yy)
+        for (int xx = j * st; xx < x1; ++xx) m = fmaxf(m, xc[yy * Wd + xx]);
+    y[t] = m;
+}
+
+// dx = the sum of dy over the windows that cover the element and whose maximum it equals (a gather: no atomics), added in
+// row-major window order from the first term on (the sum starts at -0: -0 + g == g for every g), +0 where there is none;
+// then * act'(x) of the producing layer
+__global__ __launch_bounds__(256) void pool_st_bwd_kernel(const float* __restrict__ x,
+                                                         const float* __restrict__ y,
+                                                         const float* __restrict__ dy,
+                                                         float* __restrict__ dx, long long total, int H,
+                                                         int Wd, int p, int st, int Ho, int Wo, int prev_act,
+                                                         float prev_prm) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int HW = H * Wd;
+    const long long nc = t / HW;
+    const int q = (int)(t - nc * HW);
+    const int yy = q / Wd, xx = q - yy * Wd;
+    const int i0 = yy >= p ? (yy - p + st) / st : 0, i1 = min(Ho - 1, yy / st);
+    const int j0 = xx >= p ? (xx - p + st) / st : 0, j1 = min(Wo - 1, xx / st);
+    const float xv = x[t];
+    const float* yc = y + nc * (long long)(Ho * Wo);
+    const float* dyc = dy + nc * (long long)(Ho * Wo);
+    float s = -0.f;
+    bool any = false;
+    for (int i = i0; i <= i1; ++i)
+        for (int j = j0; j <= j1; ++j)
+            if (xv == yc[i * Wo + j]) {
+                s += dyc[i * Wo + j];
+                any = true;
+            }
+    float r = any ? s : 0.f;
+    if (prev_act != TN_ACT_LINEAR) r *= tn_act_grad_from_out(xv, prev_act, prev_prm);
+    dx[t] = r;
+}
+
 __global__ __launch_bounds__(64) void mean_fwd_kernel(const float* __restrict__ x,
                                                      float* __restrict__ y, int HW) {
     const float* xc = x + (size_t)blockIdx.x * HW;
@@ -121,6 +173,28 @@ int tn_pool_bwd(tn_ctx* ctx, const float* x, const float* y, const float* dy, fl
     const long long total = (long long)NC * H * Wd;
     pool_bwd_kernel<<<cdiv(total, 256), 256, 0, ctx->stream>>>(x, y, dy, dx, total, H, Wd, p, Ho, Wo,
                                                               prev_act, prev_act_param);
+    TN_LAUNCH_CHECK();
+    return TN_OK;
+}
+
+int tn_pool_st_fwd(tn_ctx* ctx, const float* x, float* y, int NC, int H, int Wd, int p, int st, int Ho, int Wo) {
+    TN_REQUIRE(x && y && NC > 0 && p > 0 && st > 0 && Ho > 0 && Wo > 0 && (long long)(Ho - 1) * st < H &&
+                   (long long)(Wo - 1) * st < Wd,
+               "tn_pool_st_fwd: bad arguments (NC %d, H %d W %d, window %d stride %d, Ho %d Wo %d)", NC, H, Wd, p, st, Ho, Wo);
+    const long long total = (long long)NC * Ho * Wo;
+    pool_st_fwd_kernel<<<cdiv(total, 256), 256, 0, ctx->stream>>>(x, y, total, H, Wd, p, st, Ho, Wo);
+    TN_LAUNCH_CHECK();
+    return TN_OK;
+}
+
+int tn_pool_st_bwd(tn_ctx* ctx, const float* x, const float* y, const float* dy, float* dx, int NC, int H, int Wd, int p,
+                   int st, int Ho, int Wo, int prev_act, float prev_act_param) {
+    TN_REQUIRE(x && y && dy && dx && NC > 0 && p > 0 && st > 0 && Ho > 0 && Wo > 0 && (long long)(Ho - 1) * st < H &&
+                   (long long)(Wo - 1) * st < Wd,
+               "tn_pool_st_bwd: bad arguments (NC %d, H %d W %d, window %d stride %d, Ho %d Wo %d)", NC, H, Wd, p, st, Ho, Wo);
+    const long long total = (long long)NC * H * Wd;
+    pool_st_bwd_kernel<<<cdiv(total, 256), 256, 0, ctx->stream>>>(x, y, dy, dx, total, H, Wd, p, st, Ho, Wo, prev_act,
+                                                                 prev_act_param);
     TN_LAUNCH_CHECK();
     return TN_OK;
 }

@@ -244,6 +244,12 @@ int tn_c8_pool_bwd(tn_ctx* ctx, const void*, const void*, const void*, void*, in
     NOT_HERE("tn_c8_pool_bwd");
 }
 int tn_c8_pool_plan(int, int, int, int, int, int, int, int, int*, int) { return TN_E_ARG; }
+int tn_c8_pool_st_supported(int, int, int, int, int, int, int, int) { return 0; }
+int tn_c8_pool_st_fwd(tn_ctx* ctx, const void*, void*, int, int, int, int, int, int, int, int) { NOT_HERE("tn_c8_pool_st_fwd"); }
+int tn_c8_pool_st_bwd(tn_ctx* ctx, const void*, const void*, const void*, void*, int, int, int, int, int, int, int, int) {
+    NOT_HERE("tn_c8_pool_st_bwd");
+}
+int tn_c8_pool_st_plan(int, int, int, int, int, int, int, int, int, int*, int) { return TN_E_ARG; }
 int tn_c8_conv1_supported(int, int, int, int, int) { return 0; }
 int tn_c8_conv1_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, uint8_t*, int, int, int, int, int, int,
                     float, int) { NOT_HERE("tn_c8_conv1_fwd"); }
@@ -497,6 +503,54 @@ int tn_pool_bwd(tn_ctx*, const float* x, const float* y, const float* dy, float*
                     g = dy[((size_t)m * Ho + i) * Wo + j];
                 if (prev_act != TN_ACT_LINEAR) g *= act_grad_from_out(xi[(size_t)r * Wd + c], prev_act, prev_act_param);
                 dxi[(size_t)r * Wd + c] = g;
+            }
+    }
+    return TN_OK;
+}
+// a stride of its own: the device's windows, scan order and summation order (pool.hip)
+int tn_pool_st_fwd(tn_ctx* ctx, const float* x, float* y, int NC, int H, int Wd, int p, int st, int Ho, int Wo) {
+    REQUIRE(x && y && NC > 0 && p > 0 && st > 0 && Ho > 0 && Wo > 0 && (long long)(Ho - 1) * st < H && (long long)(Wo - 1) * st < Wd,
+            "tn_pool_st_fwd: bad arguments (NC %d, H %d W %d, window %d stride %d, Ho %d Wo %d)", NC, H, Wd, p, st, Ho, Wo);
+#pragma omp parallel for
+    for (int m = 0; m < NC; ++m) {
+        const float* xi = x + (size_t)m * H * Wd;
+        float* yo = y + (size_t)m * Ho * Wo;
+        for (int i = 0; i < Ho; ++i)
+            for (int j = 0; j < Wo; ++j) {
+                float best = -INFINITY;
+                for (int r = i * st; r < std::min(H, i * st + p); ++r)
+                    for (int c = j * st; c < std::min(Wd, j * st + p); ++c) best = std::fmax(best, xi[(size_t)r * Wd + c]);
+                yo[(size_t)i * Wo + j] = best;
+            }
+    }
+    return TN_OK;
+}
+int tn_pool_st_bwd(tn_ctx* ctx, const float* x, const float* y, const float* dy, float* dx, int NC, int H, int Wd, int p,
+                   int st, int Ho, int Wo, int prev_act, float prev_act_param) {
+    REQUIRE(x && y && dy && dx && NC > 0 && p > 0 && st > 0 && Ho > 0 && Wo > 0 && (long long)(Ho - 1) * st < H &&
+                (long long)(Wo - 1) * st < Wd,
+            "tn_pool_st_bwd: bad arguments (NC %d, H %d W %d, window %d stride %d, Ho %d Wo %d)", NC, H, Wd, p, st, Ho, Wo);
+#pragma omp parallel for
+    for (int m = 0; m < NC; ++m) {
+        const float* xi = x + (size_t)m * H * Wd;
+        const float* yi = y + (size_t)m * Ho * Wo;
+        const float* dyi = dy + (size_t)m * Ho * Wo;
+        float* dxi = dx + (size_t)m * H * Wd;
+        for (int r = 0; r < H; ++r)
+            for (int c = 0; c < Wd; ++c) {
+                const int i0 = r >= p ? (r - p + st) / st : 0, i1 = std::min(Ho - 1, r / st);
+                const int j0 = c >= p ? (c - p + st) / st : 0, j1 = std::min(Wo - 1, c / st);
+                const float xv = xi[(size_t)r * Wd + c];
+                float s = 0.f;
+                bool any = false;
+                for (int i = i0; i <= i1; ++i)
+                    for (int j = j0; j <= j1; ++j)
+                        if (xv == yi[(size_t)i * Wo + j]) {              // every tie of every covering window: MaxPoolGrad
+                            s = any ? s + dyi[(size_t)i * Wo + j] : dyi[(size_t)i * Wo + j];
+                            any = true;
+                        }
+                if (prev_act != TN_ACT_LINEAR) s *= act_grad_from_out(xv, prev_act, prev_act_param);
+                dxi[(size_t)r * Wd + c] = s;
             }
     }
     return TN_OK;

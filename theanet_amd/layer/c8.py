@@ -8,12 +8,15 @@ import numpy as np
 from ..device import C8Array, c8_pitch, c8_pool_pitch
 
 
-def pool_stands_alone(pool_sz, fused=True, below=None, any_shapes=False):
+def pool_stands_alone(pool_sz, fused=True, below=None, any_shapes=False, stride=None):
     """Which of its two forms a PoolLayer on the stack takes: a 2x2 one is the second half of the fused conv + pool block
     of the ConvLayer below it while the net fuses (``fused``: NeuralNet.fuse_conv_pool); every other one -- and every one
     of a net that does not fuse -- stands alone (tn_c8_pool_fwd / tn_c8_pool_bwd).  ``any_shapes`` (the net's
     CONV_SHAPES 'any') with the layer ``below``: a 2x2 one stands alone too where the block cannot take it -- above a
-    ConvLayer of the general family (ConvFamily.pools false: never fused) and on an odd map."""
+    ConvLayer of the general family (ConvFamily.pools false: never fused) and on an odd map.  A pool whose ``stride``
+    differs from its window (None: the window) always stands alone (tn_c8_pool_st_fwd / tn_c8_pool_st_bwd)."""
+    if stride is not None and stride != pool_sz:
+        return True
     if not (fused and pool_sz == 2):
         return True
     if any_shapes and type(below).__name__ == "ConvLayer":
@@ -28,15 +31,16 @@ STACK_HEADS = ("SoftmaxLayer", "SoftAuxLayer", "HingeLayer", "ExpLossLayer", "Ce
 HEAD_HINT = "training param STACK_HEAD: 'any' lets an output head close the stack"
 
 
-def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False, stack_head=False):
+def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False, stack_head=False, stride=None):
     """The stack's grammar, asserted before a layer of class ``kind`` (its name) is built on the stack tensor that layer
     ``below`` puts out: Conv / Pool / Mean / DropOut layers pass stack tensors on (a MeanLayer closes the stack with an
     fp32 (N, C) output), a HiddenLayer consumes one -- and so does, with ``stack_head`` (the net's STACK_HEAD 'any'), an
     output head (STACK_HEADS).  A fused PoolLayer (pool_stands_alone) exists only inside the block
     of the ConvLayer directly below it, 2x2 on even maps; a stand-alone one follows any layer that puts out a stack tensor
-    (its geometry is the constructor's to refuse: tn_c8_pool_supported)."""
+    (its geometry is the constructor's to refuse: tn_c8_pool_supported / tn_c8_pool_st_supported).  ``stride``: the
+    PoolLayer's, None for its window."""
     below_kind = type(below).__name__
-    if kind == "PoolLayer" and pool_stands_alone(pool_sz, fused, below, any_shapes):
+    if kind == "PoolLayer" and pool_stands_alone(pool_sz, fused, below, any_shapes, stride=stride):
         assert below_kind in ("ConvLayer", "PoolLayer", "DropOutLayer"), \
             "DTYPE {}: a stand-alone PoolLayer follows a Conv, Pool or DropOut layer (got {})".format(dtype, below_kind)
         return

@@ -2,6 +2,7 @@
 Same constructor arguments, shape rules and ``representation`` strings; the
 compute is enqueued on the HIP backend (include/theanet_hip.h)."""
 import math
+import numbers
 import os
 from collections import namedtuple
 
@@ -135,7 +136,10 @@ class ConvLayer(Layer):
 
     def can_fuse_with(self, pool):
         """conv -> act -> 2x2 max-pool as one fused kernel pair -- the conv activation never reaches HBM.  Returns the
-        family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused."""
+        family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused.
+        A pool whose stride differs from its window is never fused: the blocks pool with stride = window."""
+        if getattr(pool, "strided", False):
+            return None
         if self.f16:
             # what the fused block takes; any other PoolLayer of the stack stands alone (c8.check_follows)
             return True if pool.pool_sz == 2 and self.out_sz % 2 == 0 and not pool.c8_alone and self.c8_fam.pools else None
@@ -317,16 +321,36 @@ class ConvLayer(Layer):
         return self.gin
 
 
+def pool_out_sz(in_sz, pool_sz, stride=None, ignore_border=False):
+    """The output side of a PoolLayer on maps of ``in_sz`` pixels (Theano's Pool.out_shape): windows of ``pool_sz`` at
+    ``stride`` (None: the window), the last one clipped at the map edge or -- ignore_border -- dropped.  With stride =
+    window: in_sz // pool_sz and ceil(in_sz / pool_sz)."""
+    st = pool_sz if stride is None else stride
+    if st == pool_sz:
+        return in_sz // pool_sz if ignore_border else math.ceil(in_sz / pool_sz)
+    if ignore_border:
+        return (in_sz - pool_sz) // st + 1
+    if st >= pool_sz:
+        return (in_sz - 1) // st + 1
+    return max(0, (in_sz - 1 - pool_sz + st) // st) + 1
+
+
 class PoolLayer(Layer):
-    def __init__(self, inpt, num_maps, in_sz, pool_sz, ignore_border=False, c8_alone=False):
+    def __init__(self, inpt, num_maps, in_sz, pool_sz, ignore_border=False, c8_alone=False, stride=None):
         """Max-pool, stride = window.  ignore_border=False keeps the partial last
         window: (5,5) with pool 2 -> (3,3); True -> (2,2) (convpool.py:98-112).
         ``c8_alone`` (16-bit stack, the net's to say: c8.pool_stands_alone): not the second half of a fused conv + pool
-        block but a layer of its own (tn_c8_pool_fwd / tn_c8_pool_bwd) -- any window on any map."""
-        if ignore_border:
-            self.out_sz = in_sz // pool_sz
-        else:
-            self.out_sz = math.ceil(in_sz / pool_sz)
+        block but a layer of its own (tn_c8_pool_fwd / tn_c8_pool_bwd) -- any window on any map.
+        ``stride`` (pool_2d's st=; None: the window): an integer >= 1.  A stride that differs from the window -- windows
+        that overlap or leave gaps, clipped at the map edge, never padded -- runs on ops of its own (tn_pool_st_* /
+        tn_c8_pool_st_*), never inside a fused block; a stride equal to the window is the layer without the argument."""
+        assert stride is None or (isinstance(stride, numbers.Integral) and not isinstance(stride, bool) and stride >= 1), \
+            "PoolLayer stride must be an integer >= 1 (None: the window), not {!r}".format(stride)
+        self.stride = pool_sz if stride is None else int(stride)
+        self.strided = self.stride != pool_sz
+        assert not (ignore_border and in_sz < pool_sz and self.strided), (
+            "PoolLayer with ignore_border: a window of {} pixels does not fit a map of {}".format(pool_sz, in_sz))
+        self.out_sz = pool_out_sz(in_sz, pool_sz, self.stride, ignore_border)
 
         self.ctx = inpt.ctx
         self.params = []
@@ -334,13 +358,25 @@ class PoolLayer(Layer):
         self.num_maps = num_maps
         self.in_sz, self.pool_sz = in_sz, pool_sz
         self.ignore_border = ignore_border
-        self.args = (num_maps, in_sz, pool_sz, ignore_border, c8_alone)
+        self.args = (num_maps, in_sz, pool_sz, ignore_border, c8_alone, stride)
         self.n_out = num_maps * self.out_sz ** 2
         self.batch_sz = inpt.shape[0]
         self.f16 = is_c8(inpt)      # 16-bit stack: pooled c8 tensor (of a fused block, or this layer's own)
         self.c8_alone = self.f16 and c8_alone
         self.below = None           # (stand-alone) the layer below, set by the net: act_info() looks through to it
-        if self.c8_alone:
+        assert not (self.f16 and self.strided and not self.c8_alone), \
+            "DTYPE {}: a PoolLayer whose stride differs from its window stands alone (c8.pool_stands_alone)".format(inpt.elem)
+        if self.c8_alone and self.strided:
+            pitch = c8_pool_pitch(self.out_sz)
+            self.c8_geom = (self.batch_sz, num_maps, in_sz, inpt.pitch, pool_sz, self.stride, self.out_sz, pitch)
+            assert self.ctx.lib.tn_c8_pool_st_supported(*self.c8_geom), (
+                "DTYPE {}: a stand-alone PoolLayer takes a window of 2 to 64 pixels at a stride of 1 to 64 that leaves at "
+                "least one output pixel, on tensors of fewer than 2^32 - 256 cells (got {} maps of {} pixels at pitch {}, "
+                "window {} stride {}, {} border: {} pixels at pitch {})".format(
+                    inpt.elem, num_maps, in_sz, inpt.pitch, pool_sz, self.stride, "ignored" if ignore_border else "kept",
+                    self.out_sz, pitch))
+            self.output = C8Array(self.ctx, self.batch_sz, num_maps, self.out_sz, self.out_sz, inpt.elem, pitch=pitch)
+        elif self.c8_alone:
             pitch = c8_pool_pitch(self.out_sz)
             self.c8_geom = (self.batch_sz, num_maps, in_sz, inpt.pitch, pool_sz, self.out_sz, pitch)
             assert self.ctx.lib.tn_c8_pool_supported(*self.c8_geom), (
@@ -363,6 +399,8 @@ class PoolLayer(Layer):
             "".format(num_maps, pool_sz,
                       "Ignore" if ignore_border else "Keep",
                       self.out_sz))
+        if self.strided:
+            self.representation += " Stride:{}".format(self.stride)
 
     def TestVersion(self, inpt):
         return PoolLayer(inpt, *self.args)
@@ -385,7 +423,8 @@ class PoolLayer(Layer):
     def forward(self, train=True):
         conv = self.fused_conv
         if self.c8_alone:
-            return self.ctx.call("tn_c8_pool_fwd", self.inpt.ptr, self.output.ptr, *self.c8_geom)
+            return self.ctx.call("tn_c8_pool_st_fwd" if self.strided else "tn_c8_pool_fwd", self.inpt.ptr, self.output.ptr,
+                                 *self.c8_geom)
         if self.f16:
             if train and self.mask is None:
                 self.mask = self.ctx.empty(self.output.shape, np.uint8)
@@ -406,6 +445,9 @@ class PoolLayer(Layer):
                           self.output.ptr, self.mask.ptr if (train and self.mask is not None) else None,
                           *conv._fused_geom())
             return
+        if self.strided:
+            return self.ctx.call("tn_pool_st_fwd", self.inpt.ptr, self.output.ptr, self.batch_sz * self.num_maps, self.in_sz,
+                                 self.in_sz, self.pool_sz, self.stride, self.out_sz, self.out_sz)
         self.ctx.call("tn_pool_fwd", self.inpt.ptr, self.output.ptr,
                       self.batch_sz * self.num_maps, self.in_sz, self.in_sz, self.pool_sz,
                       self.out_sz, self.out_sz)
@@ -419,13 +461,19 @@ class PoolLayer(Layer):
             # selection only: act' of the block below is already in gout (act_info)
             if self.gin is None:
                 self.gin = C8Array.like(self.inpt)
-            self.ctx.call("tn_c8_pool_bwd", self.inpt.ptr, self.output.ptr, gout.ptr, self.gin.ptr, *self.c8_geom)
+            self.ctx.call("tn_c8_pool_st_bwd" if self.strided else "tn_c8_pool_bwd", self.inpt.ptr, self.output.ptr, gout.ptr,
+                          self.gin.ptr, *self.c8_geom)
             return self.gin
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
         _, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
         # below.output IS self.inpt, so the activation gradient rides along for free
+        if self.strided:
+            self.ctx.call("tn_pool_st_bwd", self.inpt.ptr, self.output.ptr, gout.ptr, self.gin.ptr,
+                          self.batch_sz * self.num_maps, self.in_sz, self.in_sz, self.pool_sz, self.stride,
+                          self.out_sz, self.out_sz, b_act, b_prm)
+            return self.gin
         self.ctx.call("tn_pool_bwd", self.inpt.ptr, self.output.ptr, gout.ptr, self.gin.ptr,
                       self.batch_sz * self.num_maps, self.in_sz, self.in_sz, self.pool_sz,
                       self.out_sz, self.out_sz, b_act, b_prm)

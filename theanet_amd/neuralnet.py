@@ -283,7 +283,7 @@ class NeuralNet():
         if is_c8(tr_inpt):
             # 16-bit-resident tensors of the conv stack (device.C8Array) pass from layer to layer as they are
             check_follows(self.dtype, prev_tr_layer, layer_type, layer_args.get("pool_sz"), self.fuse_conv_pool,
-                          self.conv_shapes == 'any', stack_head=self.stack_head == 'any')
+                          self.conv_shapes == 'any', stack_head=self.stack_head == 'any', stride=layer_args.get("stride"))
 
         if curr_layer_type in (ElasticLayer, ColorLayer, ConvLayer, PoolLayer, MeanLayer):
             use_tr_layer, k = prev_tr_layer, self.num_layers - 1
@@ -326,7 +326,8 @@ class NeuralNet():
                 # 16-bit stack: half of a fused conv + pool block, or a layer of its own that -- like a DropOutLayer --
                 # stands for the block below it (PoolLayer.act_info)
                 layer_args = dict(layer_args, c8_alone=pool_stands_alone(layer_args.get("pool_sz"), self.fuse_conv_pool,
-                                                                         prev_tr_layer, self.conv_shapes == 'any'))
+                                                                         prev_tr_layer, self.conv_shapes == 'any',
+                                                                         stride=layer_args.get("stride")))
             curr_layer = curr_layer_type(tr_inpt,
                                          num_maps=num_prev_maps,
                                          in_sz=prev_out_sz,
