@@ -147,6 +147,22 @@ int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx,
                     int N, int C, int H, int Wd, int K, int f, int stride, int pad_lo,
                     int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
 
+/* Depthwise convolution (ConvLayer(..., depthwise=True); theanet_amd/csrc/dwconv.hip): every map with its own filter,
+ *   z[n,c,i,j] = b[c] + sum_{u,v} xpad[n,c,i*s+u,j*s+v] * W[c,0,f-1-u,f-1-v]
+ * W (C,1,f,f), b (C), f 3 or 5; the arguments are tn_conv2d_*'s without K, NCHW fp32.  fwd fuses bias + activation;
+ * wgrad OVERWRITES dW / db (slab sums finished by the context's fixed-order reduction); dgrad fuses act'(prev_a) (NULL:
+ * none) and is a gather, no atomics.  fp32 under every CONV mode (there is no matrix product to round); refused in a
+ * 16-bit DTYPE mode like tn_conv2d_*.  supported: 1 for f 3 or 5, 1 <= stride <= 16, at most 65535 maps, rows and columns, fewer than
+ * 2^32 elements a tensor and Ho / Wo the number of windows that fit with pad_lo <= f / 2 low and at most as much high
+ * padding; bad geometry or a NULL tensor: TN_E_ARG naming the entry point, nothing launched.                          */
+int tn_dwconv_supported(int N, int C, int H, int Wd, int f, int stride, int pad_lo, int Ho, int Wo);
+int tn_dwconv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int f,
+                  int stride, int pad_lo, int Ho, int Wo, int act, float act_param);
+int tn_dwconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int f,
+                    int stride, int pad_lo, int Ho, int Wo);
+int tn_dwconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int f, int stride,
+                    int pad_lo, int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
+
 /* ---- DTYPE 'float16' / 'bfloat16' (BASELINE configs[4]; the reference is float32-only, weights.py:8 `floatX`: opt-in
  * training params of this build, default off) ----
  * dtype 0: every tensor fp32 (reference arithmetic).  dtype 1: the conv stack of the net lives in HBM as halfs and is
@@ -450,6 +466,27 @@ int tn_c8_convg_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, flo
                       int f, int stride, int pad, int So, int Po);
 int tn_c8_convg_plan(int op, int N, int C, int S, int P, int K, int f, int stride, int pad, int So, int Po, int act,
                      float prm, int* out, int nout);
+/* Depthwise ConvLayers on c8 tensors (ConvLayer(..., depthwise=True): every map convolved with its own f x f filter,
+ * nothing summed across maps; theanet_amd/csrc/dwconv_c8.hip, dwconv.h).  The arguments are tn_c8_convg_*'s without K: x / dx
+ * and y / dz both hold N x C maps; W (C, 1, f, f) fp32 master weights in tn_conv2d_*'s orientation, b (C) fp32; f is 3 or 5.
+ * Arithmetic: the stack's -- x and dz as stored, W rounded to the 16-bit type (nearest even), exact products, fp32
+ * accumulation (no matrix product: an LDS halo tile and a register sliding window over 16-byte cells), bias / activation
+ * on the fp32 sums, one rounding on store; dz / dx carry the gradient scale.
+ * fwd: y = act(dwconv(x, W) + b).  dgrad: dx = R(dwconv^T(dz, W) * act'(prev_a)) (NULL: no derivative), a gather in a
+ *   fixed order, no atomics.  EVERY cell of y / dx is written by the op: pad cells, channels past C in a ragged last
+ *   octet and input pixels no strided window touches as exact +0.
+ * wgrad: dW (C, 1, f, f), db (C) fp32, OVERWRITE, the gradient scale removed in the fp32 epilogue; db is summed from the
+ *   stored dz.  Slab sums in context scratch finished by the context's reduction: a slab count that depends on the
+ *   geometry alone, one order, the same bits every run.
+ * supported: 1 for f 3 or 5, 1 <= stride <= 16 and consistent geometry (tn_c8_convg_supported's rule) with fewer than 2^32
+ *   cells per tensor.  Anything else, and any NULL tensor: TN_E_ARG naming the entry point, nothing launched.          */
+int tn_c8_dwconv_supported(int N, int C, int S, int P, int f, int stride, int pad, int So, int Po);
+int tn_c8_dwconv_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, int N, int C, int S, int P, int f,
+                     int stride, int pad, int So, int Po, int act, float prm);
+int tn_c8_dwconv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int S, int P, int f, int stride,
+                       int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);
+int tn_c8_dwconv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int f,
+                       int stride, int pad, int So, int Po);
 /* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
  * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
  * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on

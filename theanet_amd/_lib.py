@@ -83,6 +83,10 @@ SIGNATURES = {
     "tn_conv2d_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 10 + [c_int, c_float]),
     "tn_conv2d_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 10),
     "tn_conv2d_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 10 + [P, c_int, c_float]),
+    "tn_dwconv_supported": (c_int, [c_int] * 9),
+    "tn_dwconv_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 9 + [c_int, c_float]),
+    "tn_dwconv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 9),
+    "tn_dwconv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 9 + [P, c_int, c_float]),
     "tn_set_matmul_dtype": (c_int, [CTX, c_int, c_float]),
     "tn_get_matmul_dtype": (c_int, [CTX]),
     "tn_set_fc_matmul": (c_int, [CTX, c_int]),
@@ -133,6 +137,10 @@ SIGNATURES = {
     "tn_c8_convg_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 10 + [P, c_int, c_float]),
     "tn_c8_convg_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 10),
     "tn_c8_convg_plan": (c_int, [c_int] * 12 + [c_float, POINTER(c_int), c_int]),
+    "tn_c8_dwconv_supported": (c_int, [c_int] * 9),
+    "tn_c8_dwconv_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 10 + [c_float]),
+    "tn_c8_dwconv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 9 + [P, c_int, c_float]),
+    "tn_c8_dwconv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 9),
     "tn_c8_pack_pitch": (c_int, [CTX, P, c_int64, P] + [c_int] * 4 + [c_float]),
     "tn_c8_pad_zero": (c_int, [CTX, P] + [c_int] * 4),
     "tn_c8_crop": (c_int, [CTX, P, P] + [c_int] * 4),

@@ -444,6 +444,98 @@ int tn_conv2d_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int
     return TN_OK;
 }
 
+// ---- depthwise conv (ConvLayer depthwise): plain loops, W (C,1,f,f) in tn_conv2d_*'s orientation ----
+static bool dw_axis_ok(int S, int f, int stride, int pad, int So) {
+    if (S < 1 || So < 1) return false;
+    const long long hi = (long long)(So - 1) * stride + f - pad - S;
+    return pad >= 0 && pad <= f / 2 && hi <= pad && hi > -(long long)stride;
+}
+int tn_dwconv_supported(int N, int C, int H, int Wd, int f, int stride, int pad, int Ho, int Wo) {
+    if (N < 1 || C < 1 || C > 65535 || H > 65535 || Wd > 65535 || (f != 3 && f != 5) || stride < 1 || stride > 16) return 0;
+    if (!dw_axis_ok(H, f, stride, pad, Ho) || !dw_axis_ok(Wd, f, stride, pad, Wo)) return 0;
+    return (long long)N * C * H * Wd < (1ll << 32) && (long long)N * C * Ho * Wo < (1ll << 32);
+}
+#define DW_FMT "(N %d, %d maps of %d x %d -> %d x %d, filter %d stride %d pad_lo %d)"
+#define DW_ARGS N, C, H, Wd, Ho, Wo, f, stride, pad
+
+int tn_dwconv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int f,
+                  int stride, int pad, int Ho, int Wo, int act, float prm) {
+    REQUIRE(x && W && b && a && tn_dwconv_supported(N, C, H, Wd, f, stride, pad, Ho, Wo), "tn_dwconv_fwd: bad arguments " DW_FMT,
+            DW_ARGS);
+#pragma omp parallel for schedule(static)
+    for (int p = 0; p < N * C; ++p) {
+        const float *xp = x + (size_t)p * H * Wd, *w = W + (size_t)(p % C) * f * f;
+        for (int i = 0; i < Ho; ++i)
+            for (int j = 0; j < Wo; ++j) {
+                float z = 0.f;
+                for (int u = 0; u < f; ++u)
+                    for (int v = 0; v < f; ++v) {
+                        const int yy = i * stride + u - pad, xx = j * stride + v - pad;
+                        if (yy >= 0 && yy < H && xx >= 0 && xx < Wd) z += xp[(size_t)yy * Wd + xx] * w[(f - 1 - u) * f + (f - 1 - v)];
+                    }
+                a[((size_t)p * Ho + i) * Wo + j] = act_fwd(z + b[p % C], act, prm);
+            }
+    }
+    return TN_OK;
+}
+
+int tn_dwconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int f,
+                    int stride, int pad, int Ho, int Wo) {
+    REQUIRE(x && dz && dW && db && tn_dwconv_supported(N, C, H, Wd, f, stride, pad, Ho, Wo),
+            "tn_dwconv_wgrad: bad arguments " DW_FMT, DW_ARGS);
+#pragma omp parallel for schedule(static)
+    for (int c = 0; c < C; ++c) {                               // images in order: deterministic
+        float s[25] = {0.f}, sb = 0.f;
+        for (int n = 0; n < N; ++n) {
+            const float *xp = x + ((size_t)n * C + c) * H * Wd, *dp = dz + ((size_t)n * C + c) * Ho * Wo;
+            for (int i = 0; i < Ho; ++i)
+                for (int j = 0; j < Wo; ++j) {
+                    const float d = dp[(size_t)i * Wo + j];
+                    sb += d;
+                    for (int u = 0; u < f; ++u)
+                        for (int v = 0; v < f; ++v) {
+                            const int yy = i * stride + u - pad, xx = j * stride + v - pad;
+                            if (yy >= 0 && yy < H && xx >= 0 && xx < Wd) s[(f - 1 - u) * f + (f - 1 - v)] += d * xp[(size_t)yy * Wd + xx];
+                        }
+                }
+        }
+        for (int k = 0; k < f * f; ++k) dW[(size_t)c * f * f + k] = s[k];
+        db[c] = sb;
+    }
+    return TN_OK;
+}
+
+int tn_dwconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int f, int stride,
+                    int pad, int Ho, int Wo, const float* prev_a, int prev_act, float prev_prm) {
+    REQUIRE(dz && W && dx && tn_dwconv_supported(N, C, H, Wd, f, stride, pad, Ho, Wo), "tn_dwconv_dgrad: bad arguments " DW_FMT,
+            DW_ARGS);
+#pragma omp parallel for schedule(static)
+    for (int p = 0; p < N * C; ++p) {
+        const float *dp = dz + (size_t)p * Ho * Wo, *w = W + (size_t)(p % C) * f * f;
+        float* o = dx + (size_t)p * H * Wd;
+        std::memset(o, 0, sizeof(float) * H * Wd);
+        for (int i = 0; i < Ho; ++i)
+            for (int j = 0; j < Wo; ++j)
+                for (int u = 0; u < f; ++u)
+                    for (int v = 0; v < f; ++v) {
+                        const int yy = i * stride + u - pad, xx = j * stride + v - pad;
+                        if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                            o[(size_t)yy * Wd + xx] += dp[(size_t)i * Wo + j] * w[(f - 1 - u) * f + (f - 1 - v)];
+                    }
+        if (prev_a && prev_act != TN_ACT_LINEAR)
+            for (int k = 0; k < H * Wd; ++k) o[k] *= act_grad_from_out(prev_a[(size_t)p * H * Wd + k], prev_act, prev_prm);
+    }
+    return TN_OK;
+}
+int tn_c8_dwconv_supported(int, int, int, int, int, int, int, int, int) { return 0; }
+int tn_c8_dwconv_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int,
+                     int, float) { NOT_HERE("tn_c8_dwconv_fwd"); }
+int tn_c8_dwconv_dgrad(tn_ctx* ctx, const void*, const float*, void*, int, int, int, int, int, int, int, int, int, const void*,
+                       int, float) { NOT_HERE("tn_c8_dwconv_dgrad"); }
+int tn_c8_dwconv_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, int) {
+    NOT_HERE("tn_c8_dwconv_wgrad");
+}
+
 // ---- MI355X-specific fused blocks: not offered here (capability queries answer 0) ----
 int tn_convpool_supported(int, int, int, int) { return 0; }
 int tn_convpool_fwd(tn_ctx* ctx, const float*, const float*, const float*, float*, int, int, int, int, int, int, int, int,

@@ -34,6 +34,8 @@ FusedGeom = namedtuple("FusedGeom", "N C H W K f pad Ho Wo p Hp Wp act prm")
 
 
 class ConvLayer(Layer):
+    depthwise = False          # (class level: the default of a layer built without the keyword)
+
     def __init__(self, inpt, wts, rand_gen,
                  batch_sz, num_prev_maps, in_sz,
                  num_maps, filter_sz, stride,
@@ -41,17 +43,28 @@ class ConvLayer(Layer):
                  actvn='relu50',
                  reg=(),
                  dtype='float32',
-                 conv_shapes='tiled'):
+                 conv_shapes='tiled',
+                 depthwise=False):
+        """``depthwise``: every map is convolved with its own filter and nothing is summed across maps (channel
+        multiplier 1: W (C, 1, f, f)); 3x3 or 5x5, stride 1 or 2, kernels of their own (tn_dwconv_* / tn_c8_dwconv_*),
+        never fused with a layer above or below.  Under CONV 'bfloat16' the layer stays fp32: it has no matrix product."""
         assert (wts is not None or rand_gen is not None)
         assert mode in ("valid", "full", "same")
         if mode == "full":
             raise NotImplementedError(
                 "ConvLayer mode 'full': the reference computes out_sz = in+f+1 "
                 "(convpool.py:63-64), which no backend can honour")
+        self.depthwise = bool(depthwise)
+        if self.depthwise:
+            assert num_maps == num_prev_maps, (
+                "a depthwise ConvLayer has channel multiplier 1: num_maps must equal the maps below it "
+                "(got num_maps {} on {} maps)".format(num_maps, num_prev_maps))
+            assert filter_sz in (3, 5), "a depthwise ConvLayer takes filter_sz 3 or 5, not {!r}".format(filter_sz)
+            assert stride in (1, 2), "a depthwise ConvLayer takes stride 1 or 2, not {!r}".format(stride)
 
-        filter_shape = (num_maps, num_prev_maps, filter_sz, filter_sz)
-        fan_in = num_prev_maps * filter_sz * filter_sz
-        fan_out = num_maps * filter_sz * filter_sz
+        filter_shape = (num_maps, 1 if self.depthwise else num_prev_maps, filter_sz, filter_sz)
+        fan_in = filter_shape[1] * filter_sz * filter_sz
+        fan_out = (1 if self.depthwise else num_maps) * filter_sz * filter_sz
         self.W, self.b = init_wb(wts, rand_gen, filter_shape, (filter_shape[0], ),
                                  fan_in, fan_out, actvn, 'Conv')
 
@@ -87,7 +100,7 @@ class ConvLayer(Layer):
             # construction fails there for a shape the net's CONV_SHAPES does not let onto the stack)
             self.c8_fam, self.c8_1x1, P, Po = choose_conv(
                 lib, dtype, conv_shapes, batch_sz, num_prev_maps, in_sz, inpt.pitch if is_c8(inpt) else None, num_maps,
-                filter_sz, stride, mode, self.pad_lo, self.out_sz)
+                filter_sz, stride, mode, self.pad_lo, self.out_sz, depthwise=self.depthwise)
             self.pitch = P
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
             self.x16 = None if is_c8(inpt) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz, dtype, pitch=P)
@@ -123,6 +136,9 @@ class ConvLayer(Layer):
             "Act:{}\n\t  L1:{L1} L2:{L2} Momentum:{momentum} Rate:{rate} Max Norm:{maxnorm}"
             "".format(num_maps, filter_sz, stride, mode, self.out_sz,
                       actvn, **self.reg))
+        if self.depthwise:
+            self.args += (True,)
+            self.representation += " Depthwise"
 
     def TestVersion(self, inpt):
         return ConvLayer(inpt, (self.W, self.b), None, *self.args)
@@ -131,14 +147,15 @@ class ConvLayer(Layer):
         return self.output, self.act.kind, self.act.prm, None
 
     def _geom(self):
-        return (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz, self.num_maps,
-                self.filter_sz, self.stride, self.pad_lo, self.out_sz, self.out_sz)
+        """The geometry arguments of tn_conv2d_* -- of tn_dwconv_* for a depthwise layer: the same without K."""
+        return (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz) + (() if self.depthwise else (self.num_maps,)) + \
+            (self.filter_sz, self.stride, self.pad_lo, self.out_sz, self.out_sz)
 
     def can_fuse_with(self, pool):
         """conv -> act -> 2x2 max-pool as one fused kernel pair -- the conv activation never reaches HBM.  Returns the
         family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused.
         A pool whose stride differs from its window is never fused: the blocks pool with stride = window."""
-        if getattr(pool, "strided", False):
+        if getattr(pool, "strided", False) or self.depthwise:
             return None
         if self.f16:
             # what the fused block takes; any other PoolLayer of the stack stands alone (c8.check_follows)
@@ -243,8 +260,8 @@ class ConvLayer(Layer):
             return                       # the pool layer launches the fused kernel
         if self.f16:
             return self._c8_forward(self.output, None)
-        self.ctx.call("tn_conv2d_fwd", self.inpt.ptr, self.W.ptr, self.b.ptr, self.output.ptr,
-                      *self._geom(), self.act.kind, self.act.prm)
+        self.ctx.call("tn_dwconv_fwd" if self.depthwise else "tn_conv2d_fwd", self.inpt.ptr, self.W.ptr, self.b.ptr,
+                      self.output.ptr, *self._geom(), self.act.kind, self.act.prm)
 
     def _block_route(self, need_gin, below):
         """Which backward the fused fp32 block takes.  Decided once, from whether the layer below wants a gradient and an
@@ -309,15 +326,16 @@ class ConvLayer(Layer):
             if not need_gin or route.writes_dx:
                 return gout
         elif self.has_updates():
-            self.ctx.call("tn_conv2d_wgrad", self.inpt.ptr, gout.ptr, self.grads[0].ptr,
-                          self.grads[1].ptr, *self._geom())
+            self.ctx.call("tn_dwconv_wgrad" if self.depthwise else "tn_conv2d_wgrad", self.inpt.ptr, gout.ptr,
+                          self.grads[0].ptr, self.grads[1].ptr, *self._geom())
         if not need_gin:
             return None
         if self.gin is None:
             self.gin = self.ctx.empty(self.inpt.shape)
         b_ptr, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
-        self.ctx.call("tn_conv2d_dgrad", gout.ptr, self.W.ptr, self.gin.ptr, *self._geom(), b_ptr, b_act, b_prm)
+        self.ctx.call("tn_dwconv_dgrad" if self.depthwise else "tn_conv2d_dgrad", gout.ptr, self.W.ptr, self.gin.ptr,
+                      *self._geom(), b_ptr, b_act, b_prm)
         return self.gin
 
 

@@ -46,7 +46,7 @@ def net_step_flops(net):
     total, first = 0, True
     for lyr in net.tr_layers:
         if isinstance(lyr, ConvLayer):
-            f = 2 * lyr.batch_sz * lyr.out_sz ** 2 * lyr.num_maps * lyr.num_prev_maps * lyr.filter_sz ** 2
+            f = 2 * lyr.batch_sz * lyr.out_sz ** 2 * lyr.num_maps * lyr.W.shape[1] * lyr.filter_sz ** 2
         elif isinstance(lyr, HiddenLayer):
             f = 2 * lyr.batch_sz * lyr.n_in * lyr.n_out
         else:
