@@ -163,6 +163,26 @@ int tn_dwconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, flo
 int tn_dwconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int f, int stride,
                     int pad_lo, int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
 
+/* Grouped convolution (ConvLayer(..., groups=g); theanet_amd/csrc/gconv.hip): the C maps and the K filters are cut into g
+ * groups, filter k reads the C/g maps of group k / (K/g) alone,
+ *   z[n,k,i,j] = b[k] + sum_{c<C/g,u,v} xpad[n,(k/(K/g))*(C/g)+c,i*s+u,j*s+v] * W[k,c,f-1-u,f-1-v]
+ * W (K,C/g,f,f), b (K); the arguments are tn_conv2d_*'s with g behind K, NCHW fp32, any f, stride and padding a ConvLayer
+ * takes.  One launch a product for the whole layer; products and accumulation in fp32 (v_mfma_f32_16x16x4_f32 where
+ * K/g >= 16 and C/g >= 4, fmaf below), the same under every CONV mode
+ * (CONV 'bfloat16' leaves a grouped layer on these ops); refused in a 16-bit DTYPE mode like tn_conv2d_*.  fwd fuses bias
+ * + activation; wgrad OVERWRITES dW / db (slab sums finished by the context's fixed-order reduction, a slab count of the
+ * geometry alone, no atomics: the same bits every run); dgrad fuses act'(prev_a) (NULL: none), a strided one is a gather.
+ * supported: 1 for g >= 1 dividing C and K, f <= 64, at most 65535 maps, rows and columns, fewer than 2^32 elements a
+ * tensor, K C/g f f < 2^28 and Ho / Wo the number of windows that fit with pad_lo <= f / 2 low and at most as much high
+ * padding (tn_c8_convg_supported's rule); bad geometry or a NULL tensor: TN_E_ARG naming the entry point, nothing launched. */
+int tn_gconv_supported(int N, int C, int H, int Wd, int K, int g, int f, int stride, int pad_lo, int Ho, int Wo);
+int tn_gconv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K, int g,
+                 int f, int stride, int pad_lo, int Ho, int Wo, int act, float act_param);
+int tn_gconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K, int g,
+                   int f, int stride, int pad_lo, int Ho, int Wo);
+int tn_gconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int g, int f,
+                   int stride, int pad_lo, int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
+
 /* ---- DTYPE 'float16' / 'bfloat16' (BASELINE configs[4]; the reference is float32-only, weights.py:8 `floatX`: opt-in
  * training params of this build, default off) ----
  * dtype 0: every tensor fp32 (reference arithmetic).  dtype 1: the conv stack of the net lives in HBM as halfs and is
@@ -487,6 +507,30 @@ int tn_c8_dwconv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, in
                        int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);
 int tn_c8_dwconv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int f,
                        int stride, int pad, int So, int Po);
+/* Grouped ConvLayers on c8 tensors (ConvLayer(..., groups=g): filter k reads the C/g maps of group k / (K/g) alone;
+ * theanet_amd/csrc/gconv_c8.hip, gconv.h).  The arguments are tn_c8_convg_*'s with g behind K: x / dx hold N x C maps, y / dz
+ * N x K; W (K, C/g, f, f) fp32 master weights in tn_conv2d_*'s orientation, b (K) fp32.  C/g and K/g are multiples of 8: a
+ * group is a whole number of 16-byte cells.  The semantics are tn_c8_convg_*'s restricted to the groups: x and dz as
+ * stored, W rounded to the 16-bit type (nearest even), exact products, fp32 accumulation on the matrix core
+ * (v_mfma_f32_16x16x32: 16 rows are one group's outputs, the reduction four (tap, octet) cells fed from an LDS halo tile;
+ * v_mfma_f32_32x32x16 for groups of a multiple of 32 outputs on planes of 16 rows or more),
+ * bias / activation on the fp32 sums, one rounding on store; dz / dx carry the gradient scale.  One launch a product for
+ * the whole layer, no product on the zero blocks of the block-diagonal dense form.
+ * fwd: y = act(gconv(x, W) + b).  dgrad: dx = R(gconv^T(dz, W) * act'(prev_a)) (NULL: no derivative).  EVERY cell of y / dx
+ *   is written by the op: pad cells and input pixels no strided window touches as exact +0.
+ * wgrad: dW (K, C/g, f, f), db (K) fp32, OVERWRITE, the gradient scale removed in the fp32 epilogue; db is summed from the
+ *   stored dz.  Slab sums in context scratch finished by the context's reduction: a slab count that depends on the
+ *   geometry alone, no atomics, the same bits every run.
+ * supported: tn_c8_convg_supported's consistency rule, and g >= 1 dividing C and K with C/g and K/g multiples of 8, at most
+ *   65535 groups, f <= 255 and f f max(C/g, K/g) / 8 <= 4096.  Anything else, and any NULL tensor: TN_E_ARG naming the
+ *   entry point, nothing launched.                                                                                       */
+int tn_c8_gconv_supported(int N, int C, int S, int P, int K, int g, int f, int stride, int pad, int So, int Po);
+int tn_c8_gconv_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, int N, int C, int S, int P, int K, int g,
+                    int f, int stride, int pad, int So, int Po, int act, float prm);
+int tn_c8_gconv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int S, int P, int K, int g, int f,
+                      int stride, int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);
+int tn_c8_gconv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int K, int g,
+                      int f, int stride, int pad, int So, int Po);
 /* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
  * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
  * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on

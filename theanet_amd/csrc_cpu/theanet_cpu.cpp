@@ -536,6 +536,114 @@ int tn_c8_dwconv_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, in
     NOT_HERE("tn_c8_dwconv_wgrad");
 }
 
+// ---- grouped conv (ConvLayer groups): plain loops, W (K,C/g,f,f) in tn_conv2d_*'s orientation ----
+static bool gc_axis_ok(int S, int f, int stride, int pad, int So) {
+    if (S < 1 || So < 1 || f < 1 || stride < 1 || pad < 0 || f >= (1 << 15) || stride >= (1 << 15)) return false;
+    const long long hi = (long long)(So - 1) * stride + f - pad - S;
+    return pad <= f / 2 && hi <= pad && hi > -(long long)stride;
+}
+int tn_gconv_supported(int N, int C, int H, int Wd, int K, int g, int f, int stride, int pad, int Ho, int Wo) {
+    if (N < 1 || g < 1 || C < 1 || K < 1 || C % g || K % g || K > 65535 || C > 65535 || f > 64 || H > 65535 || Wd > 65535) return 0;
+    if (!gc_axis_ok(H, f, stride, pad, Ho) || !gc_axis_ok(Wd, f, stride, pad, Wo)) return 0;
+    if ((long long)N * C * H * Wd >= (1ll << 32) || (long long)N * K * Ho * Wo >= (1ll << 32)) return 0;
+    return (long long)K * (C / g) * f * f < (1ll << 28);
+}
+#define GC_FMT "(N %d, %d maps of %d x %d -> %d maps of %d x %d, %d groups, filter %d stride %d pad_lo %d)"
+#define GC_ARGS N, C, H, Wd, K, Ho, Wo, g, f, stride, pad
+
+int tn_gconv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K, int g,
+                 int f, int stride, int pad, int Ho, int Wo, int act, float prm) {
+    REQUIRE(x && W && b && a && tn_gconv_supported(N, C, H, Wd, K, g, f, stride, pad, Ho, Wo), "tn_gconv_fwd: bad arguments " GC_FMT,
+            GC_ARGS);
+    const int Cg = C / g, Kg = K / g;
+#pragma omp parallel for schedule(static)
+    for (int p = 0; p < N * K; ++p) {
+        const int n = p / K, k = p % K;
+        const float *xg = x + ((size_t)n * C + (size_t)(k / Kg) * Cg) * H * Wd, *w = W + (size_t)k * Cg * f * f;
+        for (int i = 0; i < Ho; ++i)
+            for (int j = 0; j < Wo; ++j) {
+                float z = 0.f;
+                for (int c = 0; c < Cg; ++c)
+                    for (int u = 0; u < f; ++u)
+                        for (int v = 0; v < f; ++v) {
+                            const int yy = i * stride + u - pad, xx = j * stride + v - pad;
+                            if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                                z += xg[((size_t)c * H + yy) * Wd + xx] * w[(c * f + f - 1 - u) * f + (f - 1 - v)];
+                        }
+                a[((size_t)p * Ho + i) * Wo + j] = act_fwd(z + b[k], act, prm);
+            }
+    }
+    return TN_OK;
+}
+
+int tn_gconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K, int g,
+                   int f, int stride, int pad, int Ho, int Wo) {
+    REQUIRE(x && dz && dW && db && tn_gconv_supported(N, C, H, Wd, K, g, f, stride, pad, Ho, Wo),
+            "tn_gconv_wgrad: bad arguments " GC_FMT, GC_ARGS);
+    const int Cg = C / g, Kg = K / g;
+#pragma omp parallel for schedule(static)
+    for (int k = 0; k < K; ++k) {                               // images in order: deterministic
+        float* s = dW + (size_t)k * Cg * f * f;
+        std::memset(s, 0, sizeof(float) * Cg * f * f);
+        float sb = 0.f;
+        for (int n = 0; n < N; ++n) {
+            const float *xg = x + ((size_t)n * C + (size_t)(k / Kg) * Cg) * H * Wd, *dp = dz + ((size_t)n * K + k) * Ho * Wo;
+            for (int i = 0; i < Ho; ++i)
+                for (int j = 0; j < Wo; ++j) {
+                    const float d = dp[(size_t)i * Wo + j];
+                    sb += d;
+                    for (int c = 0; c < Cg; ++c)
+                        for (int u = 0; u < f; ++u)
+                            for (int v = 0; v < f; ++v) {
+                                const int yy = i * stride + u - pad, xx = j * stride + v - pad;
+                                if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                                    s[(c * f + f - 1 - u) * f + (f - 1 - v)] += d * xg[((size_t)c * H + yy) * Wd + xx];
+                            }
+                }
+        }
+        db[k] = sb;
+    }
+    return TN_OK;
+}
+
+int tn_gconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int g, int f,
+                   int stride, int pad, int Ho, int Wo, const float* prev_a, int prev_act, float prev_prm) {
+    REQUIRE(dz && W && dx && tn_gconv_supported(N, C, H, Wd, K, g, f, stride, pad, Ho, Wo), "tn_gconv_dgrad: bad arguments " GC_FMT,
+            GC_ARGS);
+    const int Cg = C / g, Kg = K / g;
+#pragma omp parallel for schedule(static)
+    for (int p = 0; p < N * g; ++p) {                           // a group of an image: its Cg planes of dx
+        const int n = p / g, grp = p % g;
+        float* o = dx + ((size_t)n * C + (size_t)grp * Cg) * H * Wd;
+        std::memset(o, 0, sizeof(float) * Cg * H * Wd);
+        for (int kl = 0; kl < Kg; ++kl) {
+            const int k = grp * Kg + kl;
+            const float *dp = dz + ((size_t)n * K + k) * Ho * Wo, *w = W + (size_t)k * Cg * f * f;
+            for (int c = 0; c < Cg; ++c)
+                for (int i = 0; i < Ho; ++i)
+                    for (int j = 0; j < Wo; ++j)
+                        for (int u = 0; u < f; ++u)
+                            for (int v = 0; v < f; ++v) {
+                                const int yy = i * stride + u - pad, xx = j * stride + v - pad;
+                                if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                                    o[((size_t)c * H + yy) * Wd + xx] += dp[(size_t)i * Wo + j] * w[(c * f + f - 1 - u) * f + (f - 1 - v)];
+                            }
+        }
+        if (prev_a && prev_act != TN_ACT_LINEAR) {
+            const float* pa = prev_a + ((size_t)n * C + (size_t)grp * Cg) * H * Wd;
+            for (size_t q = 0; q < (size_t)Cg * H * Wd; ++q) o[q] *= act_grad_from_out(pa[q], prev_act, prev_prm);
+        }
+    }
+    return TN_OK;
+}
+int tn_c8_gconv_supported(int, int, int, int, int, int, int, int, int, int, int) { return 0; }
+int tn_c8_gconv_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int, int,
+                    int, int, float) { NOT_HERE("tn_c8_gconv_fwd"); }
+int tn_c8_gconv_dgrad(tn_ctx* ctx, const void*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int,
+                      const void*, int, float) { NOT_HERE("tn_c8_gconv_dgrad"); }
+int tn_c8_gconv_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, int, int,
+                      int) { NOT_HERE("tn_c8_gconv_wgrad"); }
+
 // ---- MI355X-specific fused blocks: not offered here (capability queries answer 0) ----
 int tn_convpool_supported(int, int, int, int) { return 0; }
 int tn_convpool_fwd(tn_ctx* ctx, const float*, const float*, const float*, float*, int, int, int, int, int, int, int, int,

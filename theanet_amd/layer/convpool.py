@@ -35,6 +35,7 @@ FusedGeom = namedtuple("FusedGeom", "N C H W K f pad Ho Wo p Hp Wp act prm")
 
 class ConvLayer(Layer):
     depthwise = False          # (class level: the default of a layer built without the keyword)
+    groups = 1
 
     def __init__(self, inpt, wts, rand_gen,
                  batch_sz, num_prev_maps, in_sz,
@@ -44,10 +45,16 @@ class ConvLayer(Layer):
                  reg=(),
                  dtype='float32',
                  conv_shapes='tiled',
-                 depthwise=False):
+                 depthwise=False,
+                 groups=1):
         """``depthwise``: every map is convolved with its own filter and nothing is summed across maps (channel
         multiplier 1: W (C, 1, f, f)); 3x3 or 5x5, stride 1 or 2, kernels of their own (tn_dwconv_* / tn_c8_dwconv_*),
-        never fused with a layer above or below.  Under CONV 'bfloat16' the layer stays fp32: it has no matrix product."""
+        never fused with a layer above or below.  Under CONV 'bfloat16' the layer stays fp32: it has no matrix product.
+        ``groups`` (g > 1): the maps below and the filters are cut into g groups, filter k reads the num_prev_maps / g maps
+        of group k // (num_maps / g) alone: W (K, C/g, f, f); any filter_sz, stride and mode, kernels of their own
+        (tn_gconv_* / tn_c8_gconv_*), never fused with a pool.  Under CONV 'bfloat16' a grouped layer stays on its fp32 ops
+        (no bf16-operand form).  On a 16-bit DTYPE C/g and K/g must be multiples of 8 (a group is a whole number of
+        16-byte cells) or construction fails; float32 takes every divisor.  groups=1 is the dense layer, unchanged."""
         assert (wts is not None or rand_gen is not None)
         assert mode in ("valid", "full", "same")
         if mode == "full":
@@ -61,10 +68,15 @@ class ConvLayer(Layer):
                 "(got num_maps {} on {} maps)".format(num_maps, num_prev_maps))
             assert filter_sz in (3, 5), "a depthwise ConvLayer takes filter_sz 3 or 5, not {!r}".format(filter_sz)
             assert stride in (1, 2), "a depthwise ConvLayer takes stride 1 or 2, not {!r}".format(stride)
+        self.groups = int(groups)
+        assert self.groups >= 1 and num_prev_maps % self.groups == 0 and num_maps % self.groups == 0, (
+            "ConvLayer groups must divide the maps below and num_maps (got groups {!r}, {} maps on {})".format(
+                groups, num_maps, num_prev_maps))
+        assert not (self.groups > 1 and self.depthwise), "ConvLayer takes groups > 1 or depthwise, not both"
 
-        filter_shape = (num_maps, 1 if self.depthwise else num_prev_maps, filter_sz, filter_sz)
+        filter_shape = (num_maps, 1 if self.depthwise else num_prev_maps // self.groups, filter_sz, filter_sz)
         fan_in = filter_shape[1] * filter_sz * filter_sz
-        fan_out = (1 if self.depthwise else num_maps) * filter_sz * filter_sz
+        fan_out = (1 if self.depthwise else num_maps // self.groups) * filter_sz * filter_sz
         self.W, self.b = init_wb(wts, rand_gen, filter_shape, (filter_shape[0], ),
                                  fan_in, fan_out, actvn, 'Conv')
 
@@ -100,7 +112,7 @@ class ConvLayer(Layer):
             # construction fails there for a shape the net's CONV_SHAPES does not let onto the stack)
             self.c8_fam, self.c8_1x1, P, Po = choose_conv(
                 lib, dtype, conv_shapes, batch_sz, num_prev_maps, in_sz, inpt.pitch if is_c8(inpt) else None, num_maps,
-                filter_sz, stride, mode, self.pad_lo, self.out_sz, depthwise=self.depthwise)
+                filter_sz, stride, mode, self.pad_lo, self.out_sz, depthwise=self.depthwise, groups=self.groups)
             self.pitch = P
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
             self.x16 = None if is_c8(inpt) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz, dtype, pitch=P)
@@ -139,6 +151,9 @@ class ConvLayer(Layer):
         if self.depthwise:
             self.args += (True,)
             self.representation += " Depthwise"
+        if self.groups > 1:
+            self.args += (False, self.groups)
+            self.representation += " Groups:{}".format(self.groups)
 
     def TestVersion(self, inpt):
         return ConvLayer(inpt, (self.W, self.b), None, *self.args)
@@ -147,15 +162,21 @@ class ConvLayer(Layer):
         return self.output, self.act.kind, self.act.prm, None
 
     def _geom(self):
-        """The geometry arguments of tn_conv2d_* -- of tn_dwconv_* for a depthwise layer: the same without K."""
-        return (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz) + (() if self.depthwise else (self.num_maps,)) + \
+        """The geometry arguments of tn_conv2d_* -- of tn_dwconv_* for a depthwise layer: the same without K; of tn_gconv_*
+        for a grouped one: the same with the groups behind K."""
+        k = () if self.depthwise else ((self.num_maps, self.groups) if self.groups > 1 else (self.num_maps,))
+        return (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz) + k + \
             (self.filter_sz, self.stride, self.pad_lo, self.out_sz, self.out_sz)
+
+    def _op(self, which):
+        """The fp32 op of the layer's family: tn_conv2d_*, tn_dwconv_* (depthwise) or tn_gconv_* (groups > 1)."""
+        return ("tn_dwconv_" if self.depthwise else "tn_gconv_" if self.groups > 1 else "tn_conv2d_") + which
 
     def can_fuse_with(self, pool):
         """conv -> act -> 2x2 max-pool as one fused kernel pair -- the conv activation never reaches HBM.  Returns the
         family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused.
         A pool whose stride differs from its window is never fused: the blocks pool with stride = window."""
-        if getattr(pool, "strided", False) or self.depthwise:
+        if getattr(pool, "strided", False) or self.depthwise or self.groups > 1:
             return None
         if self.f16:
             # what the fused block takes; any other PoolLayer of the stack stands alone (c8.check_follows)
@@ -260,7 +281,7 @@ class ConvLayer(Layer):
             return                       # the pool layer launches the fused kernel
         if self.f16:
             return self._c8_forward(self.output, None)
-        self.ctx.call("tn_dwconv_fwd" if self.depthwise else "tn_conv2d_fwd", self.inpt.ptr, self.W.ptr, self.b.ptr,
+        self.ctx.call(self._op("fwd"), self.inpt.ptr, self.W.ptr, self.b.ptr,
                       self.output.ptr, *self._geom(), self.act.kind, self.act.prm)
 
     def _block_route(self, need_gin, below):
@@ -326,7 +347,7 @@ class ConvLayer(Layer):
             if not need_gin or route.writes_dx:
                 return gout
         elif self.has_updates():
-            self.ctx.call("tn_dwconv_wgrad" if self.depthwise else "tn_conv2d_wgrad", self.inpt.ptr, gout.ptr,
+            self.ctx.call(self._op("wgrad"), self.inpt.ptr, gout.ptr,
                           self.grads[0].ptr, self.grads[1].ptr, *self._geom())
         if not need_gin:
             return None
@@ -334,7 +355,7 @@ class ConvLayer(Layer):
             self.gin = self.ctx.empty(self.inpt.shape)
         b_ptr, b_act, b_prm, b_mask = below_info(below)
         assert b_mask is None
-        self.ctx.call("tn_dwconv_dgrad" if self.depthwise else "tn_conv2d_dgrad", gout.ptr, self.W.ptr, self.gin.ptr,
+        self.ctx.call(self._op("dgrad"), gout.ptr, self.W.ptr, self.gin.ptr,
                       *self._geom(), b_ptr, b_act, b_prm)
         return self.gin
 
