@@ -183,6 +183,28 @@ int tn_gconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, floa
 int tn_gconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int g, int f,
                    int stride, int pad_lo, int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
 
+/* Dilated convolution (ConvLayer(..., dilation=d), Theano's filter_dilation=(d, d); theanet_amd/csrc/dilconv.hip, dilconv.h):
+ * the taps of the f x f filter are d pixels apart,
+ *   z[n,k,i,j] = b[k] + sum_{c,u,v} xpad[n,c,i+u*d,j+v*d] * W[k,c,f-1-u,f-1-v]
+ * -- what a dense layer of filter fe = (f-1)*d+1 computes whose weights are W zero-stuffed; pad_lo, Ho and Wo are that
+ * layer's.  W (K,C,f,f), b (K); the arguments are tn_conv2d_*'s with d behind K, NCHW fp32.  One launch a product: the
+ * layer is split into its d*d phases, each a dense f x f convolution on a d-strided sub-lattice, the phase a grid
+ * dimension, its source tile (halo f-1) staged in LDS; v_mfma_f32_16x16x4_f32 where K >= 16 and C >= 4, fmaf below.  fp32
+ * under every CONV mode; refused in a 16-bit DTYPE mode like tn_conv2d_*.  fwd fuses bias + activation; wgrad OVERWRITES
+ * dW / db (slab sums finished by the context's fixed-order reduction, a slab count of the geometry alone, no atomics: the
+ * same bits every run); dgrad fuses act'(prev_a) (NULL: none).  d = 1 with stride > 1 is handed to tn_conv2d_*.
+ * supported: 1 for 1 <= d <= 255, f <= 32, stride 1 when d > 1, at most 65535 maps, rows and columns, fewer than 2^32
+ * elements a tensor, K C f f < 2^28 and Ho / Wo the number of windows of side fe that fit with pad_lo <= fe / 2 low and at
+ * most as much high padding (tn_c8_convg_supported's rule with fe for f); bad geometry or a NULL tensor: TN_E_ARG naming
+ * the entry point, nothing launched. */
+int tn_dilconv_supported(int N, int C, int H, int Wd, int K, int d, int f, int stride, int pad_lo, int Ho, int Wo);
+int tn_dilconv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K, int d,
+                   int f, int stride, int pad_lo, int Ho, int Wo, int act, float act_param);
+int tn_dilconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K, int d,
+                     int f, int stride, int pad_lo, int Ho, int Wo);
+int tn_dilconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int d, int f,
+                     int stride, int pad_lo, int Ho, int Wo, const float* prev_a, int prev_act, float prev_act_param);
+
 /* ---- DTYPE 'float16' / 'bfloat16' (BASELINE configs[4]; the reference is float32-only, weights.py:8 `floatX`: opt-in
  * training params of this build, default off) ----
  * dtype 0: every tensor fp32 (reference arithmetic).  dtype 1: the conv stack of the net lives in HBM as halfs and is
@@ -531,6 +553,29 @@ int tn_c8_gconv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int
                       int stride, int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);
 int tn_c8_gconv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int K, int g,
                       int f, int stride, int pad, int So, int Po);
+/* Dilated ConvLayers on c8 tensors (ConvLayer(..., dilation=d): taps d pixels apart; theanet_amd/csrc/dilconv_c8.hip,
+ * dilconv.h).  The arguments are tn_c8_convg_*'s with d behind K; pad, So and Po are those of the dense layer of filter
+ * (f-1)*d+1; W (K, C, f, f) fp32 master weights in tn_conv2d_*'s orientation, b (K) fp32; any C and K.  The semantics are
+ * tn_c8_convg_*'s: x and dz as stored, W rounded to the 16-bit type (nearest even), exact products, fp32 accumulation on
+ * the matrix core, bias / activation on the fp32 sums, one rounding on store; dz / dx carry the gradient scale.  One
+ * launch a product, split into the d*d phases of the layer: a block stages ONE phase's source tile (16-byte cells at a
+ * stride of d cells, halo f-1) in LDS and feeds v_mfma_f32_16x16x32 (v_mfma_f32_32x32x16 for a multiple of 32 outputs on
+ * a phase plane with the rows for it) from it.
+ * fwd: y = act(dilconv(x, W) + b).  dgrad: dx = R(dilconv^T(dz, W) * act'(prev_a)) (NULL: no derivative).  EVERY cell of
+ *   y / dx is written by the op: pad cells and maps past the last as exact +0.
+ * wgrad: dW (K, C, f, f), db (K) fp32, OVERWRITE, the gradient scale removed in the fp32 epilogue; slab sums finished by
+ *   the context's reduction: a slab count of the geometry alone, no atomics, the same bits every run.
+ * d = 1 with stride > 1 is handed to tn_c8_convg_*.
+ * supported: tn_c8_convg_supported's consistency rule with (f-1)*d+1 for f, 1 <= d <= 255, f <= 32, stride 1 when d > 1,
+ *   fewer than 2^32 cells a tensor, K C f f < 2^28.  Anything else, and any NULL tensor: TN_E_ARG naming the entry point,
+ *   nothing launched.                                                                                                    */
+int tn_c8_dilconv_supported(int N, int C, int S, int P, int K, int d, int f, int stride, int pad, int So, int Po);
+int tn_c8_dilconv_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, int N, int C, int S, int P, int K, int d,
+                      int f, int stride, int pad, int So, int Po, int act, float prm);
+int tn_c8_dilconv_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int S, int P, int K, int d, int f,
+                        int stride, int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);
+int tn_c8_dilconv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int K, int d,
+                        int f, int stride, int pad, int So, int Po);
 /* Padded pitch: a c8 tensor of S x S maps may be stored at a power-of-two side P > S (4 <= P <= 64), rows and columns
  * S..P-1 of every octet plane zero.  The conv entry points above then run on the P x P shape (their 'same' products
  * read zeros where the logical ones read padding) and the forward / input gradient are followed by tn_c8_pad_zero on

@@ -91,6 +91,10 @@ SIGNATURES = {
     "tn_gconv_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 11 + [c_int, c_float]),
     "tn_gconv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 11),
     "tn_gconv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 11 + [P, c_int, c_float]),
+    "tn_dilconv_supported": (c_int, [c_int] * 11),
+    "tn_dilconv_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 11 + [c_int, c_float]),
+    "tn_dilconv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 11),
+    "tn_dilconv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 11 + [P, c_int, c_float]),
     "tn_set_matmul_dtype": (c_int, [CTX, c_int, c_float]),
     "tn_get_matmul_dtype": (c_int, [CTX]),
     "tn_set_fc_matmul": (c_int, [CTX, c_int]),
@@ -149,6 +153,10 @@ SIGNATURES = {
     "tn_c8_gconv_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 12 + [c_float]),
     "tn_c8_gconv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 11 + [P, c_int, c_float]),
     "tn_c8_gconv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 11),
+    "tn_c8_dilconv_supported": (c_int, [c_int] * 11),
+    "tn_c8_dilconv_fwd": (c_int, [CTX, P, P, P, P] + [c_int] * 12 + [c_float]),
+    "tn_c8_dilconv_dgrad": (c_int, [CTX, P, P, P] + [c_int] * 11 + [P, c_int, c_float]),
+    "tn_c8_dilconv_wgrad": (c_int, [CTX, P, P, P, P] + [c_int] * 11),
     "tn_c8_pack_pitch": (c_int, [CTX, P, c_int64, P] + [c_int] * 4 + [c_float]),
     "tn_c8_pad_zero": (c_int, [CTX, P] + [c_int] * 4),
     "tn_c8_crop": (c_int, [CTX, P, P] + [c_int] * 4),

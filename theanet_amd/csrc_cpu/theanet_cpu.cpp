@@ -644,6 +644,106 @@ int tn_c8_gconv_dgrad(tn_ctx* ctx, const void*, const float*, void*, int, int, i
 int tn_c8_gconv_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, int, int,
                       int) { NOT_HERE("tn_c8_gconv_wgrad"); }
 
+// ---- dilated conv (ConvLayer dilation): plain loops, taps d pixels apart, W (K,C,f,f) in tn_conv2d_*'s orientation ----
+int tn_dilconv_supported(int N, int C, int H, int Wd, int K, int d, int f, int stride, int pad, int Ho, int Wo) {
+    if (N < 1 || C < 1 || K < 1 || K > 65535 || C > 65535 || H > 65535 || Wd > 65535) return 0;
+    if (d < 1 || d > 255 || f < 1 || f > 32 || (d > 1 && stride != 1)) return 0;
+    const int fe = (f - 1) * d + 1;
+    if (!gc_axis_ok(H, fe, stride, pad, Ho) || !gc_axis_ok(Wd, fe, stride, pad, Wo)) return 0;
+    if ((long long)N * C * H * Wd >= (1ll << 32) || (long long)N * K * Ho * Wo >= (1ll << 32)) return 0;
+    return (long long)K * C * f * f < (1ll << 28);
+}
+#define DC_FMT "(N %d, %d maps of %d x %d -> %d maps of %d x %d, dilation %d, filter %d stride %d pad_lo %d)"
+#define DC_ARGS N, C, H, Wd, K, Ho, Wo, d, f, stride, pad
+
+int tn_dilconv_fwd(tn_ctx* ctx, const float* x, const float* W, const float* b, float* a, int N, int C, int H, int Wd, int K, int d,
+                   int f, int stride, int pad, int Ho, int Wo, int act, float prm) {
+    REQUIRE(x && W && b && a && tn_dilconv_supported(N, C, H, Wd, K, d, f, stride, pad, Ho, Wo), "tn_dilconv_fwd: bad arguments " DC_FMT,
+            DC_ARGS);
+#pragma omp parallel for schedule(static)
+    for (int p = 0; p < N * K; ++p) {
+        const int n = p / K, k = p % K;
+        const float *xn = x + (size_t)n * C * H * Wd, *w = W + (size_t)k * C * f * f;
+        for (int i = 0; i < Ho; ++i)
+            for (int j = 0; j < Wo; ++j) {
+                float z = 0.f;
+                for (int c = 0; c < C; ++c)
+                    for (int u = 0; u < f; ++u)
+                        for (int v = 0; v < f; ++v) {
+                            const int yy = i * stride + u * d - pad, xx = j * stride + v * d - pad;
+                            if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                                z += xn[((size_t)c * H + yy) * Wd + xx] * w[(c * f + f - 1 - u) * f + (f - 1 - v)];
+                        }
+                a[((size_t)p * Ho + i) * Wo + j] = act_fwd(z + b[k], act, prm);
+            }
+    }
+    return TN_OK;
+}
+
+int tn_dilconv_wgrad(tn_ctx* ctx, const float* x, const float* dz, float* dW, float* db, int N, int C, int H, int Wd, int K, int d,
+                     int f, int stride, int pad, int Ho, int Wo) {
+    REQUIRE(x && dz && dW && db && tn_dilconv_supported(N, C, H, Wd, K, d, f, stride, pad, Ho, Wo),
+            "tn_dilconv_wgrad: bad arguments " DC_FMT, DC_ARGS);
+#pragma omp parallel for schedule(static)
+    for (int k = 0; k < K; ++k) {                               // images in order: deterministic
+        float* s = dW + (size_t)k * C * f * f;
+        std::memset(s, 0, sizeof(float) * C * f * f);
+        float sb = 0.f;
+        for (int n = 0; n < N; ++n) {
+            const float *xn = x + (size_t)n * C * H * Wd, *dp = dz + ((size_t)n * K + k) * Ho * Wo;
+            for (int i = 0; i < Ho; ++i)
+                for (int j = 0; j < Wo; ++j) {
+                    const float g = dp[(size_t)i * Wo + j];
+                    sb += g;
+                    for (int c = 0; c < C; ++c)
+                        for (int u = 0; u < f; ++u)
+                            for (int v = 0; v < f; ++v) {
+                                const int yy = i * stride + u * d - pad, xx = j * stride + v * d - pad;
+                                if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                                    s[(c * f + f - 1 - u) * f + (f - 1 - v)] += g * xn[((size_t)c * H + yy) * Wd + xx];
+                            }
+                }
+        }
+        db[k] = sb;
+    }
+    return TN_OK;
+}
+
+int tn_dilconv_dgrad(tn_ctx* ctx, const float* dz, const float* W, float* dx, int N, int C, int H, int Wd, int K, int d, int f,
+                     int stride, int pad, int Ho, int Wo, const float* prev_a, int prev_act, float prev_prm) {
+    REQUIRE(dz && W && dx && tn_dilconv_supported(N, C, H, Wd, K, d, f, stride, pad, Ho, Wo), "tn_dilconv_dgrad: bad arguments " DC_FMT,
+            DC_ARGS);
+#pragma omp parallel for schedule(static)
+    for (int n = 0; n < N; ++n) {
+        float* o = dx + (size_t)n * C * H * Wd;
+        std::memset(o, 0, sizeof(float) * C * H * Wd);
+        for (int k = 0; k < K; ++k) {
+            const float *dp = dz + ((size_t)n * K + k) * Ho * Wo, *w = W + (size_t)k * C * f * f;
+            for (int c = 0; c < C; ++c)
+                for (int i = 0; i < Ho; ++i)
+                    for (int j = 0; j < Wo; ++j)
+                        for (int u = 0; u < f; ++u)
+                            for (int v = 0; v < f; ++v) {
+                                const int yy = i * stride + u * d - pad, xx = j * stride + v * d - pad;
+                                if (yy >= 0 && yy < H && xx >= 0 && xx < Wd)
+                                    o[((size_t)c * H + yy) * Wd + xx] += dp[(size_t)i * Wo + j] * w[(c * f + f - 1 - u) * f + (f - 1 - v)];
+                            }
+        }
+        if (prev_a && prev_act != TN_ACT_LINEAR) {
+            const float* pa = prev_a + (size_t)n * C * H * Wd;
+            for (size_t q = 0; q < (size_t)C * H * Wd; ++q) o[q] *= act_grad_from_out(pa[q], prev_act, prev_prm);
+        }
+    }
+    return TN_OK;
+}
+int tn_c8_dilconv_supported(int, int, int, int, int, int, int, int, int, int, int) { return 0; }
+int tn_c8_dilconv_fwd(tn_ctx* ctx, const void*, const float*, const float*, void*, int, int, int, int, int, int, int, int, int, int,
+                      int, int, float) { NOT_HERE("tn_c8_dilconv_fwd"); }
+int tn_c8_dilconv_dgrad(tn_ctx* ctx, const void*, const float*, void*, int, int, int, int, int, int, int, int, int, int, int,
+                        const void*, int, float) { NOT_HERE("tn_c8_dilconv_dgrad"); }
+int tn_c8_dilconv_wgrad(tn_ctx* ctx, const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, int, int,
+                        int) { NOT_HERE("tn_c8_dilconv_wgrad"); }
+
 // ---- MI355X-specific fused blocks: not offered here (capability queries answer 0) ----
 int tn_convpool_supported(int, int, int, int) { return 0; }
 int tn_convpool_fwd(tn_ctx* ctx, const float*, const float*, const float*, float*, int, int, int, int, int, int, int, int,

@@ -14,8 +14,8 @@ def pool_stands_alone(pool_sz, fused=True, below=None, any_shapes=False, stride=
     of a net that does not fuse -- stands alone (tn_c8_pool_fwd / tn_c8_pool_bwd).  ``any_shapes`` (the net's
     CONV_SHAPES 'any') with the layer ``below``: a 2x2 one stands alone too where the block cannot take it -- above a
     ConvLayer of the general family (ConvFamily.pools false: never fused) and on an odd map.  Above a depthwise ConvLayer
-    (dwconv_c8.hip: never fused) and above a grouped one (gconv_c8.hip: never fused) it stands alone under either
-    CONV_SHAPES.  A pool whose ``stride``
+    (dwconv_c8.hip: never fused) and above a grouped or dilated one (gconv_c8.hip, dilconv_c8.hip: never fused) it
+    stands alone under either CONV_SHAPES.  A pool whose ``stride``
     differs from its window (None: the window) always stands alone (tn_c8_pool_st_fwd / tn_c8_pool_st_bwd)."""
     if stride is not None and stride != pool_sz:
         return True
@@ -23,8 +23,8 @@ def pool_stands_alone(pool_sz, fused=True, below=None, any_shapes=False, stride=
         return True
     if type(below).__name__ == "ConvLayer":
         fam = getattr(below, "c8_fam", None)
-        if fam is not None and fam.fwd in ("tn_c8_dwconv_fwd", "tn_c8_gconv_fwd"):
-            return True                      # a depthwise / grouped layer never pools, whatever CONV_SHAPES says
+        if fam is not None and fam.fwd in ("tn_c8_dwconv_fwd", "tn_c8_gconv_fwd", "tn_c8_dilconv_fwd"):
+            return True                      # a depthwise / grouped / dilated layer never pools, whatever CONV_SHAPES says
         if any_shapes:
             return (fam is not None and not fam.pools) or below.out_sz % 2 != 0
     return False
@@ -73,12 +73,16 @@ def check_follows(dtype, below, kind, pool_sz=None, fused=True, any_shapes=False
 ConvFamily = namedtuple("ConvFamily", "fwd wgrad dgrad geom tiles pad_zero pools")
 
 
-def conv_family(one_by_one, n, c, side, pitch, k, general=None, depthwise=False, groups=1):
+def conv_family(one_by_one, n, c, side, pitch, k, general=None, depthwise=False, groups=1, dilation=1):
     """3x3 stride-1 'same' (conv_c8.hip: runs on the pitch x pitch shape), 1x1 stride-1 (conv1_c8.hip: rounds its
     operand tiles per call, writes its output's pad cells itself) or -- ``general``: (filter, stride, low padding, output
     side, output pitch) -- any shape (convg_c8.hip: like the 1x1 family, an output pitch of its own, no pooling).
     ``depthwise`` (with ``general``): the per-channel family (dwconv_c8.hip: the general family's geometry without k).
-    ``groups`` > 1 (with ``general``): the grouped family (gconv_c8.hip: the general family's geometry, groups behind k)."""
+    ``groups`` > 1 (with ``general``): the grouped family (gconv_c8.hip: the general family's geometry, groups behind k).
+    ``dilation`` > 1 (with ``general``): the dilated family (dilconv_c8.hip: likewise, the dilation behind k)."""
+    if dilation > 1:
+        return ConvFamily("tn_c8_dilconv_fwd", "tn_c8_dilconv_wgrad", "tn_c8_dilconv_dgrad",
+                          (n, c, side, pitch, k, dilation) + tuple(general), False, False, False)
     if groups > 1:
         return ConvFamily("tn_c8_gconv_fwd", "tn_c8_gconv_wgrad", "tn_c8_gconv_dgrad",
                           (n, c, side, pitch, k, groups) + tuple(general), False, False, False)
@@ -95,7 +99,7 @@ def conv_family(one_by_one, n, c, side, pitch, k, general=None, depthwise=False,
 
 
 def choose_conv(lib, dtype, conv_shapes, n, c, side, in_pitch, k, f, stride, mode, pad_lo, out_side, depthwise=False,
-                groups=1):
+                groups=1, dilation=1):
     """The family that runs a ConvLayer of the stack and the pitches of its maps: (ConvFamily, 1x1 family?, input pitch,
     output pitch), from the library's capability queries alone (no device).  Maps of S pixels a side are stored at a pitch
     P: the input's (``in_pitch``), or -- first conv layer, None -- the smallest power of two >= max(S, 8); the tiled
@@ -107,7 +111,18 @@ def choose_conv(lib, dtype, conv_shapes, n, c, side, in_pitch, k, f, stride, mod
     two up to 64 pixels (tn_c8_pack_pitch), dense above (tn_c8_pack); its output pitch is c8_pool_pitch(out_side), so
     that any layer of the stack can follow.  ``depthwise``: the per-channel family (dwconv_c8.hip) with the general
     family's pitches, under either ``conv_shapes`` -- it has no tiled form to prefer.  ``groups`` > 1: the grouped family
-    (gconv_c8.hip), likewise; a group must be a whole number of 16-byte cells (c / groups and k / groups multiples of 8)."""
+    (gconv_c8.hip), likewise; a group must be a whole number of 16-byte cells (c / groups and k / groups multiples of 8).
+    ``dilation`` > 1: the dilated family (dilconv_c8.hip), likewise, any c and k; ``pad_lo`` and ``out_side`` are those of
+    the window (f - 1) dilation + 1."""
+    if dilation > 1:
+        P = in_pitch if in_pitch is not None else c8_pool_pitch(side)
+        Po = c8_pool_pitch(out_side)
+        general = (f, stride, pad_lo, out_side, Po)
+        assert lib.tn_c8_dilconv_supported(n, c, side, P, k, dilation, *general), (
+            "DTYPE {}: the dilated conv kernels refuse this layer (got {} maps on {}, {}x{} at pitch {}, {} filter {} "
+            "dilation {} stride {}: {}x{} at pitch {})".format(dtype, k, c, side, side, P, mode, f, dilation, stride,
+                                                               out_side, out_side, Po))
+        return conv_family(False, n, c, side, P, k, general, dilation=dilation), False, P, Po
     if groups > 1:
         P = in_pitch if in_pitch is not None else c8_pool_pitch(side)
         Po = c8_pool_pitch(out_side)

@@ -36,6 +36,7 @@ FusedGeom = namedtuple("FusedGeom", "N C H W K f pad Ho Wo p Hp Wp act prm")
 class ConvLayer(Layer):
     depthwise = False          # (class level: the default of a layer built without the keyword)
     groups = 1
+    dilation = 1
 
     def __init__(self, inpt, wts, rand_gen,
                  batch_sz, num_prev_maps, in_sz,
@@ -46,7 +47,8 @@ class ConvLayer(Layer):
                  dtype='float32',
                  conv_shapes='tiled',
                  depthwise=False,
-                 groups=1):
+                 groups=1,
+                 dilation=1):
         """``depthwise``: every map is convolved with its own filter and nothing is summed across maps (channel
         multiplier 1: W (C, 1, f, f)); 3x3 or 5x5, stride 1 or 2, kernels of their own (tn_dwconv_* / tn_c8_dwconv_*),
         never fused with a layer above or below.  Under CONV 'bfloat16' the layer stays fp32: it has no matrix product.
@@ -54,7 +56,13 @@ class ConvLayer(Layer):
         of group k // (num_maps / g) alone: W (K, C/g, f, f); any filter_sz, stride and mode, kernels of their own
         (tn_gconv_* / tn_c8_gconv_*), never fused with a pool.  Under CONV 'bfloat16' a grouped layer stays on its fp32 ops
         (no bf16-operand form).  On a 16-bit DTYPE C/g and K/g must be multiples of 8 (a group is a whole number of
-        16-byte cells) or construction fails; float32 takes every divisor.  groups=1 is the dense layer, unchanged."""
+        16-byte cells) or construction fails; float32 takes every divisor.  groups=1 is the dense layer, unchanged.
+        ``dilation`` (d > 1, Theano's filter_dilation=(d, d)): the taps of the filter are d pixels apart -- the layer computes
+        what a dense layer of filter_sz fe = (filter_sz - 1) d + 1 computes whose weights are W zero-stuffed, and takes its
+        shape rules ('valid': out_sz = in_sz - fe + 1; 'same': the padding of fe); W stays (K, C, f, f) and fan_in / fan_out
+        come from f.  stride 1, not with depthwise or groups; kernels of their own (tn_dilconv_* / tn_c8_dilconv_*: the d d
+        phases of the layer as dense convolutions on sub-lattices), never fused with a pool; under CONV 'bfloat16' the
+        layer stays on its fp32 ops.  dilation=1 is the layer without the keyword."""
         assert (wts is not None or rand_gen is not None)
         assert mode in ("valid", "full", "same")
         if mode == "full":
@@ -73,6 +81,14 @@ class ConvLayer(Layer):
             "ConvLayer groups must divide the maps below and num_maps (got groups {!r}, {} maps on {})".format(
                 groups, num_maps, num_prev_maps))
         assert not (self.groups > 1 and self.depthwise), "ConvLayer takes groups > 1 or depthwise, not both"
+        assert isinstance(dilation, (int, np.integer)) and dilation >= 1, (
+            "ConvLayer dilation must be an integer >= 1, not {!r}".format(dilation))
+        self.dilation = int(dilation)
+        if self.dilation > 1:
+            assert stride == 1, "a ConvLayer with dilation > 1 takes stride 1, not {!r}".format(stride)
+            assert not self.depthwise, "ConvLayer takes dilation > 1 or depthwise, not both"
+            assert self.groups == 1, "ConvLayer takes dilation > 1 or groups > 1, not both (got groups {})".format(self.groups)
+        fe = (filter_sz - 1) * self.dilation + 1      # the side of the window the filter spans
 
         filter_shape = (num_maps, 1 if self.depthwise else num_prev_maps // self.groups, filter_sz, filter_sz)
         fan_in = filter_shape[1] * filter_sz * filter_sz
@@ -82,17 +98,17 @@ class ConvLayer(Layer):
 
         if mode == 'same':
             assert stride == 1, "For Same mode stride should be 1"
-            shift = (filter_sz - 1) // 2
-            self.pad_lo, pad_hi = filter_sz - 1 - shift, shift
+            shift = (fe - 1) // 2
+            self.pad_lo, pad_hi = fe - 1 - shift, shift
             self.out_sz = in_sz
         else:
             self.pad_lo, pad_hi = 0, 0
-            self.out_sz = in_sz - filter_sz + 1
+            self.out_sz = in_sz - fe + 1
         self.out_sz //= stride
-        theano_out = (in_sz + self.pad_lo + pad_hi - filter_sz) // stride + 1
+        theano_out = (in_sz + self.pad_lo + pad_hi - fe) // stride + 1
         assert self.out_sz == theano_out, (
             "stride {} must divide the stride-1 output size {}".format(
-                stride, in_sz + self.pad_lo + pad_hi - filter_sz + 1))
+                stride, in_sz + self.pad_lo + pad_hi - fe + 1))
 
         self.act = activation_by_name(actvn)
         assert self.act.kind is not None, "softmax is not a conv activation"
@@ -112,7 +128,8 @@ class ConvLayer(Layer):
             # construction fails there for a shape the net's CONV_SHAPES does not let onto the stack)
             self.c8_fam, self.c8_1x1, P, Po = choose_conv(
                 lib, dtype, conv_shapes, batch_sz, num_prev_maps, in_sz, inpt.pitch if is_c8(inpt) else None, num_maps,
-                filter_sz, stride, mode, self.pad_lo, self.out_sz, depthwise=self.depthwise, groups=self.groups)
+                filter_sz, stride, mode, self.pad_lo, self.out_sz, depthwise=self.depthwise, groups=self.groups,
+                dilation=self.dilation)
             self.pitch = P
             # the first conv layer of the net gets NCHW fp32 images: packed into a c8 tensor in front of the kernel
             self.x16 = None if is_c8(inpt) else C8Array(self.ctx, batch_sz, num_prev_maps, in_sz, in_sz, dtype, pitch=P)
@@ -154,6 +171,9 @@ class ConvLayer(Layer):
         if self.groups > 1:
             self.args += (False, self.groups)
             self.representation += " Groups:{}".format(self.groups)
+        if self.dilation > 1:
+            self.args += (False, 1, self.dilation)
+            self.representation += " Dilation:{}".format(self.dilation)
 
     def TestVersion(self, inpt):
         return ConvLayer(inpt, (self.W, self.b), None, *self.args)
@@ -163,20 +183,23 @@ class ConvLayer(Layer):
 
     def _geom(self):
         """The geometry arguments of tn_conv2d_* -- of tn_dwconv_* for a depthwise layer: the same without K; of tn_gconv_*
-        for a grouped one: the same with the groups behind K."""
-        k = () if self.depthwise else ((self.num_maps, self.groups) if self.groups > 1 else (self.num_maps,))
+        for a grouped one: the same with the groups behind K; of tn_dilconv_* for a dilated one: the dilation behind K."""
+        k = () if self.depthwise else ((self.num_maps, self.groups) if self.groups > 1 else
+                                       (self.num_maps, self.dilation) if self.dilation > 1 else (self.num_maps,))
         return (self.batch_sz, self.num_prev_maps, self.in_sz, self.in_sz) + k + \
             (self.filter_sz, self.stride, self.pad_lo, self.out_sz, self.out_sz)
 
     def _op(self, which):
-        """The fp32 op of the layer's family: tn_conv2d_*, tn_dwconv_* (depthwise) or tn_gconv_* (groups > 1)."""
-        return ("tn_dwconv_" if self.depthwise else "tn_gconv_" if self.groups > 1 else "tn_conv2d_") + which
+        """The fp32 op of the layer's family: tn_conv2d_*, tn_dwconv_* (depthwise), tn_gconv_* (groups > 1) or tn_dilconv_*
+        (dilation > 1)."""
+        return ("tn_dwconv_" if self.depthwise else "tn_gconv_" if self.groups > 1 else
+                "tn_dilconv_" if self.dilation > 1 else "tn_conv2d_") + which
 
     def can_fuse_with(self, pool):
         """conv -> act -> 2x2 max-pool as one fused kernel pair -- the conv activation never reaches HBM.  Returns the
         family of kernels that runs the block (ConvBlock.family; True on the 16-bit stack), None if it cannot be fused.
         A pool whose stride differs from its window is never fused: the blocks pool with stride = window."""
-        if getattr(pool, "strided", False) or self.depthwise or self.groups > 1:
+        if getattr(pool, "strided", False) or self.depthwise or self.groups > 1 or self.dilation > 1:
             return None
         if self.f16:
             # what the fused block takes; any other PoolLayer of the stack stands alone (c8.check_follows)

@@ -101,11 +101,13 @@ class NeuralNet():
     fused_step = True
     # the C-ABI ops that carry a net's conv products (bench.py brackets them for the conv roofline legs)
     CONV_FWD_OPS = ("tn_conv2d_fwd", "tn_convpool_fwd_mask", "tn_elastic_convpool_fwd_mask", "tn_c8_conv_fwd",
-                    "tn_c8_conv1_fwd", "tn_dwconv_fwd", "tn_c8_dwconv_fwd", "tn_gconv_fwd", "tn_c8_gconv_fwd")
+                    "tn_c8_conv1_fwd", "tn_dwconv_fwd", "tn_c8_dwconv_fwd", "tn_gconv_fwd", "tn_c8_gconv_fwd",
+                    "tn_dilconv_fwd", "tn_c8_dilconv_fwd")
     CONV_BWD_OPS = ("tn_conv2d_wgrad", "tn_conv2d_dgrad", "tn_convpool_bwd_mask_dx", "tn_convpool_bwd_mask",
                     "tn_convblock_bwd_mask", "tn_convblock_bwd", "tn_convpool_bwd", "tn_c8_conv_wgrad", "tn_c8_conv_dgrad",
                     "tn_c8_conv1_wgrad", "tn_c8_conv1_dgrad", "tn_dwconv_wgrad", "tn_dwconv_dgrad", "tn_c8_dwconv_wgrad",
-                    "tn_c8_dwconv_dgrad", "tn_gconv_wgrad", "tn_gconv_dgrad", "tn_c8_gconv_wgrad", "tn_c8_gconv_dgrad")
+                    "tn_c8_dwconv_dgrad", "tn_gconv_wgrad", "tn_gconv_dgrad", "tn_c8_gconv_wgrad", "tn_c8_gconv_dgrad",
+                    "tn_dilconv_wgrad", "tn_dilconv_dgrad", "tn_c8_dilconv_wgrad", "tn_c8_dilconv_dgrad")
 
     # step state (class-level: the twin of the pipelined schedule is given _is_twin / _main before its __init__ runs)
     _is_twin, _main = False, None     # the second net of a _PipeTrainFn (odd steps) and the net it is the twin of
