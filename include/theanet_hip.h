@@ -544,8 +544,14 @@ int tn_c8_dwconv_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, fl
  *   stored dz.  Slab sums in context scratch finished by the context's reduction: a slab count that depends on the
  *   geometry alone, no atomics, the same bits every run.
  * supported: tn_c8_convg_supported's consistency rule, and g >= 1 dividing C and K with C/g and K/g multiples of 8, at most
- *   65535 groups, f <= 255 and f f max(C/g, K/g) / 8 <= 4096.  Anything else, and any NULL tensor: TN_E_ARG naming the
- *   entry point, nothing launched.                                                                                       */
+ *   65535 groups, f <= 255 and f f max(C/g, K/g) / 8 <= 4096 -- or NARROW groups: C/g == K/g == 2 or 4 with C a multiple
+ *   of 8, f <= 255 and a smallest source tile (one cell, four units of 32 pixels with the filter's halo) that fits 64 KB of LDS.
+ *   Anything else, and any NULL tensor: TN_E_ARG naming the entry point, nothing launched.
+ * Narrow groups (gconv_c8_narrow.hip, the launchers' narrow branch; same arithmetic, same rules for pad cells and slabs):
+ *   an output cell reads the input cell with the same index alone.  fwd / dgrad on v_mfma_f32_4x4x4_16b: the 16 blocks are
+ *   the two half-cells of one cell at eight pixel quads, the B operand a ds_read_b64 of a stored half-cell from an LDS halo
+ *   tile, the A operand the tap's 4x4 weight block (groups of 2: two 2x2 blocks on its diagonal).  wgrad on fp32 FMAs, a
+ *   pixel a lane, lanes / waves / slabs added in fixed order.                                                            */
 int tn_c8_gconv_supported(int N, int C, int S, int P, int K, int g, int f, int stride, int pad, int So, int Po);
 int tn_c8_gconv_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, int N, int C, int S, int P, int K, int g,
                     int f, int stride, int pad, int So, int Po, int act, float prm);

@@ -39,6 +39,23 @@ static inline bool gc_axis_ok(int S, int f, int stride, int pad, int So) {
 
 static inline bool gc_groups_ok(int C, int K, int g) { return g >= 1 && C >= 1 && K >= 1 && C % g == 0 && K % g == 0; }
 
+// Narrow groups on the 16-bit stack (gconv_c8_narrow.hip): 2 or 4 maps a group in and out, whole cells of 8 in all -- an
+// output cell reads the input cell with the same index alone
+static inline bool gc_narrow(int C, int K, int g) {
+    return gc_groups_ok(C, K, g) && C == K && C % 8 == 0 && (C / g == 2 || C / g == 4);
+}
+// what they ask beyond the family's rule, and the narrow branches of tn_c8_gconv_* (c8b_: the bf16 unit's)
+bool gc8n_ok(int C, int S, int P, int f, int stride, int pad, int So, int Po);
+#define GC8N_DECLARE(pre)                                                                                                          \
+    int pre##gc8n_fwd(tn_ctx* ctx, const void* x, const float* W, const float* b, void* y, int N, int C, int S, int P, int g,     \
+                      int f, int stride, int pad, int So, int Po, int act, float prm);                                            \
+    int pre##gc8n_dgrad(tn_ctx* ctx, const void* dz, const float* W, void* dx, int N, int C, int S, int P, int g, int f,          \
+                        int stride, int pad, int So, int Po, const void* prev_a, int prev_act, float prev_prm);                   \
+    int pre##gc8n_wgrad(tn_ctx* ctx, const void* x, const void* dz, float* dW, float* db, int N, int C, int S, int P, int g,      \
+                        int f, int stride, int pad, int So, int Po);
+GC8N_DECLARE()
+GC8N_DECLARE(c8b_)
+
 // Slabs of a weight gradient whose grid has `cols` blocks a slab over `nt` pixel tiles: `target` blocks in all (a constant,
 // no CU count: the order of additions is the geometry's alone), at most one slab a tile.
 static inline unsigned gc_slabs(long long nt, long long cols, long long target) {

@@ -1,6 +1,7 @@
 // DTYPE 'float16' / 'bfloat16': ConvLayer(..., groups=g) on the 16-bit-resident c8 tensors of the conv stack
 // ([N][C/8][P][P][8] 16-bit values; x / dx: S x S maps at pitch P, y / dz: So x So maps at pitch Po): tn_c8_gconv_fwd / _dgrad /
-// _wgrad.  C/g and K/g are multiples of 8: a group is a whole number of 16-byte cells.  Arithmetic: the stack's (convg_c8.hip)
+// _wgrad.  C/g and K/g are multiples of 8: a group is a whole number of 16-byte cells -- or C/g == K/g == 2 or 4 with C a
+// multiple of 8: the launchers' narrow branch, gconv_c8_narrow.hip.  Arithmetic: the stack's (convg_c8.hip)
 // -- x and dz as stored, W rounded to the element type while it is arranged, exact products, fp32 accumulation on the matrix
 // core, bias / activation on the fp32 sums, one rounding on store; the weight gradient's fp32 epilogue removes the gradient
 // scale.  Filter orientation: tn_conv2d_*'s.
@@ -421,8 +422,11 @@ static long long gc8_cells(int N, int C, int S, int P) {
 }
 
 static bool gc8_ok(int N, int C, int S, int P, int K, int g, int f, int stride, int pad, int So, int Po) {
-    if (!gc_groups_ok(C, K, g) || g > 65535 || (C / g) % 8 || (K / g) % 8 || f > 255) return false;
+    if (!gc_groups_ok(C, K, g) || f > 255) return false;
+    const bool narrow = gc_narrow(C, K, g);        // groups of 2 or 4 maps in and out: gconv_c8_narrow.hip
+    if (!narrow && (g > 65535 || (C / g) % 8 || (K / g) % 8)) return false;
     if (!gc_axis_ok(S, f, stride, pad, So) || gc8_cells(N, C, S, P) < 0 || gc8_cells(N, K, So, Po) < 0) return false;
+    if (narrow) return (long long)K * (C / g) * f * f < (1ll << 28) && gc8n_ok(C, S, P, f, stride, pad, So, Po);
     const long long r8 = (C / g > K / g ? C / g : K / g) / 8;
     return (long long)f * f * r8 <= GC8_CELLS_MAX && (long long)K * (C / g) * f * f < (1ll << 28);
 }
@@ -507,6 +511,7 @@ int C8_API(tn_c8_gconv_fwd)(tn_ctx* ctx, const void* x, const float* W, const fl
     C8_TO_BF16(tn_c8_gconv_fwd, ctx, x, W, b, y, N, C, S, P, K, g, f, stride, pad, So, Po, act, prm);
     TN_REQUIRE(x && W && b && y && gc8_ok(N, C, S, P, K, g, f, stride, pad, So, Po),
                "tn_c8_gconv_fwd: bad arguments " GC8_ARGS_FMT, GC8_ARGS);
+    if (gc_narrow(C, K, g)) return C8_API(gc8n_fwd)(ctx, x, W, b, y, N, C, S, P, g, f, stride, pad, So, Po, act, prm);
     GC8 q{};
     q.src = static_cast<const uint4*>(x); q.out = static_cast<uint4*>(y); q.bias = b; q.act = act; q.prm = prm;
     q.Ss = S; q.Ps = P; q.PPs = (unsigned)P * P;
@@ -522,6 +527,8 @@ int C8_API(tn_c8_gconv_dgrad)(tn_ctx* ctx, const void* dz, const float* W, void*
     C8_TO_BF16(tn_c8_gconv_dgrad, ctx, dz, W, dx, N, C, S, P, K, g, f, stride, pad, So, Po, prev_a, prev_act, prev_prm);
     TN_REQUIRE(dz && W && dx && gc8_ok(N, C, S, P, K, g, f, stride, pad, So, Po),
                "tn_c8_gconv_dgrad: bad arguments " GC8_ARGS_FMT, GC8_ARGS);
+    if (gc_narrow(C, K, g))
+        return C8_API(gc8n_dgrad)(ctx, dz, W, dx, N, C, S, P, g, f, stride, pad, So, Po, prev_a, prev_act, prev_prm);
     GC8 q{};
     q.src = static_cast<const uint4*>(dz); q.out = static_cast<uint4*>(dx); q.prev_a = static_cast<const uint4*>(prev_a);
     q.act = prev_act; q.prm = prev_prm;
@@ -537,6 +544,7 @@ int C8_API(tn_c8_gconv_wgrad)(tn_ctx* ctx, const void* x, const void* dz, float*
     C8_TO_BF16(tn_c8_gconv_wgrad, ctx, x, dz, dW, db, N, C, S, P, K, g, f, stride, pad, So, Po);
     TN_REQUIRE(x && dz && dW && db && gc8_ok(N, C, S, P, K, g, f, stride, pad, So, Po),
                "tn_c8_gconv_wgrad: bad arguments " GC8_ARGS_FMT, GC8_ARGS);
+    if (gc_narrow(C, K, g)) return C8_API(gc8n_wgrad)(ctx, x, dz, dW, db, N, C, S, P, g, f, stride, pad, So, Po);
     GC8W q{};
     q.x = static_cast<const uint4*>(x); q.dz = static_cast<const uint4*>(dz);
     q.S = (unsigned)S; q.P = (unsigned)P; q.PP = (unsigned)P * P;

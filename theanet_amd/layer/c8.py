@@ -111,7 +111,8 @@ def choose_conv(lib, dtype, conv_shapes, n, c, side, in_pitch, k, f, stride, mod
     two up to 64 pixels (tn_c8_pack_pitch), dense above (tn_c8_pack); its output pitch is c8_pool_pitch(out_side), so
     that any layer of the stack can follow.  ``depthwise``: the per-channel family (dwconv_c8.hip) with the general
     family's pitches, under either ``conv_shapes`` -- it has no tiled form to prefer.  ``groups`` > 1: the grouped family
-    (gconv_c8.hip), likewise; a group must be a whole number of 16-byte cells (c / groups and k / groups multiples of 8).
+    (gconv_c8.hip), likewise; a group must be a whole number of 16-byte cells (c / groups and k / groups multiples of 8) or
+    narrow: 2 or 4 maps in and out, c == k a multiple of 8 (gconv_c8_narrow.hip, behind the same entry points).
     ``dilation`` > 1: the dilated family (dilconv_c8.hip), likewise, any c and k; ``pad_lo`` and ``out_side`` are those of
     the window (f - 1) dilation + 1."""
     if dilation > 1:
@@ -127,10 +128,11 @@ def choose_conv(lib, dtype, conv_shapes, n, c, side, in_pitch, k, f, stride, mod
         P = in_pitch if in_pitch is not None else c8_pool_pitch(side)
         Po = c8_pool_pitch(out_side)
         general = (f, stride, pad_lo, out_side, Po)
-        assert (c // groups) % 8 == 0 and (k // groups) % 8 == 0, (
+        narrow = c == k and c % 8 == 0 and c // groups in (2, 4)        # gconv_c8_narrow.hip
+        assert narrow or ((c // groups) % 8 == 0 and (k // groups) % 8 == 0), (
             "DTYPE {}: a grouped conv layer needs maps per group (C/g, K/g) that are multiples of 8 -- a group is a whole "
-            "number of 16-byte cells (got {} maps on {} in {} groups: {} on {} a group); float32 takes every divisor".format(
-                dtype, k, c, groups, k // groups, c // groups))
+            "number of 16-byte cells -- or groups of 2 or 4 maps in and out on a multiple of 8 maps (got {} maps on {} in {} "
+            "groups: {} on {} a group); float32 takes every divisor".format(dtype, k, c, groups, k // groups, c // groups))
         assert lib.tn_c8_gconv_supported(n, c, side, P, k, groups, *general), (
             "DTYPE {}: the grouped conv kernels refuse this layer (got {} maps on {} in {} groups, {}x{} at pitch {}, {} "
             "filter {} stride {}: {}x{} at pitch {})".format(dtype, k, c, groups, side, side, P, mode, f, stride, out_side,

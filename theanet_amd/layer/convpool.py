@@ -56,7 +56,8 @@ class ConvLayer(Layer):
         of group k // (num_maps / g) alone: W (K, C/g, f, f); any filter_sz, stride and mode, kernels of their own
         (tn_gconv_* / tn_c8_gconv_*), never fused with a pool.  Under CONV 'bfloat16' a grouped layer stays on its fp32 ops
         (no bf16-operand form).  On a 16-bit DTYPE C/g and K/g must be multiples of 8 (a group is a whole number of
-        16-byte cells) or construction fails; float32 takes every divisor.  groups=1 is the dense layer, unchanged.
+        16-byte cells), or both 2 or both 4 on a multiple of 8 maps (narrow groups, the ResNeXt 'x4d' shape: kernels on the
+        16-block 4x4x4 matrix instruction), or construction fails; float32 takes every divisor.  groups=1 is the dense layer, unchanged.
         ``dilation`` (d > 1, Theano's filter_dilation=(d, d)): the taps of the filter are d pixels apart -- the layer computes
         what a dense layer of filter_sz fe = (filter_sz - 1) d + 1 computes whose weights are W zero-stuffed, and takes its
         shape rules ('valid': out_sz = in_sz - fe + 1; 'same': the padding of fe); W stays (K, C, f, f) and fan_in / fan_out
